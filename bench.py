@@ -24,9 +24,11 @@ per-edge normal-equation blocks of its edges, [N > 1] all-gathers 36 doubles per
 
 Units (pairs / edges) are independent: each rank works on its own shard (weak scaling); inputs are resident in HBM
 before the timed region.  Weights are seeded random (no checkpoint can be fetched), data is synthetic - both stated
-in the JSON.  Prints ONE JSON line (rank 0) with the driver's contract plus `roofline` (dominant kernel = the 16-bit
-MFMA GEMM, algorithmic FLOPs / HIP-event time per launch) and `cpu_baseline` (the CPU oracle timed on this host,
-rank 0, N = 1 only, on a bounded sample).
+in the JSON.  Prints ONE JSON line (rank 0) with the driver's contract (metric, value, unit, ms_per_step, dtype, ...),
+the per-stage device times of the timed steps and the checks that the legs ran on accepted points.  `--full` adds,
+after the timed steps, `roofline` (dominant kernel = the 16-bit MFMA GEMM, algorithmic FLOPs / HIP-event time per
+launch), the other measurements outside the timed step and `cpu_baseline` (the CPU oracle timed on this host, rank 0,
+N = 1 only, on a bounded sample).  `--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -54,7 +56,15 @@ def parse(argv=None):
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", choices=("pairs", "backend"), default="pairs")
     ap.add_argument("--pairs-per-gpu", type=int, default=8)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure everything beyond the headline: per-kernel rooflines from an "
+                         "instrumented pass, the extra measurements (batch 1, other trunk precision, fp16 features, fast NN, "
+                         "calibrated tracking, backend block, dist_overhead) and the CPU baseline.  Without it a run sets up, "
+                         "warms up, times --steps steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float32 / float64; a fixed "
+                         "seeded sample of every array too large for its share of 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--matcher", choices=["iter_proj", "fast_nn"], default="iter_proj",
                     help="match leg of the pairs workload: the reference's dense matcher (iter_proj + refine_matches, default) or "
                          "the fast reciprocal nearest-neighbour matcher BASELINE.json's north_star names (MFMA search, fp16 descriptors)")
@@ -68,8 +78,8 @@ def parse(argv=None):
     ap.add_argument("--force-dist", action="store_true",
                     help="initialise torch.distributed (RCCL) and run the collectives even with one rank")
     ap.add_argument("--dist-overhead", action="store_true",
-                    help="also measure the dist_overhead block with --model tiny (always on for the full model unless --no-b1)")
-    ap.add_argument("--no-b1", action="store_true", help="skip the extra measurements outside the timed step (batch 1, fp16 features, fast NN)")
+                    help="with --full: also measure the dist_overhead block with --model tiny (always on for the full model unless --no-b1)")
+    ap.add_argument("--no-b1", action="store_true", help="with --full: skip the extra measurements outside the timed step (batch 1, fp16 features, fast NN)")
     # backend workload (BASELINE configs[4])
     ap.add_argument("--keyframes", type=int, default=256)
     ap.add_argument("--edges-per-gpu", type=int, default=96, help="undirected edges per rank (762 / 8 rounded up)")
@@ -236,6 +246,27 @@ def hbm_rows(cprof, rows):
     return out
 
 
+DUMP_BYTES = 60 * 10**6              # --dump-outputs: array bytes written in all (64 MB with the .npy headers and to spare)
+
+
+def dump_outputs(outs, out_dir):
+    """--dump-outputs: every tensor of `outs` ({name: tensor}) as out_dir/<name>.npy - floating types of up to 32 bits as
+    float32, everything else (float64, integer indices, boolean masks) as float64, exact for integers below 2**53.  A
+    tensor larger than its share of DUMP_BYTES is written as a fixed sample of its flattened elements (seed 0, positions
+    ascending), so that two runs of the same command write the same positions."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BYTES // max(len(outs), 1)
+    for name, t in outs.items():
+        dt = torch.float32 if t.is_floating_point() and t.element_size() <= 4 else torch.float64
+        keep = share // (4 if dt == torch.float32 else 8)
+        if t.numel() > keep:
+            pos = np.random.default_rng(0).choice(t.numel(), keep, replace=False, shuffle=False)
+            t = t.reshape(-1)[torch.from_numpy(np.sort(pos)).to(t.device)]
+        np.save(os.path.join(out_dir, f"{name}.npy"), t.detach().to(dt).cpu().numpy())
+
+
 # ----------------------------------------------------------------------------------------------------------------
 class StubWorkload:
     """--stub: a step is one small tensor operation on the CPU plus (N > 1) one gloo all-gather - no device, no
@@ -262,6 +293,9 @@ class StubWorkload:
 
     def drain(self):
         pass
+
+    def outputs(self):
+        return {"x": self.x}
 
     def report(self, result, args):
         result["data"] = "stub"
@@ -421,6 +455,15 @@ class PairsWorkload:
         if self.gather is not None:
             self.gathered = self.gather.wait()                      # the last step's gather belongs to the timed region
 
+    def outputs(self):
+        """What a caller of the step receives: both views' network outputs, the match maps and the tracking solve."""
+        st = self.state
+        poses, T_rel, info, vo = st["gn"]
+        out = {f"view{v}_{k}": t for v, o in ((1, st["o1"]), (2, st["o2"])) for k, t in o.items()
+               if isinstance(t, self.torch.Tensor)}
+        out.update(match_idx=st["idx"], match_valid=st["valid"], T_WC=poses, T_rel=T_rel, gn_info=info, gn_valid=vo)
+        return out
+
     def report(self, result, args):
         torch, np, P, ctx, sc, n, tcfg = self.torch, self.np, self.P, self.ctx, self.sc, self.n, self.tcfg
         from mast3r_slam import _ffi, ops
@@ -451,39 +494,7 @@ class PairsWorkload:
         elif match_valid_frac < 0.5 or valid_frac < 0.5:
             raise SystemExit(f"bench invalid: match_valid_frac={match_valid_frac:.3f} valid_frac={valid_frac:.3f} (< 0.5): "
                              "the matcher / Gauss-Newton legs would be timed on rejected points")
-        # ---- untimed instrumented pass (eager, launches serialised): per-launch device time by kernel family ----
-        ops.PROFILE = []
-        _ffi.PROFILE = {}
-        _ffi.PROFILE_NAMES = ("m3_prep_iter_proj", "m3_iter_proj", "m3_refine_matches", "m3_match_epilogue",
-                              "m3_track_gather_batch", "m3_track_gn_ray_dist_batch")
-        if self.graphs is not None:
-            # queue-ahead: two replays of the inference graph (~50 ms of device work) go first, so the eager launches below pile
-            # up BEHIND them in the stream and run back to back as they do inside the graph - an event pair then brackets the
-            # kernel's device time (what rocprofv3 reports for the timed replays), not the host's launch latency in front of
-            # an idle GPU (r04: 100.2 us per dense launch by events against 92.8 us by rocprofv3 for this reason)
-            for _ in range(2):
-                self.graphs[0].replay()
-        self.leg_infer(); i2, v2 = self.leg_match(); self.leg_gn(i2, v2)           # single stream: the launches are serialised
-        torch.cuda.synchronize()
-        prof, ops.PROFILE = ops.PROFILE, None
-        cprof, _ffi.PROFILE = _ffi.PROFILE, None
         iters = int(tcfg["max_iters"])
-        # HBM-bound kernel families: algorithmic bytes per call from SURVEY 8d (per pair at 512x512, fp32) x P pairs
-        scale = P * (self.h * self.w) / (512 * 512)
-        hbm = hbm_rows(cprof, {
-            "m3_prep_iter_proj": ("k_prep", 21.0 * MB * scale, 1),
-            "m3_iter_proj": ("k_iter_proj (+ k_iter_reduce / k_iter_limit, early-stop second pass)", 17.0 * MB * scale, 1),
-            "m3_refine_matches": ("k_refine_lds<24> / k_refine<24>", 54.5 * MB * scale, 1),
-            "m3_match_epilogue": ("k_epilogue", 9.7 * MB * scale, 1),
-            "m3_track_gather_batch": ("k_track_gather", (3.15 + 4 * 1.05 + 2.1 + 0.26 + 3.15 + 1.05 + 0.52) * MB * scale, 1),
-            "m3_track_gn_ray_dist_batch": (f"k_track_accum + k_track_solve, per GN iteration ({iters} per call)", 8.7 * MB * scale, iters),
-        })
-        valu = valu_rows(cprof, {
-            "m3_iter_proj": ("k_iter_proj", (57.8e6 + 2 * 28.9e6) / 8 * scale,
-                             "264 VALU instructions per LM step and point, a third of them float64 (numpy-twin interpolation)"),
-            "m3_refine_matches": ("k_refine_lds<24, float, 3>", 98.8e6 / 8 * scale,
-                                  "49 x 24 separately rounded multiply + add per point (bit-exact summation order)"),
-        })
         world = ctx.world
         result.update({
             "data": "synthetic: 512x512 textured pairs through the network (seeded random-init weights, no checkpoint available "
@@ -505,10 +516,42 @@ class PairsWorkload:
             "valid_frac": round(valid_frac, 4),
             "gn_pose_max_abs_err_vs_true_sim3": pose_err,
             "model_tflop_per_step": self.net.flops_per_pair(self.h, self.w) * P / 1e12,
-            "roofline": gemm_roofline(prof),
-            "hbm_rooflines": hbm,
-            "valu_rooflines": valu,
         })
+        if not args.full:
+            return
+        # ---- untimed instrumented pass (eager, launches serialised): per-launch device time by kernel family ----
+        ops.PROFILE = []
+        _ffi.PROFILE = {}
+        _ffi.PROFILE_NAMES = ("m3_prep_iter_proj", "m3_iter_proj", "m3_refine_matches", "m3_match_epilogue",
+                              "m3_track_gather_batch", "m3_track_gn_ray_dist_batch")
+        if self.graphs is not None:
+            # queue-ahead: two replays of the inference graph (~50 ms of device work) go first, so the eager launches below pile
+            # up BEHIND them in the stream and run back to back as they do inside the graph - an event pair then brackets the
+            # kernel's device time (what rocprofv3 reports for the timed replays), not the host's launch latency in front of
+            # an idle GPU (r04: 100.2 us per dense launch by events against 92.8 us by rocprofv3 for this reason)
+            for _ in range(2):
+                self.graphs[0].replay()
+        self.leg_infer(); i2, v2 = self.leg_match(); self.leg_gn(i2, v2)           # single stream: the launches are serialised
+        torch.cuda.synchronize()
+        prof, ops.PROFILE = ops.PROFILE, None
+        cprof, _ffi.PROFILE = _ffi.PROFILE, None
+        # HBM-bound kernel families: algorithmic bytes per call from SURVEY 8d (per pair at 512x512, fp32) x P pairs
+        scale = P * (self.h * self.w) / (512 * 512)
+        hbm = hbm_rows(cprof, {
+            "m3_prep_iter_proj": ("k_prep", 21.0 * MB * scale, 1),
+            "m3_iter_proj": ("k_iter_proj (+ k_iter_reduce / k_iter_limit, early-stop second pass)", 17.0 * MB * scale, 1),
+            "m3_refine_matches": ("k_refine_lds<24> / k_refine<24>", 54.5 * MB * scale, 1),
+            "m3_match_epilogue": ("k_epilogue", 9.7 * MB * scale, 1),
+            "m3_track_gather_batch": ("k_track_gather", (3.15 + 4 * 1.05 + 2.1 + 0.26 + 3.15 + 1.05 + 0.52) * MB * scale, 1),
+            "m3_track_gn_ray_dist_batch": (f"k_track_accum + k_track_solve, per GN iteration ({iters} per call)", 8.7 * MB * scale, iters),
+        })
+        valu = valu_rows(cprof, {
+            "m3_iter_proj": ("k_iter_proj", (57.8e6 + 2 * 28.9e6) / 8 * scale,
+                             "264 VALU instructions per LM step and point, a third of them float64 (numpy-twin interpolation)"),
+            "m3_refine_matches": ("k_refine_lds<24, float, 3>", 98.8e6 / 8 * scale,
+                                  "49 x 24 separately rounded multiply + add per point (bit-exact summation order)"),
+        })
+        result.update({"roofline": gemm_roofline(prof), "hbm_rooflines": hbm, "valu_rooflines": valu})
         if world == 1 and not args.no_b1:
             self._extras(result, args)
             if args.model == "full" or args.dist_overhead:
@@ -952,6 +995,16 @@ class BackendWorkload:
     def drain(self):
         pass
 
+    def outputs(self):
+        """What a caller of the step receives: every keyframe's pose after the solve, the graph's edges and the matches
+        of the edges this rank stores."""
+        fg = self.fg
+        out = {"T_WC": self.torch.cat([f.T_WC for f in self.frames._frames]), "edge_ii": fg.ii, "edge_jj": fg.jj}
+        for k in ("idx_ii2jj", "idx_jj2ii", "valid_match_j", "valid_match_i", "Q_ii2jj", "Q_jj2ii"):
+            if getattr(fg, k) is not None:
+                out[k] = getattr(fg, k)
+        return out
+
     def report(self, result, args):
         torch, np, ctx, sc = self.torch, self.np, self.ctx, self.scene
         from mast3r_slam import _ffi, kernels, ops
@@ -968,6 +1021,32 @@ class BackendWorkload:
         err1 = float((cur - sc["poses"][touched]).abs().max())
         if vm < 0.5 or kept < 0.9 * self.total_edges:
             raise SystemExit(f"bench invalid: match_valid_frac={vm:.3f}, {kept} of {self.total_edges} edges kept")
+        e_dir = 2 * (int(fg.idx_ii2jj.shape[0]) if fg.idx_ii2jj is not None else 0)     # this rank's directed edges
+        _, local_h, num_free = kernels._local_map(np.arange(self.K), np.arange(self.K), self.K, self.lcfg["pin"])
+        dim = 7 * num_free
+        world = ctx.world
+        per_edge_tflop = 2 * (self.net.flops_per_pair(self.h, self.w) - 2 * self._enc_flops())
+        result.update({
+            "data": "synthetic: cached encoder tokens (random, unit scale) through the decoders + heads (seeded random-init weights, "
+                    "no checkpoint available offline); matcher + Gauss-Newton blocks on a synthetic 256-keyframe graph of the same "
+                    "size (circular trajectory over one smooth surface, SURVEY 8d config 5), fp16 descriptors; the matcher's input maps "
+                    "of every edge batch (what the decoder would hand it) are assembled once and stay resident in HBM",
+            "config": {"workload": f"{len(self.mine)} of {self.total_edges} graph edges per GPU, {self.K} keyframes at {self.h}x{self.w} "
+                                   f"(BASELINE configs[4] per-GPU shard): symmetric decode from cached tokens ({self.dtype} trunk, fp16 heads) "
+                                   "+ iter_proj/refine match in both directions on fp16 features + rays-GN blocks of the rank's "
+                                   f"{e_dir} directed edges" + ("" if ctx.dist is None else " + RCCL all-gather of 36 doubles per directed edge")
+                                   + f" + {dim}-unknown step ({args.gn_iters} GN iteration per step)",
+                       "keyframes": self.K, "edges_per_gpu": len(self.mine), "global_edges": self.total_edges,
+                       "edge_batch": args.edge_batch, "image": [self.h, self.w], "gn_iters": args.gn_iters,
+                       "parallelism": f"edge-sharded x{world}", "launch": "eager (add_factors has one host sync per call, as the reference)"},
+            "stage_ms": {k: round(v, 3) for k, v in stage_ms.items()},
+            "stage_ms_note": "device time between stream events around add_factors (decode + match) and solve_GN_rays of every TIMED step",
+            "match_valid_frac": round(vm, 4), "edges_kept": kept,
+            "pose_max_abs_err_before_after": [err0, err1],
+            "model_tflop_per_step": per_edge_tflop * len(self.mine) / 1e12,
+        })
+        if not args.full:
+            return
         # ---- instrumented eager pass: one decode chunk by kernel family, the block kernel and the dense step alone ----
         b = min(args.edge_batch, len(self.mine))
         sel = list(self.mine)[:b]
@@ -982,7 +1061,6 @@ class BackendWorkload:
         uniq = fg.get_unique_kf_idx()
         Xs, T_WCs, Cs = fg._get_poses_points(uniq)
         li, lj, lidx, lvalid, lQ, graph = fg._local_edges(uniq)
-        e_dir = int(li.numel())
         _ffi.PROFILE = {}
         _ffi.PROFILE_NAMES = ("m3_gn_rays_blocks", "m3_gn_rays_step", "m3_iter_proj", "m3_refine_matches_f16", "m3_prep_iter_proj",
                               "m3_match_epilogue")
@@ -991,9 +1069,7 @@ class BackendWorkload:
                                             C_thresh=self.lcfg["C_conf"], Q_thresh=self.lcfg["Q_conf"])
         # the dense step on this rank's blocks (at N = 1 that is the whole system; the keyframes without an edge keep the
         # regularised identity rows): assembly + blocked Cholesky of 7 (K - 1) unknowns + retraction
-        _, local_h, num_free = kernels._local_map(np.arange(self.K), np.arange(self.K), self.K, self.lcfg["pin"])
         L = _ffi.lib()
-        dim = 7 * num_free
         hbuf = torch.empty(int(L.m3_gn_rays_hbuf_doubles(dim)), dtype=torch.float64, device=ctx.dev)
         info = torch.zeros(4, dtype=torch.float64, device=ctx.dev)
         local = torch.from_numpy(local_h).to(ctx.dev)
@@ -1019,26 +1095,7 @@ class BackendWorkload:
         })
         step_evs = cprof.get("m3_gn_rays_step", [])
         chol_us = sum(a.elapsed_time(c) for a, c in step_evs[1:]) / max(len(step_evs) - 1, 1) * 1e3
-        world = ctx.world
-        per_edge_tflop = 2 * (self.net.flops_per_pair(self.h, self.w) - 2 * self._enc_flops())
         result.update({
-            "data": "synthetic: cached encoder tokens (random, unit scale) through the decoders + heads (seeded random-init weights, "
-                    "no checkpoint available offline); matcher + Gauss-Newton blocks on a synthetic 256-keyframe graph of the same "
-                    "size (circular trajectory over one smooth surface, SURVEY 8d config 5), fp16 descriptors; the matcher's input maps "
-                    "of every edge batch (what the decoder would hand it) are assembled once and stay resident in HBM",
-            "config": {"workload": f"{len(self.mine)} of {self.total_edges} graph edges per GPU, {self.K} keyframes at {self.h}x{self.w} "
-                                   f"(BASELINE configs[4] per-GPU shard): symmetric decode from cached tokens ({self.dtype} trunk, fp16 heads) "
-                                   "+ iter_proj/refine match in both directions on fp16 features + rays-GN blocks of the rank's "
-                                   f"{e_dir} directed edges" + ("" if ctx.dist is None else " + RCCL all-gather of 36 doubles per directed edge")
-                                   + f" + {dim}-unknown step ({args.gn_iters} GN iteration per step)",
-                       "keyframes": self.K, "edges_per_gpu": len(self.mine), "global_edges": self.total_edges,
-                       "edge_batch": args.edge_batch, "image": [self.h, self.w], "gn_iters": args.gn_iters,
-                       "parallelism": f"edge-sharded x{world}", "launch": "eager (add_factors has one host sync per call, as the reference)"},
-            "stage_ms": {k: round(v, 3) for k, v in stage_ms.items()},
-            "stage_ms_note": "device time between stream events around add_factors (decode + match) and solve_GN_rays of every TIMED step",
-            "match_valid_frac": round(vm, 4), "edges_kept": kept,
-            "pose_max_abs_err_before_after": [err0, err1],
-            "model_tflop_per_step": per_edge_tflop * len(self.mine) / 1e12,
             "roofline": gemm_roofline(prof, "_backend"),
             "hbm_rooflines": hbm,
             "dense_step": {"unknowns": dim, "avg_us": chol_us,
@@ -1119,6 +1176,8 @@ def run_rank(args) -> int:
         wl.step(timed=True)
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(wl.outputs(), args.dump_outputs)
     if dist is not None:
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev if dist.get_backend() == "nccl" else "cpu")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)

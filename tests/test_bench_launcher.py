@@ -6,6 +6,8 @@ import os
 import subprocess
 import sys
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BENCH = os.path.join(ROOT, "bench.py")
 
@@ -48,3 +50,24 @@ def test_a_failing_rank_fails_the_launcher():
     assert r.returncode != 0
     assert "rank 1 exited with status" in r.stderr
     assert not [l for l in r.stdout.splitlines() if l.startswith("{")]
+
+
+def test_dump_outputs_writes_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: what the last timed step computed, as DIR/<name>.npy in float32; the same command writes the same
+    arrays, and --steps sets how many steps that is (the stub's state is scaled by 1.0001 per step)."""
+    runs = {}
+    for tag, steps in (("a", 3), ("b", 3), ("c", 5)):
+        r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--stub", "--steps", str(steps), "--warmup", "1",
+                            "--dump-outputs", str(tmp_path / tag)], capture_output=True, text=True, timeout=300, env=_env(), cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        res = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert res["steps"] == steps and res["ms_per_step"] > 0
+        runs[tag] = np.load(tmp_path / tag / "x.npy")
+    a = runs["a"]
+    assert a.dtype == np.float32 and a.shape == (64,)
+    assert np.array_equal(a, runs["b"])
+    ref = np.arange(64, dtype=np.float32)
+    for _ in range(1 + 3):                                            # one warm-up step + three timed steps
+        ref = ref * np.float32(1.0001)
+    assert np.array_equal(a, ref)
+    assert not np.array_equal(a, runs["c"])

@@ -32,12 +32,27 @@ def _bench(extra, port):
     return json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
 
 
-def test_pairs_workload_at_the_config4_shard_size():
-    res = _bench(["--model", "tiny", "--pairs-per-gpu", "8"], 29621)
+def test_pairs_workload_at_the_config4_shard_size(tmp_path):
+    """A plain run (no --full): the headline line and, with --dump-outputs, the last timed step's results - both views'
+    network outputs, the match maps and the solve - within the 64 MB bound, as float32 / float64."""
+    res = _bench(["--model", "tiny", "--pairs-per-gpu", "8", "--dump-outputs", str(tmp_path)], 29621)
     assert res["n_gpus"] == 1 and res["config"]["pairs_per_gpu"] == 8 and res["config"]["image"] == [512, 512]
     assert res["ranks"]["backend"] == "nccl" and "RCCL all-gather" in res["config"]["launch"]
     assert res["match_valid_frac"] > 0.5 and res["valid_frac"] > 0.5 and res["gn_pose_max_abs_err_vs_true_sim3"] < 5e-3
     assert res["value"] > 0 and abs(res["value"] - 8 / (res["ms_per_step"] * 1e-3)) < 1e-6 * res["value"]
+    assert not {"roofline", "hbm_rooflines", "backend", "batch1", "cpu_baseline"} & set(res)       # --full only
+    files = {f.stem: f for f in tmp_path.glob("*.npy")}
+    assert {"view1_pts3d", "view2_pts3d", "view1_desc", "match_idx", "match_valid", "T_rel", "gn_info"} <= set(files)
+    assert sum(f.stat().st_size for f in files.values()) <= 64 * 10**6
+    arr = {k: np.load(f) for k, f in files.items()}
+    assert all(a.dtype in (np.float32, np.float64) for a in arr.values())
+    assert np.isfinite(arr["view1_pts3d"]).all() and arr["T_rel"].shape == (8, 8)
+    idx = arr["match_idx"]
+    assert (idx == np.round(idx)).all() and 0 <= idx.min() and idx.max() < 512 * 512
+    # the dumped solve is the one the line reports on: the scene's Sim(3) is 2 degrees about y, t = (0.05, 0, 0.01), s = 1.02
+    a = np.deg2rad(2.0)
+    T_true = np.array([0.05, 0.0, 0.01, 0.0, np.sin(a / 2), 0.0, np.cos(a / 2), 1.02])
+    assert abs(np.abs(arr["T_rel"] - T_true).max() - res["gn_pose_max_abs_err_vs_true_sim3"]) < 1e-6
 
 
 def test_pairs_workload_with_the_fast_reciprocal_nn_matcher():
@@ -54,7 +69,7 @@ def test_pairs_workload_with_the_fast_reciprocal_nn_matcher():
 
 
 def test_default_line_carries_a_backend_block():
-    """The driver runs the default command only, so BASELINE configs[4] is part of ITS line: after the timed region the
+    """BASELINE configs[4] is part of the default workload's `--full` line: after the timed region the
     pairs workload runs 16 undirected edges of the 256-keyframe graph through the full network (symmetric decode from cached
     tokens + both match directions on fp16 features), the rays-GN blocks and the 1785-unknown dense step (reference flow
     slam.py:292-319 -> global_opt.py:49-166).  The block must be there, on valid matches, and its one Gauss-Newton iteration
@@ -62,7 +77,7 @@ def test_default_line_carries_a_backend_block():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"],
                        capture_output=True, text=True, timeout=1200, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     res = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -81,7 +96,7 @@ def test_backend_workload_small_graph_end_to_end():
     """12 keyframes, 6 undirected edges on this rank, reduced-depth network, 256 x 256: decode from cached tokens, both
     matching directions with fp16 features, blocks, one-rank RCCL gather of the blocks, dense step."""
     res = _bench(["--workload", "backend", "--model", "tiny", "--keyframes", "12", "--edges-per-gpu", "6", "--edge-batch", "4",
-                  "--image", "256", "256", "--gn-iters", "3"], 29622)
+                  "--image", "256", "256", "--gn-iters", "3", "--full"], 29622)
     assert res["unit"] == "edges/s" and res["n_gpus"] == 1 and res["config"]["edges_per_gpu"] == 6
     assert res["edges_kept"] == 6 and res["match_valid_frac"] > 0.7     # 256 x 256: the 40-px trajectory moves ~15 % of the pixels out of view
     e0, e1 = res["pose_max_abs_err_before_after"]
