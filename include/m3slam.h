@@ -341,6 +341,34 @@ int m3_gn_rays_step(float *Twc, const double *blocks, const int32_t *ii, const i
 int64_t m3_chol_ws_doubles(int dim);
 int m3_chol_solve(double *H, double *b, double *x, double *ws, int dim, double shift, void *stream);
 
+/* ----------------------------------------------------------------- retrieval */
+
+/* Keyframe retrieval database, "simple retrieval" of RetrievalDatabase (mast3r_utils.py:696-715 compute_signature,
+ * :717-795 update / query).  Host side: mast3r_slam/retrieval.py.
+ *
+ * Signature: sig[b] = m / sqrt(sum(m^2) + 1e-8) with m = mean over t of feat[b, t, :], fp32 throughout.  feat [B,T,C]
+ * contiguous, 16-byte aligned, dtype M3_RETRIEVAL_BF16 / _F16 (the M3_DT_BF16 / M3_DT_F16 codes of m3slam_model.h) or
+ * _F32; T >= 1, C a multiple of 8.  Row b is written at sig + b * sig_stride (floats): a database row is the output.
+ * The token sum is split into 32-row slices whose column sums (ws: m3_retrieval_signature_ws_bytes bytes) are added in
+ * slice order by a second launch; no atomics, so a row's bits depend on its own tokens only (not on B or its position).
+ *
+ * Top-k: score(q, n) = <qsig[q], db[n]> in fp32 with an order fixed by C alone.  Query q sees database rows [0, N), or
+ * [0, N + q) with causal = 1 (a batch of queries whose signatures are rows N, N+1, ... of the same buffer: each sees
+ * only the rows inserted before it).  Per query: idx [Q,k] int32 and score [Q,k] fp32 in descending score, equal
+ * scores to the LARGER row index first (a reversed stable ascending argsort), count [Q] int32 = number kept
+ * (<= min(k, rows seen)); with use_thresh = 1 only scores > min_thresh are kept.  Unused slots: idx -1, score 0.
+ * qsig [Q,ldq], db [>= N (+Q-1), ldd] fp32, 16-byte aligned, ldq / ldd multiples of 4; 1 <= k <= 64; C <= 8192
+ * (else M3_ERR_UNSUPPORTED).  ws: m3_retrieval_ws_bytes(N, Q, k, causal) bytes, 16-byte aligned.  Two launches:
+ * per-row-block scores and partial top-k, then a per-query merge. */
+enum { M3_RETRIEVAL_BF16 = 0, M3_RETRIEVAL_F16 = 1, M3_RETRIEVAL_F32 = 3 };
+int64_t m3_retrieval_signature_ws_bytes(int B, int T, int C);
+int m3_retrieval_signature(const void *feat, float *sig, int64_t sig_stride, float *ws, int64_t ws_bytes, int B, int T,
+                           int C, int dtype, void *stream);
+int64_t m3_retrieval_ws_bytes(int N, int Q, int k, int causal);
+int m3_retrieval_topk(const float *qsig, int64_t ldq, const float *db, int64_t ldd, int N, int Q, int C, int k,
+                      int use_thresh, float min_thresh, int causal, int32_t *count, int32_t *idx, float *score, void *ws,
+                      int64_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -150,6 +150,10 @@ class Keyframes:
     def last_keyframe(self) -> Optional[Frame]:
         return self._frames[-1] if self._frames else None
 
+    def pop_last(self) -> Optional[Frame]:
+        """frame.py:197-201: remove and return the last keyframe (None when empty)."""
+        return self._frames.pop() if self._frames else None
+
     def update_T_WCs(self, T_WCs: torch.Tensor, idx) -> None:
         """frame.py:236-246: write optimised poses ([M,8]) back to keyframes idx ([M])."""
         ids = idx.tolist() if isinstance(idx, torch.Tensor) else list(idx)

@@ -12,8 +12,8 @@ Differences, on purpose:
     identity matches / zeros (:556-569, :611-616).
   * cached `frame.feat` is reused; the reference re-encodes both images on every call (:345-355).
   * *_batch variants take P pairs at once (the data-parallel unit that shards across GPUs).
-resize_img (:132-207) is the same host-side PIL preprocessing; the retrieval database (:640-795) is
-outside the hot path and not provided.
+resize_img (:132-207) is the same host-side PIL preprocessing.  The retrieval database (load_retriever :83-114,
+RetrievalDatabase :640-795, simple retrieval only) lives in mast3r_slam/retrieval.py and is re-exported here.
 """
 from __future__ import annotations
 
@@ -25,11 +25,12 @@ import torch
 from .config import get_config
 from .model import Mast3rFull
 from . import matching
+from .retrieval import RetrievalDatabase, load_retriever
 
 __all__ = [
     "load_mast3r", "resize_img", "frame_to_numpy", "downsample", "mast3r_inference_mono", "mast3r_asymmetric_inference",
     "mast3r_symmetric_inference", "mast3r_match_asymmetric", "mast3r_match_symmetric",
-    "mast3r_decode_symmetric_batch", "mast3r_match_asymmetric_batch",
+    "mast3r_decode_symmetric_batch", "mast3r_match_asymmetric_batch", "load_retriever", "RetrievalDatabase",
 ]
 
 

@@ -1,9 +1,14 @@
 """Minimal SLAM driver over the hot-path operators: the control flow of
 /root/reference/src/mlx_mast3r_slam/slam.py (:124-153 main loop, :159-214 INIT / TRACKING,
-:292-318 backend) with the retrieval database left out - a frame that cannot be tracked is
-re-initialised as a new keyframe (the reference's "no similar keyframes" branch, :280-286).
-It exists to show the operator API dropping in under the loop and to test it end to end; dataset
-readers, trajectory writers and visualisation stay out of scope.
+:216-290 RELOC, :292-318 backend).  It exists to show the operator API dropping in under the loop and to
+test it end to end; dataset readers, trajectory writers and visualisation stay out of scope.
+
+Relocalization is opt-in: SLAM(model, retrieval=db_or_True) keeps a keyframe retrieval database
+(mast3r_slam/retrieval.py) fed on INIT and on every new keyframe, and a frame that cannot be tracked is matched
+against the retrieved keyframes (:216-290).  With retrieval=None (the default) a frame that cannot be tracked is
+re-initialised as a new keyframe at the last keyframe's pose (the reference's "no similar keyframes" branch,
+:280-286).  loop_closure=True (an extension, also opt-in) adds each new keyframe's retrieved candidates outside the
+three-keyframe window to its backend edges; the reference computes these candidates (:211) and discards them.
 """
 from __future__ import annotations
 
@@ -16,13 +21,14 @@ from .config import get_config
 from .frame import Keyframes, create_frame
 from .global_opt import FactorGraph
 from .mast3r_utils import mast3r_inference_mono, mast3r_match_asymmetric, mast3r_match_symmetric
+from .retrieval import RetrievalDatabase, load_retriever
 from .tracker import FrameTracker, sim3_act
 
 INIT, TRACKING, RELOC = "INIT", "TRACKING", "RELOC"
 
 
 class SLAM:
-    def __init__(self, model, K: Optional[torch.Tensor] = None) -> None:
+    def __init__(self, model, K: Optional[torch.Tensor] = None, retrieval=None, loop_closure: bool = False) -> None:
         self.model = model
         self.config = get_config()
         self.keyframes = Keyframes()
@@ -34,6 +40,16 @@ class SLAM:
         self._queue: deque[int] = deque()
         self.timestamps: list = []
         self.poses: list[torch.Tensor] = []
+        # retrieval: a RetrievalDatabase, True (one built by load_retriever) or None (no relocalization database)
+        if retrieval is True:
+            retrieval = load_retriever(model)
+        if retrieval is not None and not isinstance(retrieval, RetrievalDatabase):
+            raise TypeError(f"retrieval must be a RetrievalDatabase, True or None, got {type(retrieval).__name__}")
+        self.retrieval_db: Optional[RetrievalDatabase] = retrieval
+        if loop_closure and retrieval is None:
+            raise ValueError("loop_closure=True needs a retrieval database (retrieval=True or a RetrievalDatabase)")
+        self.loop_closure = bool(loop_closure)
+        self.retrieval_candidates: dict[int, list[int]] = {}     # keyframe index -> keyframes retrieved when it was added
 
     # ------------------------------------------------------------------ slam.py:124-153
     def run(self, frames: Iterable, callback: Optional[Callable] = None) -> dict:
@@ -65,9 +81,21 @@ class SLAM:
         self.keyframes.append(frame)
         self._queue.append(len(self.keyframes) - 1)
 
+    def _retrieval_update(self, frame, add_after_query: bool) -> list[int]:
+        r = self.config.get("retrieval", {})            # absent from DEFAULT_CONFIG: the reference's values (config.py)
+        return self.retrieval_db.update(frame, add_after_query=add_after_query, k=r.get("k", 3),
+                                        min_thresh=r.get("min_thresh", 0.005))
+
+    def _register_keyframe(self, frame) -> None:
+        """Database row i is keyframe i: insert the keyframe just appended and keep what it retrieved."""
+        self.retrieval_candidates[len(self.keyframes) - 1] = self._retrieval_update(frame, add_after_query=True)
+        assert len(self.retrieval_db) == len(self.keyframes)
+
     def _process_init(self, frame) -> None:             # :159-182
         self._mono(frame)
         self._add_keyframe(frame)
+        if self.retrieval_db is not None:
+            self._register_keyframe(frame)
         self.mode = TRACKING
 
     def _process_tracking(self, frame) -> None:         # :184-214
@@ -79,8 +107,13 @@ class SLAM:
         if new_kf:
             self._mono(frame)
             self._add_keyframe(frame)
+            if self.retrieval_db is not None:
+                self._register_keyframe(frame)
 
-    def _process_reloc(self, frame) -> None:            # :216-290 without the retrieval database
+    def _process_reloc(self, frame) -> None:            # :216-290
+        if self.retrieval_db is not None:
+            self._process_reloc_retrieval(frame)
+            return
         self._mono(frame)
         last = self.keyframes.last_keyframe()
         if last is not None:
@@ -89,11 +122,38 @@ class SLAM:
         self.mode = TRACKING
         self.tracker.reset_idx_f2k()
 
+    def _process_reloc_retrieval(self, frame) -> None:  # :216-290 with the retrieval database
+        self._mono(frame)
+        candidates = self._retrieval_update(frame, add_after_query=False)
+        if candidates:
+            self.keyframes.append(frame)
+            kf_idx = len(self.keyframes) - 1
+            min_match_frac = self.config["reloc"]["min_match_frac"]
+            for cand in candidates:
+                if self.factor_graph.add_factors([kf_idx], [cand], min_match_frac, mast3r_match_fn=mast3r_match_symmetric):
+                    frame.T_WC = self.keyframes[cand].T_WC.clone()
+                    self._register_keyframe(frame)
+                    if self.config.get("use_calib"):
+                        self.factor_graph.solve_GN_calib()
+                    else:
+                        self.factor_graph.solve_GN_rays()
+                    break
+            else:
+                self.keyframes.pop_last()
+        else:
+            self._add_keyframe(frame)
+            self._register_keyframe(frame)
+        assert len(self.retrieval_db) == len(self.keyframes)
+        self.mode = TRACKING
+        self.tracker.reset_idx_f2k()
+
     def _run_backend(self) -> None:                     # :292-318
         while self._queue:
             idx = self._queue.popleft()
             if idx > 0:
                 ii = list(range(max(0, idx - 3), idx))
+                if self.loop_closure and self.retrieval_db is not None:     # retrieved keyframes outside the window
+                    ii = ii + [c for c in self.retrieval_candidates.get(idx, []) if c < ii[0]]
                 self.factor_graph.add_factors(ii, [idx] * len(ii),
                                               min_match_frac=self.config["local_opt"].get("min_match_frac", 0.1),
                                               mast3r_match_fn=mast3r_match_symmetric)
