@@ -497,20 +497,13 @@ int m3_attention_dt(const void *Q, const void *K, const void *V, void *O, int q_
     return attention_launch(Q, K, V, O, q_row_stride, kv_row_stride, o_row_stride, q_batch_stride, kv_batch_stride,
                             o_batch_stride, nbatch, heads, Tq, Tk, kv_batch_shift, scale, dtype, false, stream);
 }
-// q carries softmax scale * log2(e) already (m3_gemm_rope_dt's q_scale): O = softmax2(Q K^T) V with p = 2^(s - m)
+// q carries softmax scale * log2(e) already (m3_gemm_ex's q_scale): O = softmax2(Q K^T) V with p = 2^(s - m)
 int m3_attention_prescaled_dt(const void *Q, const void *K, const void *V, void *O, int q_row_stride, int kv_row_stride,
                               int o_row_stride, int64_t q_batch_stride, int64_t kv_batch_stride, int64_t o_batch_stride,
                               int nbatch, int heads, int Tq, int Tk, int kv_batch_shift, int dtype, void *stream) {
     return attention_launch(Q, K, V, O, q_row_stride, kv_row_stride, o_row_stride, q_batch_stride, kv_batch_stride,
                             o_batch_stride, nbatch, heads, Tq, Tk, kv_batch_shift, 1.0f, dtype, true, stream);
 }
-int m3_attention_bf16(const void *Q, const void *K, const void *V, void *O, int q_row_stride, int kv_row_stride,
-                      int o_row_stride, int64_t q_batch_stride, int64_t kv_batch_stride, int64_t o_batch_stride,
-                      int nbatch, int heads, int Tq, int Tk, int kv_batch_shift, float scale, void *stream) {
-    return m3_attention_dt(Q, K, V, O, q_row_stride, kv_row_stride, o_row_stride, q_batch_stride, kv_batch_stride,
-                           o_batch_stride, nbatch, heads, Tq, Tk, kv_batch_shift, scale, DT_BF16, stream);
-}
-
 int m3_rope2d_dt(void *X, const int32_t *pos_yx, const float *cos_sin, int row_stride, int tokens, int heads,
                  int tokens_per_image, int dtype, void *stream) {
     M3_REQUIRE(X && pos_yx && cos_sin && tokens > 0 && heads > 0 && tokens_per_image > 0 && row_stride % 8 == 0);
@@ -524,10 +517,6 @@ int m3_rope2d_dt(void *X, const int32_t *pos_yx, const float *cos_sin, int row_s
                            (bf16_t *)X, pos_yx, cos_sin, row_stride, tokens, heads, tokens_per_image);
     M3_CHECK_LAUNCH("m3_rope2d");
     return M3_OK;
-}
-int m3_rope2d_bf16(void *X, const int32_t *pos_yx, const float *cos_sin, int row_stride, int tokens, int heads,
-                   int tokens_per_image, void *stream) {
-    return m3_rope2d_dt(X, pos_yx, cos_sin, row_stride, tokens, heads, tokens_per_image, DT_BF16, stream);
 }
 
 }  // extern "C"

@@ -13,7 +13,9 @@ extern "C" {
 // 2000 (round 3): m3_chol_solve's workspace is m3_chol_ws_doubles(dim) (was 1 + dim); m3_track_* info carries the
 // solver-failure flag; the RoPE GEMM entry points take (rope_tok, tokens_per_image, rope_cols) since 1001 -> callers built
 // against a 1xxx header must be rebuilt (tests assert the exact value).
-int m3_abi_version(void) { return 2007; }
+// 3000: m3_gemm_ex is the only dense GEMM entry point (RoPE from positions only; the per-token table is gone), and the
+// bf16-only aliases of the _dt operators are removed.
+int m3_abi_version(void) { return 3000; }
 
 const char *m3_status_string(int status) {
     switch (status) {

@@ -445,11 +445,6 @@ int m3_layernorm_dt(const float *x, const float *gamma, const float *beta, void 
     M3_CHECK_LAUNCH("m3_layernorm");
     return M3_OK;
 }
-int m3_layernorm_bf16(const float *x, const float *gamma, const float *beta, void *y, int M, int C, float eps,
-                      void *stream) {
-    return m3_layernorm_dt(x, gamma, beta, y, M, C, eps, DT_BF16, stream);
-}
-
 int m3_layernorm_grouped2_dt(const float *x, const float *gamma0, const float *beta0, const float *gamma1,
                              const float *beta1, void *y, int M, int C, int in_row_shift, float eps, int dtype,
                              void *stream) {
@@ -477,11 +472,6 @@ int m3_layernorm_hl_dt(const void *hi, const void *lo, const float *gamma0, cons
     M3_CHECK_LAUNCH("m3_layernorm_hl");
     return M3_OK;
 }
-int m3_layernorm_bf16_grouped2(const float *x, const float *gamma0, const float *beta0, const float *gamma1,
-                               const float *beta1, void *y, int M, int C, int in_row_shift, float eps, void *stream) {
-    return m3_layernorm_grouped2_dt(x, gamma0, beta0, gamma1, beta1, y, M, C, in_row_shift, eps, DT_BF16, stream);
-}
-
 int m3_layernorm_dual2_dt(const float *x, const float *ga0, const float *ba0, const float *ga1, const float *ba1,
                           const float *gb0, const float *bb0, const float *gb1, const float *bb1, void *y_own,
                           void *y_cross, int M, int C, float eps, int dtype, void *stream) {
@@ -509,10 +499,6 @@ int m3_patchify16_dt(const uint8_t *img, void *A, int B, int H, int W, int dtype
     M3_CHECK_LAUNCH("m3_patchify16");
     return M3_OK;
 }
-int m3_patchify16(const uint8_t *img, void *A, int B, int H, int W, void *stream) {
-    return m3_patchify16_dt(img, A, B, H, W, DT_BF16, stream);
-}
-
 int m3_cast_f32_dt(const float *x, void *y, int64_t n, int dtype, void *stream) {
     M3_REQUIRE(x && y && n > 0 && n % 4 == 0);
     M3_DT_OK(dtype);
@@ -521,8 +507,6 @@ int m3_cast_f32_dt(const float *x, void *y, int64_t n, int dtype, void *stream) 
     M3_CHECK_LAUNCH("m3_cast_f32");
     return M3_OK;
 }
-int m3_f32_to_bf16(const float *x, void *y, int64_t n, void *stream) { return m3_cast_f32_dt(x, y, n, DT_BF16, stream); }
-
 int m3_cast16(const void *x, void *y, int64_t n, int from_dtype, int to_dtype, void *stream) {
     M3_REQUIRE(x && y && n > 0 && n % 8 == 0);
     M3_DT_OK(from_dtype); M3_DT_OK(to_dtype);
@@ -552,8 +536,6 @@ int m3_add_dt(const void *a, const void *b, void *y, int64_t n, int dtype, void 
     M3_CHECK_LAUNCH("m3_add");
     return M3_OK;
 }
-int m3_add_bf16(const void *a, const void *b, void *y, int64_t n, void *stream) { return m3_add_dt(a, b, y, n, DT_BF16, stream); }
-
 int m3_concat2_bf16(const void *a, const void *b, void *out, int64_t M, int Ca, int Cb, void *stream) {
     M3_REQUIRE(a && b && out && M > 0 && Ca > 0 && Cb > 0 && Ca % 8 == 0 && Cb % 8 == 0);
     const int64_t total = M * ((Ca + Cb) / 8);
@@ -581,10 +563,6 @@ int m3_upsample2x_dt(const void *in, void *out, int B, int H, int W, int C, int 
     M3_CHECK_LAUNCH("m3_upsample2x");
     return M3_OK;
 }
-int m3_upsample2x_bf16(const void *in, void *out, int B, int H, int W, int C, void *stream) {
-    return m3_upsample2x_dt(in, out, B, H, W, C, DT_BF16, stream);
-}
-
 int m3_add_upsample2x_dt(const void *low, const void *y, void *out, int B, int H, int W, int OH, int OW, int C, int dtype,
                          void *stream) {
     M3_REQUIRE(low && y && out && B > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0);
@@ -622,10 +600,6 @@ int m3_desc_post_dt(const void *in, float *desc, float *dconf, int B, int H, int
 int m3_desc_post_f16(const void *in, void *desc_f16, float *dconf, int B, int H, int W, int dtype, void *stream) {
     return desc_post_launch(in, desc_f16, dconf, B, H, W, dtype, true, stream);
 }
-int m3_desc_post(const void *in, float *desc, float *dconf, int B, int H, int W, void *stream) {
-    return m3_desc_post_dt(in, desc, dconf, B, H, W, DT_BF16, stream);
-}
-
 
 int m3_pack_fields(void *dst, const m3_pack_seg *segs, int nseg, void *stream) {
     M3_REQUIRE(dst && segs && nseg > 0 && nseg <= 8 && (reinterpret_cast<size_t>(dst) & 15) == 0);

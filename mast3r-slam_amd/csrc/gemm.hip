@@ -449,16 +449,20 @@ int run_split(const GemmArgs &a, int S, int epi, void *ws, hipStream_t st) {
 int m3_launch_gemm256_dense(const GemmArgs &a, int epi, int bn, hipStream_t st);
 int m3_launch_gemm256_conv(const GemmArgs &a, int epi, hipStream_t st);
 
-// Large dense tiles go to the ping-pong kernel.  (A one-wave-per-SIMD 256x256 variant with AGPR accumulators was built
-// and measured in round 2 - bit-identical, 20-80 % slower: tools/experiments/gemm4w.hip, DESIGN.md section 3.  Round 3: a
+// Dense launches (m3_gemm_ex) run the tile pick_tile chooses; large tiles go to the ping-pong kernel.  (A one-wave-per-SIMD
+// 256x256 variant with AGPR accumulators was built and measured in round 2 - bit-identical, 20-80 % slower:
+// tools/experiments/gemm4w.hip, DESIGN.md section 3.  Round 3: a
 // 256x128x32 tile with TWO independent workgroups per CU, meant to run one tile's epilogue under the other's K loop -
 // bit-identical, 13-34 % slower: tools/experiments/gemm_dual.hip, DESIGN.md section 10.  Round 5: the same idea with the
 // ping-pong alternation kept INSIDE each of two 8-wave workgroups (256x128x64, 128 registers, 80 KiB of LDS each) -
 // bit-identical, within -4 ... +9 % of k_gemm256, and every forced stagger of the two workgroups slower: the K loop is bound
 // by the L2 -> LDS operand feed, which a 256x128 tile loads 1.5x harder: tools/experiments/gemm_duo.hip,
 // profiles/r05_gemm_duo_experiment.md.)
-static int launch_dense_big(const GemmArgs &a, int epi, int tile, hipStream_t st) {
-    return m3_launch_gemm256_dense(a, epi, tile, st);
+static int launch_dense(const GemmArgs &a, int epi, hipStream_t st) {
+    const int tile = pick_tile(a.M, a.N, a.groups > 1 ? 2 : 1);
+    if (tile >= 192) return m3_launch_gemm256_dense(a, epi, tile, st);
+    if (tile == 64) return launch<0, 64>(a, epi, st);
+    return launch<0>(a, epi, st);
 }
 
 extern "C" {
@@ -471,114 +475,6 @@ int m3_gemm_pick_tile(int M, int N, int groups) {
 }
 
 static bool dt_ok(int dtype) { return dtype == DT_BF16 || dtype == DT_F16; }
-// the RoPE projections also take M3_DT_F16_PVBF16 (2): an fp16 launch whose v columns (>= rope_cols) are stored as bf16
-static bool dt_ok_rope(int dtype) { return dt_ok(dtype) || dtype == 2; }
-static void set_dt(GemmArgs &a, int dtype) { a.dt = dtype == 2 ? DT_F16 : dtype; a.v_bf16 = dtype == 2; }
-
-int m3_gemm_dt(const void *A, const void *W, const float *bias, void *C, const void *R, int M, int N, int K,
-               int ldc, int epilogue, int dtype, void *stream) {
-    M3_REQUIRE(A && W && C && M > 0 && N > 0 && K > 0 && dt_ok(dtype));
-    M3_REQUIRE(K % BK == 0 && N % 4 == 0 && ldc >= N && ldc % 4 == 0 && epilogue != EPI_BF16_ROPE);
-    M3_REQUIRE(!((epilogue == EPI_F32_ACCUM || epilogue == EPI_BF16_ADD) && !R));
-    GemmArgs a{};
-    a.A = (const bf16_t *)A; a.W = (const bf16_t *)W; a.bias = bias; a.C = C; a.R = R;
-    a.M = M; a.N = N; a.K = K; a.ldc = ldc; a.dt = dtype;
-    const int tile = pick_tile(M, N);
-    if (tile >= 192) return launch_dense_big(a, epilogue, tile, (hipStream_t)stream);
-    if (tile == 64) return launch<0, 64>(a, epilogue, (hipStream_t)stream);
-    return launch<0>(a, epilogue, (hipStream_t)stream);
-}
-int m3_gemm_bf16(const void *A, const void *W, const float *bias, void *C, const void *R, int M, int N, int K,
-                 int ldc, int epilogue, void *stream) {
-    return m3_gemm_dt(A, W, bias, C, R, M, N, K, ldc, epilogue, DT_BF16, stream);
-}
-
-int m3_gemm_rope_dt(const void *A, const void *W, const float *bias, void *C, int M, int N, int K, int ldc,
-                    const float *rope_tok, int tokens_per_image, int rope_cols, int q_cols, float q_scale, int dtype,
-                    void *stream) {
-    M3_REQUIRE(A && W && C && rope_tok && M > 0 && N > 0 && K > 0 && tokens_per_image > 0 && dt_ok_rope(dtype));
-    M3_REQUIRE((reinterpret_cast<size_t>(rope_tok) & 15) == 0 && q_cols >= 0 && q_cols <= rope_cols && q_cols % 64 == 0);
-    M3_REQUIRE(K % BK == 0 && N % 64 == 0 && ldc >= N && ldc % 4 == 0 && rope_cols % 64 == 0 && rope_cols <= N);
-    GemmArgs a{};
-    a.A = (const bf16_t *)A; a.W = (const bf16_t *)W; a.bias = bias; a.C = C;
-    a.M = M; a.N = N; a.K = K; a.ldc = ldc; set_dt(a, dtype);
-    a.rope_tok = rope_tok; a.tokens_per_image = tokens_per_image; a.rope_cols = rope_cols;
-    a.q_cols = q_cols; a.q_scale = q_scale;
-    const int tile = pick_tile(M, N);
-    if (tile >= 192) return launch_dense_big(a, EPI_BF16_ROPE, tile, (hipStream_t)stream);
-    if (tile == 64) return launch<0, 64>(a, EPI_BF16_ROPE, (hipStream_t)stream);
-    return launch<0>(a, EPI_BF16_ROPE, (hipStream_t)stream);
-}
-int m3_gemm_rope_pos_dt(const void *A, const void *W, const float *bias, void *C, int M, int N, int K, int ldc,
-                        const int32_t *pos_yx, int tokens_per_image, float base, int rope_cols, int q_cols, float q_scale,
-                        int dtype, void *stream) {
-    M3_REQUIRE(A && W && C && pos_yx && M > 0 && N > 0 && K > 0 && tokens_per_image > 0 && base > 1.0f && dt_ok_rope(dtype));
-    M3_REQUIRE(q_cols >= 0 && q_cols <= rope_cols && q_cols % 64 == 0);
-    M3_REQUIRE(K % BK == 0 && N % 64 == 0 && ldc >= N && ldc % 4 == 0 && rope_cols % 64 == 0 && rope_cols <= N);
-    GemmArgs a{};
-    a.A = (const bf16_t *)A; a.W = (const bf16_t *)W; a.bias = bias; a.C = C;
-    a.M = M; a.N = N; a.K = K; a.ldc = ldc; set_dt(a, dtype);
-    a.rope_pos = pos_yx; a.rope_log2_base = log2f(base); a.tokens_per_image = tokens_per_image; a.rope_cols = rope_cols;
-    a.q_cols = q_cols; a.q_scale = q_scale;
-    const int tile = pick_tile(M, N);
-    if (tile >= 192) return launch_dense_big(a, EPI_BF16_ROPE, tile, (hipStream_t)stream);
-    if (tile == 64) return launch<0, 64>(a, EPI_BF16_ROPE, (hipStream_t)stream);
-    return launch<0>(a, EPI_BF16_ROPE, (hipStream_t)stream);
-}
-int m3_gemm_bf16_rope(const void *A, const void *W, const float *bias, void *C, int M, int N, int K, int ldc,
-                      const float *rope_tok, int tokens_per_image, int rope_cols, void *stream) {
-    return m3_gemm_rope_dt(A, W, bias, C, M, N, K, ldc, rope_tok, tokens_per_image, rope_cols, 0, 1.0f, DT_BF16, stream);
-}
-
-// Two GEMMs of identical shape in one launch (the two decoder branches / the two heads):
-// group g reads A + g*a_gstride, weights W[g], bias[g] and writes C + g*c_gstride.
-int m3_gemm_grouped2_dt(const void *A, const void *W0, const void *W1, const float *bias0, const float *bias1,
-                        void *C, const void *R, int M, int N, int K, int ldc, int64_t a_gstride,
-                        int64_t c_gstride, int epilogue, const float *rope_tok,
-                        int tokens_per_image, int rope_cols, int q_cols, float q_scale, int dtype, void *stream) {
-    M3_REQUIRE(A && W0 && W1 && C && M > 0 && N > 0 && K > 0 && (dt_ok(dtype) || (dtype == 2 && epilogue == EPI_BF16_ROPE)));
-    M3_REQUIRE(K % BK == 0 && N % 4 == 0 && ldc >= N && ldc % 4 == 0);
-    M3_REQUIRE(!((epilogue == EPI_F32_ACCUM || epilogue == EPI_BF16_ADD) && !R));
-    M3_REQUIRE((bias0 == nullptr) == (bias1 == nullptr));
-    if (epilogue == EPI_BF16_ROPE)
-        M3_REQUIRE(rope_tok && (reinterpret_cast<size_t>(rope_tok) & 15) == 0 && tokens_per_image > 0 && N % 64 == 0 &&
-                   rope_cols % 64 == 0 && rope_cols <= N && q_cols >= 0 && q_cols <= rope_cols && q_cols % 64 == 0);
-    GemmArgs a{};
-    a.A = (const bf16_t *)A; a.W = (const bf16_t *)W0; a.W2 = (const bf16_t *)W1; a.bias = bias0; a.bias2 = bias1;
-    a.C = C; a.R = R; a.M = M; a.N = N; a.K = K; a.ldc = ldc; set_dt(a, dtype);
-    a.a_gstride = a_gstride; a.c_gstride = c_gstride; a.groups = 2;
-    a.rope_tok = rope_tok; a.tokens_per_image = tokens_per_image; a.rope_cols = rope_cols;
-    a.q_cols = q_cols; a.q_scale = q_scale;
-    const int tile = pick_tile(M, N, 2);
-    if (tile >= 192) return launch_dense_big(a, epilogue, tile, (hipStream_t)stream);
-    if (tile == 64) return launch<0, 64>(a, epilogue, (hipStream_t)stream);
-    return launch<0>(a, epilogue, (hipStream_t)stream);
-}
-int m3_gemm_grouped2_rope_pos_dt(const void *A, const void *W0, const void *W1, const float *bias0, const float *bias1,
-                                 void *C, int M, int N, int K, int ldc, int64_t a_gstride, int64_t c_gstride,
-                                 const int32_t *pos_yx, int tokens_per_image, float base, int rope_cols, int q_cols,
-                                 float q_scale, int dtype, void *stream) {
-    M3_REQUIRE(A && W0 && W1 && C && pos_yx && M > 0 && N > 0 && K > 0 && tokens_per_image > 0 && base > 1.0f && dt_ok_rope(dtype));
-    M3_REQUIRE(K % BK == 0 && N % 64 == 0 && ldc >= N && ldc % 4 == 0 && (bias0 == nullptr) == (bias1 == nullptr));
-    M3_REQUIRE(rope_cols % 64 == 0 && rope_cols <= N && q_cols >= 0 && q_cols <= rope_cols && q_cols % 64 == 0);
-    GemmArgs a{};
-    a.A = (const bf16_t *)A; a.W = (const bf16_t *)W0; a.W2 = (const bf16_t *)W1; a.bias = bias0; a.bias2 = bias1;
-    a.C = C; a.M = M; a.N = N; a.K = K; a.ldc = ldc; set_dt(a, dtype);
-    a.a_gstride = a_gstride; a.c_gstride = c_gstride; a.groups = 2;
-    a.rope_pos = pos_yx; a.rope_log2_base = log2f(base); a.tokens_per_image = tokens_per_image; a.rope_cols = rope_cols;
-    a.q_cols = q_cols; a.q_scale = q_scale;
-    const int tile = pick_tile(M, N, 2);
-    if (tile >= 192) return launch_dense_big(a, EPI_BF16_ROPE, tile, (hipStream_t)stream);
-    if (tile == 64) return launch<0, 64>(a, EPI_BF16_ROPE, (hipStream_t)stream);
-    return launch<0>(a, EPI_BF16_ROPE, (hipStream_t)stream);
-}
-int m3_gemm_bf16_grouped2(const void *A, const void *W0, const void *W1, const float *bias0, const float *bias1,
-                          void *C, const void *R, int M, int N, int K, int ldc, int64_t a_gstride,
-                          int64_t c_gstride, int epilogue, const float *rope_tok,
-                          int tokens_per_image, int rope_cols, void *stream) {
-    return m3_gemm_grouped2_dt(A, W0, W1, bias0, bias1, C, R, M, N, K, ldc, a_gstride, c_gstride, epilogue, rope_tok,
-                               tokens_per_image, rope_cols, 0, 1.0f, DT_BF16, stream);
-}
 
 // widest node of the statistics' canonical tree for a stream of C columns (gemm_common.h): 256, 192 or 0 (no fold for this width)
 static int ln_top_width(int C) {
@@ -605,7 +501,8 @@ int m3_gemm_ex(const m3_gemm_desc *d, void *stream) {
     M3_REQUIRE(d && d->A && d->W && (d->C || d->c_lo) && d->M > 0 && d->N > 0 && d->K > 0);
     const int epi = d->epilogue, groups = d->groups > 1 ? 2 : 1;
     const bool rope = epi == EPI_BF16_ROPE;
-    M3_REQUIRE(rope ? dt_ok_rope(d->dtype) : dt_ok(d->dtype));
+    // the RoPE projections also take M3_DT_F16_PVBF16 (2): an fp16 launch whose v columns (>= rope_cols) are stored as bf16
+    M3_REQUIRE(dt_ok(d->dtype) || (rope && d->dtype == 2));
     M3_REQUIRE(d->K % BK == 0 && d->N % 4 == 0 && d->ldc >= d->N && d->ldc % 4 == 0);
     M3_REQUIRE(!((epi == EPI_F32_ACCUM || epi == EPI_BF16_ADD) && !d->R));
     M3_REQUIRE(epi >= EPI_BF16 && epi <= EPI_BF16_ROPE);
@@ -638,7 +535,7 @@ int m3_gemm_ex(const m3_gemm_desc *d, void *stream) {
     GemmArgs a{};
     a.A = (const bf16_t *)d->A; a.W = (const bf16_t *)d->W; a.W2 = (const bf16_t *)d->W1; a.bias = d->bias; a.bias2 = d->bias1;
     a.C = d->C; a.R = d->R; a.M = d->M; a.N = d->N; a.K = d->K; a.ldc = d->ldc;
-    if (rope) set_dt(a, d->dtype); else a.dt = d->dtype;
+    a.dt = d->dtype == 2 ? DT_F16 : d->dtype; a.v_bf16 = d->dtype == 2;
     a.a_gstride = d->a_gstride; a.c_gstride = d->c_gstride; a.groups = groups == 2 ? 2 : 0;
     if (rope) {
         a.rope_pos = d->rope_pos; a.rope_log2_base = log2f(d->rope_base); a.tokens_per_image = d->tokens_per_image;
@@ -655,10 +552,7 @@ int m3_gemm_ex(const m3_gemm_desc *d, void *stream) {
         a.ln_gsz = d->ln_slots / a.ln_tops;                  // 1 .. 4 stored slots per top node
     }
     a.stats_w = d->stats_out ? ln_store_width(d->M, d->N, groups) : 0;
-    const int tile = pick_tile(d->M, d->N, groups);
-    if (tile >= 192) return launch_dense_big(a, epi, tile, (hipStream_t)stream);
-    if (tile == 64) return launch<0, 64>(a, epi, (hipStream_t)stream);
-    return launch<0>(a, epi, (hipStream_t)stream);
+    return launch_dense(a, epi, (hipStream_t)stream);
 }
 
 int64_t m3_conv3x3_splitk_bytes(int B, int H, int Wd, int Cin, int Cout, int stride) {
@@ -723,13 +617,6 @@ int m3_conv3x3_grouped2_dt(const void *X, const void *W0, const void *W1, const 
     return launch<1>(a, epilogue, (hipStream_t)stream);
 }
 
-int m3_conv3x3_bf16(const void *X, const void *W, const float *bias, void *Y, const void *R, const void *zero16,
-                    int B, int H, int Wd, int Cin, int Cout, int stride, int epilogue, void *splitk_ws,
-                    int64_t splitk_ws_bytes, void *stream) {
-    return m3_conv3x3_dt(X, W, bias, Y, R, zero16, B, H, Wd, Cin, Cout, stride, epilogue, splitk_ws, splitk_ws_bytes,
-                         DT_BF16, stream);
-}
-
 // Last stage of the DPT head in one launch: Y = relu(conv3x3(X) + bias) (Cout = 128, never written),
 // raw = Y . W4^T + b4 (4 channels), pts = xyz / |xyz| * expm1(|xyz|), conf = 1 + exp(raw[3]).
 int m3_conv3x3_relu_head4_dt(const void *X, const void *W, const float *bias, const void *W4, const float *b4,
@@ -745,10 +632,6 @@ int m3_conv3x3_relu_head4_dt(const void *X, const void *W, const float *bias, co
     a.H = H; a.Wd = Wd; a.Cin = Cin; a.stride = 1; a.OH = H; a.OW = Wd;
     a.M = B * H * Wd; a.N = 128; a.K = 9 * Cin; a.ldc = 3; a.dt = dtype;
     return launch<1>(a, EPI_RELU_HEAD4, (hipStream_t)stream);
-}
-int m3_conv3x3_relu_head4(const void *X, const void *W, const float *bias, const void *W4, const float *b4,
-                          float *pts, float *conf, const void *zero16, int B, int H, int Wd, int Cin, void *stream) {
-    return m3_conv3x3_relu_head4_dt(X, W, bias, W4, b4, pts, conf, zero16, B, H, Wd, Cin, DT_BF16, stream);
 }
 
 }  // extern "C"

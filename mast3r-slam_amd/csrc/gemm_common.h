@@ -111,12 +111,11 @@ struct GemmArgs {
     // conv geometry
     int H, Wd, Cin, OH, OW, stride;
     // fused RoPE-2D epilogue (EPI_BF16_ROPE): columns < rope_cols are 64-wide heads to rotate
-    const float *rope_tok;  // [tokens_per_image, 2 (y|x), 2 (cos|sin), 16]; or, position mode:
-    const int *rope_pos;    // [tokens_per_image, 2 (y|x)] grid positions - cos/sin are then computed in the epilogue
+    const int *rope_pos;    // [tokens_per_image, 2 (y|x)] grid positions - cos/sin are computed in the epilogue
     float rope_log2_base;   //   from frequencies base^(-i/16), i = 0..15 (v_sin_f32 / v_cos_f32, arguments in revolutions)
     int tokens_per_image, rope_cols;
     int ln_gsz, ln_tops;    // consumer: stored slots per top node (1 .. 4) and top nodes (<= 4)
-    int rope_pmax;          //   position mode: > 0 = every position is in [0, rope_pmax) (<= kRopeTableRows): the kernels then build
+    int rope_pmax;          //   > 0 = every position is in [0, rope_pmax) (<= kRopeTableRows): the kernels then build
                             //   the cos / sin of all rope_pmax x 16 (position, frequency) pairs ONCE per workgroup in LDS
     int q_cols;             // columns < q_cols (the q heads) are multiplied by q_scale after the rotation, before the
     float q_scale;          // 16-bit rounding: softmax scale * log2(e) folded into q (attention then needs no per-score FMA)
@@ -153,7 +152,8 @@ struct GemmArgs {
     void *C_lo;
     // consumer (16-bit epilogues): A is such a copy of the RAW stream and W carries gamma; the epilogue turns the product into
     // the product with the normalised row: rstd[m] * (acc - mean[m] * ln_colsum[n]) (+ bias, which carries beta . W^T);
-    // mean / rstd of row m come from ln_stats [M][ln_slots][2], ln_slots = K / 32 (summed in ONE order by every kernel)
+    // mean / rstd of row m come from ln_stats [ln_slots][M][2] (slot-major): the producer's nodes of the rows' canonical sum tree
+    // (m3_ln_slot_count: K / 64 pairs, K / 128 halves or one per top node), finished in ONE order by every kernel
     const float *ln_stats;
     const float *ln_colsum, *ln_colsum2;       // [N] sums over k of the 16-bit weights (group 0 / group 1)
     int ln_slots;
@@ -232,16 +232,11 @@ __device__ __forceinline__ void store_tile(const GemmArgs &g, f32x4 v, int m, in
 // t[0..NJ-1] are the 16-column tiles, lane holds columns 16*j + 4*(lane>>4) + e.  Every 32-column
 // block is half a head: even blocks rotate with the token's y, odd blocks with x; element i pairs
 // with i+16, i.e. tile 2b with tile 2b+1 in the SAME lane and register.  Bias is added first.
-// Coefficients come from a PER-TOKEN table rope_tok[tokens_per_image][2 (y|x)][2 (cos|sin)][16 freq] f32
-// (256 B per token, L2-resident): two independent 16-byte reads per (row, block), no position lookup in
-// front of it and no branch around it - the first version (position table -> cos/sin table, both behind
-// per-row branches) made every row a dependent chain of two L2 round trips: 128 us instead of 93 us for
-// the 16384 x 3072 x 1024 projection.
+// The coefficients come from the token's grid position g.rope_pos (one 4-byte position per (row, axis)): angle in
+// revolutions = pos * base^(-i/16) / 2pi (at most ~10 for a 64 x 64 token grid; v_sin_f32's domain is +-256), absolute
+// error ~1e-6.  (A per-token cos / sin table read 64 B per 64 B of output, fetched as 16 rows x 64 B pieces by every wave
+// that shares a row - by ablation ~10 us of a 105 us projection, while the rotation arithmetic itself is free.)
 struct RopeCoef { float4 c, s; };               // cos / sin of frequencies fi .. fi+3
-// Position mode (g.rope_pos): the table read is 64 B of cos/sin per 64 B of output, fetched as 16 rows x 64 B pieces by
-// every wave that shares a row - by ablation ~10 us of a 105 us projection, while the rotation arithmetic itself is free.
-// One 4-byte position per (row, axis) and eight transcendentals per 32-column block replace it: angle in revolutions =
-// pos * base^(-i/16) / 2pi (at most ~10 for a 64 x 64 token grid; v_sin_f32's domain is +-256), absolute error ~1e-6.
 struct RopeFreq { float rev[4]; };              // this lane's four frequencies (columns fi..fi+3 of a 16-wide group) / 2pi
 __device__ __forceinline__ RopeFreq rope_freqs(const GemmArgs &g, int lane) {
     RopeFreq f;
@@ -250,7 +245,7 @@ __device__ __forceinline__ RopeFreq rope_freqs(const GemmArgs &g, int lane) {
     for (int k = 0; k < 4; ++k) f.rev[k] = exp2f(-(float)(fi + k) * (g.rope_log2_base * (1.0f / 16.0f))) * 0.15915494309189535f;
     return f;
 }
-// LDS table of the rotation coefficients, position mode: rows of 32 floats, row p = cos(p f_i), i = 0..15 | sin(p f_i), i = 0..15
+// LDS table of the rotation coefficients: rows of 32 floats, row p = cos(p f_i), i = 0..15 | sin(p f_i), i = 0..15
 // - the SAME expressions as the per-lane computation in rope_load (same bits).  Per 32-column block and row a lane then reads
 // two 16-byte LDS words instead of issuing eight transcendentals: in the 256 x 256 tile a lane owns 32 rows x 2 blocks = 512
 // v_sin / v_cos (quarter rate: ~16 cycles each per wave), 6.8 us per tile with two waves per SIMD - all of what the fused
@@ -274,10 +269,8 @@ __device__ __forceinline__ int2 rope_pos_of(const GemmArgs &g, int m) {
     return *reinterpret_cast<const int2 *>(g.rope_pos + (size_t)(mm % g.tokens_per_image) * 2);
 }
 template <int NJ>
-__device__ __forceinline__ void rope_load(const GemmArgs &g, RopeCoef (&cf)[NJ / 2], int m, int n_base, int lane,
-                                          const RopeFreq &fr, int2 pyx = int2{0, 0}, const float *ropet = nullptr) {
-    const int mm = m < g.M ? m : g.M - 1;
-    const int tok = mm % g.tokens_per_image;
+__device__ __forceinline__ void rope_load(const GemmArgs &g, RopeCoef (&cf)[NJ / 2], int n_base, int lane, const RopeFreq &fr,
+                                          int2 pyx, const float *ropet = nullptr) {
     const int fi = (lane >> 4) * 4;
 #pragma unroll
     for (int blk = 0; blk < NJ / 2; ++blk) {
@@ -289,16 +282,12 @@ __device__ __forceinline__ void rope_load(const GemmArgs &g, RopeCoef (&cf)[NJ /
             const float *row = ropet + p * 32 + fi;
             cf[blk].c = *reinterpret_cast<const float4 *>(row);
             cf[blk].s = *reinterpret_cast<const float4 *>(row + 16);
-        } else if (g.rope_pos) {                                         // kernel-uniform
+        } else {
             const float pos = (float)(axis ? pyx.y : pyx.x);
             cf[blk].c = make_float4(__builtin_amdgcn_cosf(pos * fr.rev[0]), __builtin_amdgcn_cosf(pos * fr.rev[1]),
                                     __builtin_amdgcn_cosf(pos * fr.rev[2]), __builtin_amdgcn_cosf(pos * fr.rev[3]));
             cf[blk].s = make_float4(__builtin_amdgcn_sinf(pos * fr.rev[0]), __builtin_amdgcn_sinf(pos * fr.rev[1]),
                                     __builtin_amdgcn_sinf(pos * fr.rev[2]), __builtin_amdgcn_sinf(pos * fr.rev[3]));
-        } else {
-            const float *row = g.rope_tok + (size_t)(tok * 2 + axis) * 32 + fi;
-            cf[blk].c = *reinterpret_cast<const float4 *>(row);
-            cf[blk].s = *reinterpret_cast<const float4 *>(row + 16);
         }
     }
 }
@@ -338,7 +327,7 @@ __device__ __forceinline__ void rope_strip(const GemmArgs &g, f32x4 *t, int m, i
         bj[j] = (g.bias && n_base + j * 16 + fi < g.N) ? *reinterpret_cast<const float4 *>(g.bias + n_base + j * 16 + fi)
                                                        : make_float4(0.f, 0.f, 0.f, 0.f);
     RopeCoef cf[NJ / 2];
-    rope_load<NJ>(g, cf, m, n_base, lane, rope_freqs(g, lane), g.rope_pos ? rope_pos_of(g, m) : int2{0, 0});
+    rope_load<NJ>(g, cf, n_base, lane, rope_freqs(g, lane), g.rope_pos ? rope_pos_of(g, m) : int2{0, 0});
     rope_apply<NJ>(g, t, cf, bj, n_base);
 }
 
@@ -703,8 +692,7 @@ __device__ __forceinline__ void epilogue_rows(const GemmArgs &g, f32x4 (&acc)[NI
                     for (int ii = 0; ii < TP; ++ii) pyx[ii] = rope_pos_of(g, m_base + (pass * TP + ii) * 16 + r);
                 }
 #pragma unroll
-                for (int ii = 0; ii < TP; ++ii)
-                    rope_load<NJ>(g, cf[ii], m_base + (pass * TP + ii) * 16 + r, n_base, lane, fr, pyx[ii], ropet);
+                for (int ii = 0; ii < TP; ++ii) rope_load<NJ>(g, cf[ii], n_base, lane, fr, pyx[ii], ropet);
             }
 #pragma unroll
             for (int ii = 0; ii < TP; ++ii) {

@@ -85,38 +85,8 @@ def zero_page(dev):
 
 
 def gemm(a: torch.Tensor, w: torch.Tensor, bias=None, epi: int = EPI_BF16, out=None, resid=None):
-    """out[M,N] = epi(a[M,K] @ w[N,K].T + bias).  a, w bf16; out bf16 or f32 by epilogue."""
-    a = _ffi.check(a, H16, "a")
-    w = _ffi.check(w, H16, "w")
-    dt = _same16(a, w)
-    m, k = a.shape
-    n = w.shape[0]
-    if w.shape[1] != k:
-        raise ValueError(f"K mismatch: a {tuple(a.shape)} vs w {tuple(w.shape)}")
-    odt = torch.float32 if epi in _F32_EPIS else a.dtype
-    if out is None:
-        out = torch.empty((m, n), dtype=odt, device=a.device)
-    else:
-        if out.dtype != odt or out.shape[0] != m or out.shape[1] < n or out.stride(1) != 1:
-            raise ValueError("bad `out`")
-    ldc = out.stride(0)
-    if bias is not None:
-        bias = _ffi.check(bias, torch.float32, "bias", (n,))
-    if resid is not None and (resid.dtype != odt or resid.stride(0) != ldc):
-        raise ValueError("residual must match out dtype/stride")
-    e0 = _prof_begin()
-    _ffi.call("m3_gemm_dt", _ffi.ptr(a), _ffi.ptr(w), _ffi.ptr(bias), _ffi.ptr(out), _ffi.ptr(resid),
-              m, n, k, ldc, epi, dt, _ffi.stream_ptr())
-    esz = out.element_size()
-    _prof_end(e0, _gemm_kind(m, n), 2.0 * m * n * k, 2.0 * (m * k + n * k) + esz * m * n * (1 if resid is None else 2),
-              f"gemm {m}x{n}x{k} epi{epi} {a.dtype}")
-    return out
-
-
-def rope_token_table(pos_yx, cos_sin):
-    """pos_yx int [T,2] (y,x), cos_sin f32 [max_pos,16,2] -> per-token table f32 [T,2,2,16] = (token, axis y|x,
-    cos|sin, frequency): what the fused RoPE epilogue reads, no position lookup on the device."""
-    return cos_sin[pos_yx.long()].transpose(-1, -2).contiguous()
+    """out[M,N] = epi(a[M,K] @ w[N,K].T + bias).  a, w 16-bit; out 16-bit or f32 by epilogue (gemm_ex)."""
+    return gemm_ex(a, w, bias, epi, out=out, resid=resid)
 
 
 QK_PRESCALE = 0.125 * 1.4426950408889634     # softmax scale (head dim 64) * log2(e), folded into q by the RoPE epilogue
@@ -145,40 +115,12 @@ def _rope_pmax(t) -> int:
     return b if 0 < b <= 64 else 0
 
 
-def _rope_table(t):
-    """The `rope` operand of the fused epilogue: int32 [T,2] grid positions (y, x) - cos/sin computed in the kernel -
-    or float32 [T,2,2,16] per-token cos/sin table (rope_token_table).  Returns (tensor, tokens_per_image, by_position)."""
-    if isinstance(t, torch.Tensor) and t.dtype == torch.int32:
-        t = _ffi.check(t, torch.int32, "rope positions", (None, 2))
-        return t, t.shape[0], True
-    t = _ffi.check(t, torch.float32, "rope_tok", (None, 2, 2, 16))
-    return t, t.shape[0], False
-
-
 def gemm_rope(a, w, bias, rope_tok, rope_cols: int, q_cols: int = 0, q_scale: float = 1.0, base: float = ROPE_BASE,
               pv_bf16: bool = False):
     """16-bit out[M,N] = a @ w.T + bias with RoPE-2D applied to the 64-wide heads in columns < rope_cols;
-    rope_tok: int32 [tokens_per_image,2] token grid positions (frequencies base^(-i/16)) or the f32
-    [tokens_per_image,2,2,16] table of rope_token_table.  pv_bf16 (fp16 tensors only): the columns >= rope_cols
-    (v) of the fp16 output buffer hold bf16 values - what attention(..., pv_bf16=True) reads."""
-    rope_tok, tokens_per_image, by_pos = _rope_table(rope_tok)
-    a = _ffi.check(a, H16, "a")
-    w = _ffi.check(w, H16, "w")
-    dt = _pv_code(_same16(a, w), pv_bf16)
-    m, k = a.shape
-    n = w.shape[0]
-    if by_pos and float(base) == ROPE_BASE:                   # the descriptor entry point carries the position bound (rope_bound)
-        return gemm_ex(a, w, bias, EPI_BF16_ROPE, rope=(rope_tok, rope_cols, q_cols, q_scale), pv_bf16=pv_bf16)
-    out = torch.empty((m, n), dtype=a.dtype, device=a.device)
-    e0 = _prof_begin()
-    if by_pos:
-        _ffi.call("m3_gemm_rope_pos_dt", _ffi.ptr(a), _ffi.ptr(w), _ffi.ptr(bias), _ffi.ptr(out), m, n, k, n,
-                  _ffi.ptr(rope_tok), tokens_per_image, float(base), rope_cols, int(q_cols), float(q_scale), dt, _ffi.stream_ptr())
-    else:
-        _ffi.call("m3_gemm_rope_dt", _ffi.ptr(a), _ffi.ptr(w), _ffi.ptr(bias), _ffi.ptr(out), m, n, k, n,
-                  _ffi.ptr(rope_tok), tokens_per_image, rope_cols, int(q_cols), float(q_scale), dt, _ffi.stream_ptr())
-    _prof_end(e0, _gemm_kind(m, n), 2.0 * m * n * k, 2.0 * (m * k + n * k + m * n))
-    return out
+    rope_tok: int32 [tokens_per_image,2] token grid positions (frequencies base^(-i/16)).  pv_bf16 (fp16 tensors only):
+    the columns >= rope_cols (v) of the fp16 output buffer hold bf16 values - what attention(..., pv_bf16=True) reads."""
+    return gemm_ex(a, w, bias, EPI_BF16_ROPE, rope=(rope_tok, rope_cols, q_cols, q_scale), pv_bf16=pv_bf16, rope_base=base)
 
 
 def conv3x3(x: torch.Tensor, w: torch.Tensor, bias=None, epi: int = EPI_BF16, stride: int = 1, resid=None, out=None,
@@ -551,41 +493,9 @@ def add(a, b):
 
 
 def gemm_grouped2(a, w0, w1, b0, b1, epi=EPI_BF16, out=None, resid=None, rope=None, pv_bf16=False):
-    """Two same-shape GEMMs in one launch.  a [2,M,K] bf16, weights [N,K] x2 -> out [2,M,N].
-    rope = (positions int32 [T,2] or table f32 [T,2,2,16], rope_cols[, q_cols, q_scale]) with epi=EPI_BF16_ROPE;
-    pv_bf16 as gemm_rope."""
-    a = _ffi.check(a, H16, "a")
-    if a.dim() != 3 or a.shape[0] != 2:
-        raise ValueError(f"a must be [2,M,K], got {tuple(a.shape)}")
-    _, m, k = a.shape
-    w0 = _ffi.check(w0, H16, "w0")
-    w1 = _ffi.check(w1, H16, "w1", tuple(w0.shape))
-    if pv_bf16 and epi != EPI_BF16_ROPE:
-        raise ValueError("pv_bf16 goes with epi=EPI_BF16_ROPE")
-    dt = _pv_code(_same16(a, w0, w1), pv_bf16)
-    n = w0.shape[0]
-    odt = torch.float32 if epi in _F32_EPIS else a.dtype
-    if out is None:
-        out = torch.empty((2, m, n), dtype=odt, device=a.device)
-    elif out.dtype != odt or out.dim() != 3 or out.shape[0] != 2 or out.shape[1] != m or out.shape[2] < n or not out.is_contiguous():
-        raise ValueError("bad `out`")
-    ldc = out.shape[2]                                           # > n: the extra columns (zero padding) are left alone
-    if resid is not None and (resid.dtype != odt or tuple(resid.shape) != tuple(out.shape) or not resid.is_contiguous()):
-        raise ValueError("bad `resid`")
-    rtok, rc, qc, qs = (tuple(rope) + (0, 1.0))[:4] if rope is not None else (None, 0, 0, 1.0)
-    tpi, by_pos = 0, False
-    if rtok is not None:
-        rtok, tpi, by_pos = _rope_table(rtok)
-    if by_pos:
-        if epi != EPI_BF16_ROPE or resid is not None:
-            raise ValueError("rope positions go with epi=EPI_BF16_ROPE and no residual")
-        return gemm_ex(a, w0, b0, EPI_BF16_ROPE, out=out, w1=w1, bias1=b1, rope=(rtok, rc, qc, qs), pv_bf16=pv_bf16)
-    e0 = _prof_begin()
-    _ffi.call("m3_gemm_grouped2_dt", _ffi.ptr(a), _ffi.ptr(w0), _ffi.ptr(w1), _ffi.ptr(b0), _ffi.ptr(b1), _ffi.ptr(out),
-              _ffi.ptr(resid), m, n, k, ldc, m * k, m * ldc, epi, _ffi.ptr(rtok), tpi, rc, int(qc), float(qs), dt, _ffi.stream_ptr())
-    _prof_end(e0, _gemm_kind(m, n, 2), 4.0 * m * n * k,
-              2.0 * (2.0 * (m * k + n * k) + out.element_size() * m * n * (1 if resid is None else 2)))
-    return out
+    """Two same-shape GEMMs in one launch.  a [2,M,K] 16-bit, weights [N,K] x2 -> out [2,M,N] (gemm_ex).
+    rope = (positions int32 [T,2], rope_cols[, q_cols, q_scale]) with epi=EPI_BF16_ROPE; pv_bf16 as gemm_rope."""
+    return gemm_ex(a, w0, b0, epi, out=out, resid=resid, w1=w1, bias1=b1, rope=rope, pv_bf16=pv_bf16)
 
 
 LN_EPS = 1e-6
@@ -643,10 +553,12 @@ def layernorm_hl(hl, g0, b0, g1=None, b1=None, eps=1e-6, dtype=torch.float16):
 
 
 def gemm_ex(a, w, bias=None, epi: int = EPI_BF16, out=None, resid=None, w1=None, bias1=None, rope=None, pv_bf16: bool = False,
-            fold_in=None, fold_out=None, a_swap: bool = False, hl=None):
-    """m3_gemm_ex: one or two groups, any epilogue, with the LayerNorm fold (include/m3slam_model.h).
-      a [M,K] (w1 None) or [2,M,K]; w (and w1) [N,K]; out / resid like gemm / gemm_grouped2; rope = (positions int32 [T,2],
-      rope_cols[, q_cols, q_scale]) with EPI_BF16_ROPE.
+            fold_in=None, fold_out=None, a_swap: bool = False, hl=None, rope_base: float = ROPE_BASE):
+    """The dense GEMM launch that every wrapper above goes through (the m3_gemm_desc entry point of include/m3slam_model.h):
+      one or two groups, any epilogue, with the LayerNorm fold.
+      a [M,K] (w1 None) or [2,M,K]; w (and w1) [N,K]; bias (and bias1) f32 [N] or None.  out: allocated when None, else a
+      contiguous [M,N'] (or [2,M,N']) buffer with N' >= N (the columns beyond N are left alone); resid: like out.
+      rope = (positions int32 [T,2], rope_cols[, q_cols, q_scale]) with EPI_BF16_ROPE: cos / sin of pos * rope_base^(-i/16).
       fold_out = (x16, stats): PRODUCER - with EPI_F32 / EPI_F32_ACCUM also writes the 16-bit copy of the fp32 output and the
         rows' partial statistics (ln_fold_buffers).
       fold_in = (stats, colsum[, colsum1]): CONSUMER - `a` is the 16-bit copy of the raw stream, w carries gamma, bias carries
@@ -656,6 +568,7 @@ def gemm_ex(a, w, bias=None, epi: int = EPI_BF16, out=None, resid=None, w1=None,
       hl = (hi, lo, stats) (ln_hl_buffers; fp16): PRODUCER on a hi / lo stream, in place - EPI_F32: the stream becomes
         a @ w^T + bias; EPI_F32_ACCUM: it is updated by that product.  No fp32 tensor is written; returns None."""
     grouped = w1 is not None
+    g = 2 if grouped else 1
     a = _ffi.check(a, H16, "a")
     w = _ffi.check(w, H16, "w")
     if grouped:
@@ -670,9 +583,20 @@ def gemm_ex(a, w, bias=None, epi: int = EPI_BF16, out=None, resid=None, w1=None,
         raise ValueError(f"K mismatch: a {tuple(a.shape)} vs w {tuple(w.shape)}")
     if pv_bf16 and epi != EPI_BF16_ROPE:
         raise ValueError("pv_bf16 goes with epi=EPI_BF16_ROPE")
+    if rope is not None and (epi != EPI_BF16_ROPE or resid is not None):
+        raise ValueError("rope positions go with epi=EPI_BF16_ROPE and no residual")
     dt = _pv_code(_same16(a, w, w1), pv_bf16)
-    odt = torch.float32 if epi in _F32_EPIS else a.dtype
+    if bias is not None:
+        bias = _ffi.check(bias, torch.float32, "bias", (n,))
+    if bias1 is not None:
+        bias1 = _ffi.check(bias1, torch.float32, "bias1", (n,))
     lead = (2,) if grouped else ()
+    d = _ffi.GemmDesc()
+    d.A = (a[1] if (grouped and a_swap) else a).data_ptr()
+    d.W, d.W1 = w.data_ptr(), _ffi.ptr(w1)
+    d.bias, d.bias1 = _ffi.ptr(bias), _ffi.ptr(bias1)
+    d.M, d.N, d.K, d.epilogue, d.dtype, d.groups = m, n, k, epi, dt, g
+    d.a_gstride = (-m * k if a_swap else m * k) if grouped else 0
     if hl is not None:
         if epi not in _F32_EPIS or a.dtype != torch.float16 or out is not None or resid is not None or fold_out is not None:
             raise ValueError("hl goes with EPI_F32 / EPI_F32_ACCUM on fp16 operands, without out / resid / fold_out")
@@ -680,54 +604,46 @@ def gemm_ex(a, w, bias=None, epi: int = EPI_BF16, out=None, resid=None, w1=None,
         for t_ in (hi, lo):
             if t_.dtype != torch.float16 or tuple(t_.shape) != lead + (m, n) or not t_.is_contiguous():
                 raise ValueError("bad hi / lo planes (ln_hl_buffers)")
-        slots = ln_slot_count(m, n, 2 if grouped else 1)
+        slots = ln_slot_count(m, n, g)
         if stats.dtype != torch.float32 or tuple(stats.shape) != lead + (slots, m, 2) or not stats.is_contiguous():
             raise ValueError("bad statistics buffer (ln_hl_buffers)")
-        d = _ffi.GemmDesc()
-        d.A, d.W, d.W1 = a.data_ptr(), w.data_ptr(), _ffi.ptr(w1)
-        d.bias, d.bias1 = _ffi.ptr(bias), _ffi.ptr(bias1)
         d.c16, d.c_lo, d.stats_out, d.stats_slots = hi.data_ptr(), lo.data_ptr(), stats.data_ptr(), slots
         if epi == EPI_F32_ACCUM:
             d.R, d.r_lo = hi.data_ptr(), lo.data_ptr()
-        d.M, d.N, d.K, d.ldc, d.epilogue, d.dtype, d.groups = m, n, k, n, epi, dt, 2 if grouped else 1
-        d.a_gstride, d.c_gstride = (m * k, m * n) if grouped else (0, 0)
+        d.ldc = n
+        d.c_gstride = m * n if grouped else 0
         d.stats_gstride = m * slots * 2 if grouped else 0
-        e0 = _prof_begin()
-        _ffi.call("m3_gemm_ex", C.addressof(d), _ffi.stream_ptr())
-        g_ = 2 if grouped else 1
-        _prof_end(e0, _gemm_kind(m, n, g_), 2.0 * g_ * m * n * k,
-                  g_ * (2.0 * (m * k + n * k) + 4.0 * m * n * (1 if epi == EPI_F32 else 2) + 8.0 * m * (n // 32)),
-                  f"gemm_ex hl {g_}x{m}x{n}x{k} epi{epi}")
-        return None
-    if out is None:
-        out = torch.empty(lead + (m, n), dtype=odt, device=a.device)
-    elif out.dtype != odt or tuple(out.shape[:-1]) != lead + (m,) or out.shape[-1] < n or not out.is_contiguous():
-        raise ValueError("bad `out`")
-    ldc = out.shape[-1]
-    if resid is not None and (resid.dtype != odt or tuple(resid.shape) != tuple(out.shape) or not resid.is_contiguous()):
-        raise ValueError("bad `resid`")
-    d = _ffi.GemmDesc()
-    d.A = (a[1] if (grouped and a_swap) else a).data_ptr()
-    d.W, d.W1 = w.data_ptr(), _ffi.ptr(w1)
-    d.bias, d.bias1 = _ffi.ptr(bias), _ffi.ptr(bias1)
-    d.C, d.R = out.data_ptr(), _ffi.ptr(resid)
-    d.M, d.N, d.K, d.ldc, d.epilogue, d.dtype, d.groups = m, n, k, ldc, epi, dt, 2 if grouped else 1
-    d.a_gstride = (-m * k if a_swap else m * k) if grouped else 0
-    d.c_gstride = m * ldc if grouped else 0
+        nb = 2.0 * (m * k + n * k) + 4.0 * m * n * (1 if epi == EPI_F32 else 2) + 8.0 * m * (n // 32)
+    else:
+        odt = torch.float32 if epi in _F32_EPIS else a.dtype
+        if out is None:
+            out = torch.empty(lead + (m, n), dtype=odt, device=a.device)
+        elif out.dtype != odt or tuple(out.shape[:-1]) != lead + (m,) or out.shape[-1] < n or not out.is_contiguous():
+            raise ValueError("bad `out`")
+        ldc = out.shape[-1]
+        if resid is not None and (resid.dtype != odt or tuple(resid.shape) != tuple(out.shape) or not resid.is_contiguous()):
+            raise ValueError("bad `resid`")
+        d.C, d.R, d.ldc = out.data_ptr(), _ffi.ptr(resid), ldc
+        d.c_gstride = m * ldc if grouped else 0
+        nb = 2.0 * (m * k + n * k) + out.element_size() * m * n * (1 if resid is None else 2)
+        if fold_out is not None:
+            x16, stats = fold_out
+            slots = ln_slot_count(m, n, g)
+            if (x16.dtype != a.dtype or tuple(x16.shape) != tuple(out.shape) or not x16.is_contiguous() or stats.dtype != torch.float32
+                    or tuple(stats.shape) != lead + (slots, m, 2) or not stats.is_contiguous() or ldc != n):
+                raise ValueError("bad fold_out buffers (ln_fold_buffers)")
+            d.c16, d.stats_out, d.stats_slots = x16.data_ptr(), stats.data_ptr(), slots
+            d.stats_gstride = m * slots * 2 if grouped else 0
+            nb += 2.0 * m * n + 8.0 * m * (n // 32)
     if rope is not None:
-        rtok, rc, qc, qs = (tuple(rope) + (0, 1.0))[:4]
-        d.rope_max_pos = _rope_pmax(rtok)
-        rtok = _ffi.check(rtok, torch.int32, "rope positions", (None, 2))
-        d.rope_pos, d.tokens_per_image, d.rope_base = rtok.data_ptr(), rtok.shape[0], float(ROPE_BASE)
+        pos, rc, qc, qs = (tuple(rope) + (0, 1.0))[:4]
+        if isinstance(pos, torch.Tensor) and pos.dtype != torch.int32:
+            raise TypeError(f"rope: expected int32 [T,2] token grid positions (y, x), got {pos.dtype} - the epilogue computes "
+                            "cos / sin itself and takes no coefficient table")
+        d.rope_max_pos = _rope_pmax(pos)                          # keyed by the caller's tensor (rope_bound)
+        pos = _ffi.check(pos, torch.int32, "rope positions", (None, 2))
+        d.rope_pos, d.tokens_per_image, d.rope_base = pos.data_ptr(), pos.shape[0], float(rope_base)
         d.rope_cols, d.q_cols, d.q_scale = int(rc), int(qc), float(qs)
-    if fold_out is not None:
-        x16, stats = fold_out
-        slots = ln_slot_count(m, n, 2 if grouped else 1)
-        if (x16.dtype != a.dtype or tuple(x16.shape) != tuple(out.shape) or not x16.is_contiguous() or stats.dtype != torch.float32
-                or tuple(stats.shape) != lead + (slots, m, 2) or not stats.is_contiguous() or ldc != n):
-            raise ValueError("bad fold_out buffers (ln_fold_buffers)")
-        d.c16, d.stats_out, d.stats_slots = x16.data_ptr(), stats.data_ptr(), slots
-        d.stats_gstride = m * slots * 2 if grouped else 0
     if fold_in is not None:
         stats, cs0 = fold_in[0], fold_in[1]
         cs1 = fold_in[2] if len(fold_in) > 2 else None
@@ -745,11 +661,8 @@ def gemm_ex(a, w, bias=None, epi: int = EPI_BF16, out=None, resid=None, w1=None,
         d.ln_gstride = (-per if a_swap else per) if grouped else 0
     e0 = _prof_begin()
     _ffi.call("m3_gemm_ex", C.addressof(d), _ffi.stream_ptr())
-    g = 2 if grouped else 1
-    nb = 2.0 * (m * k + n * k) + out.element_size() * m * n * (1 if resid is None else 2)
-    if fold_out is not None:
-        nb += 2.0 * m * n + 8.0 * m * (n // 32)
-    _prof_end(e0, _gemm_kind(m, n, g), 2.0 * g * m * n * k, g * nb, f"gemm_ex {g}x{m}x{n}x{k} epi{epi} {a.dtype}")
+    _prof_end(e0, _gemm_kind(m, n, g), 2.0 * g * m * n * k, g * nb,
+              f"gemm_ex{' hl' if hl is not None else ''} {g}x{m}x{n}x{k} epi{epi} {a.dtype}")
     return out
 
 
