@@ -369,6 +369,54 @@ int m3_retrieval_topk(const float *qsig, int64_t ldq, const float *db, int64_t l
                       int use_thresh, float min_thresh, int causal, int32_t *count, int32_t *idx, float *score, void *ws,
                       int64_t ws_bytes, void *stream);
 
+/* ----------------------------------------------------------------- map export */
+
+/* Dense map export (slam.py:320-415 _get_results / save_pointcloud).  Host side: mast3r_slam/export.py.
+ *
+ * K keyframes share a point count N and arrive as DEVICE tables with one entry per keyframe: X[k] -> float [N,3]
+ * canonical points, C[k] -> float [N] summed confidence, img[k] -> the colour image, poses [K,8] (t, q xyzw, s),
+ * Nk [K] int32 fusion counts.  Source point (k, n) is kept when C[k][n] / (float)Nk[k] > thresh (IEEE fp32 divide,
+ * strict, NaN fails; use_thresh = 0 skips this test) and all three components of the world point s R X + t are finite.
+ * Kept points are written in ascending source index k * N + n:
+ *   points float [M,3], colors uint8 [M,3], and when the pointers are not NULL index int64 [M] (the source index) and
+ *   conf float [M] (the average confidence, the input of the voxel stage).
+ * layout M3_MAP_IMG_F32_CHW: img[k] is float [3,N] planes, colour = (uint8)floorf(min(max(v, 0), 1) * 255.0f), NaN -> 0;
+ * M3_MAP_IMG_U8_HWC: img[k] is uint8 [N,3], passed through.  16-byte loads are used per keyframe when N % 4 == 0 and
+ * its arrays are 16-byte aligned; any other input takes scalar loads, with the same result.
+ *
+ * m3_map_export_count: two launches (kept points per 1024-point workgroup tile, then an exclusive scan in one
+ * workgroup).  Afterwards the first int32 of ws is M - the one value the host has to read - and the rest holds the
+ * tile offsets.  m3_map_export_scatter: one launch with the SAME inputs, threshold and ws, M as read back (>= 1; the
+ * host launches nothing when M = 0) and outputs of exactly M rows.  No launch count depends on K.  Output positions
+ * come from the scan, never from an atomic counter: two calls give identical bytes.
+ * ws: m3_map_export_ws_bytes(K, N) bytes (0 = unsupported shape: K * N must stay below 2^31), 16-byte aligned.
+ *
+ * Voxel thinning of an exported cloud (points / conf / colors / index as written above, M rows): the voxel of a point
+ * is floorf(p / voxel_size) per axis (correctly rounded fp32 divide); per occupied voxel the point with the largest
+ * confidence survives, equal confidences (-0 = +0) go to the smaller row, a NaN confidence ranks below every number;
+ * survivors keep their order.  A point with |voxel coordinate| >= 2^20 on any axis does not fit the 3 x 21-bit key: it
+ * is dropped and counted.  m3_map_voxel_count: clears an open-addressing table of m3_map_voxel_table_slots(M) 64-bit
+ * keys (claimed with atomicCAS) and values (confidence key << 32 | ~row, raised with atomicMax), inserts, counts the
+ * winners per tile and scans.  Afterwards ws int32 [0] = M2 (survivors) and [1] = dropped points.  Integer atomics
+ * commute, so the result is reproducible bit for bit.  m3_map_voxel_scatter: one launch, M2 as read back (>= 1),
+ * outputs of exactly M2 rows; index may be NULL (index_out then receives the row number in the input cloud), index_out
+ * may be NULL.  ws: m3_map_voxel_ws_bytes(M) bytes, 16-byte aligned; 1 <= M < 2^31. */
+enum { M3_MAP_IMG_F32_CHW = 0, M3_MAP_IMG_U8_HWC = 1 };
+int64_t m3_map_export_ws_bytes(int K, int N);
+int m3_map_export_count(const float *const *X, const float *const *C, const float *poses, const int32_t *Nk, int K, int N,
+                        int use_thresh, float thresh, void *ws, int64_t ws_bytes, void *stream);
+int m3_map_export_scatter(const float *const *X, const float *const *C, const void *const *img, const float *poses,
+                          const int32_t *Nk, int K, int N, int use_thresh, float thresh, int layout, const void *ws,
+                          int64_t ws_bytes, int64_t M, float *points, uint8_t *colors, int64_t *index, float *conf,
+                          void *stream);
+int64_t m3_map_voxel_table_slots(int64_t M);
+int64_t m3_map_voxel_ws_bytes(int64_t M);
+int m3_map_voxel_count(const float *points, const float *conf, int64_t M, float voxel_size, void *ws, int64_t ws_bytes,
+                       void *stream);
+int m3_map_voxel_scatter(const float *points, const uint8_t *colors, const int64_t *index, int64_t M, const void *ws,
+                         int64_t ws_bytes, int64_t M2, float *points_out, uint8_t *colors_out, int64_t *index_out,
+                         void *stream);
+
 #ifdef __cplusplus
 }
 #endif

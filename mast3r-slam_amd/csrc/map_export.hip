@@ -1,0 +1,442 @@
+// Dense map export (mast3r_slam/export.py): world points and colours of K keyframes, filtered by average confidence,
+// compacted in source order and optionally thinned to one point per voxel.  Stage A is count -> scan -> scatter over
+// 1024-point workgroup tiles; stage B claims voxels in an open-addressing table with integer atomics and then reuses the
+// same count -> scan -> scatter.  Output positions come from an exclusive scan, never from an atomic counter, and the
+// only atomics are integer CAS / max, so the bytes of every output are the same on every call.
+#include "common.h"
+#include "sim3_dev.h"
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kPts = 4;                       // consecutive points per thread: one 16-byte load of C, three of X
+constexpr int kTile = kThreads * kPts;        // points per workgroup
+constexpr int kScanThreads = 1024;
+constexpr int kHdrWords = 4;                  // ws words: [0] kept count, [1] points dropped by the voxel key (stage B), [2..3] unused
+constexpr unsigned long long kEmpty = ~0ull;  // a packed voxel key uses 63 bits
+
+__device__ __forceinline__ bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
+
+// Position of this thread's first kept point among the workgroup's kept points (source order: thread, then bit), and the
+// workgroup's total.  keep: bit j = point j of this thread is kept.
+__device__ __forceinline__ int block_prefix(unsigned keep, int &total) {
+    __shared__ int wsum[kThreads / M3_WAVE];
+    int before = 0, wtot = 0;
+#pragma unroll
+    for (int j = 0; j < kPts; ++j) {
+        const unsigned long long b = __ballot((keep >> j) & 1u);
+        before += __builtin_amdgcn_mbcnt_hi((unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, 0u));
+        wtot += __popcll(b);
+    }
+    const int w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) wsum[w] = wtot;
+    __syncthreads();
+    int base = 0;
+    total = 0;
+#pragma unroll
+    for (int i = 0; i < kThreads / M3_WAVE; ++i) {
+        base += i < w ? wsum[i] : 0;
+        total += wsum[i];
+    }
+    return base + before;
+}
+
+// ---- stage A -----------------------------------------------------------------------------------------------------
+struct Tile {
+    int k, n0;            // keyframe, first point of this thread
+    bool vec;             // 16-byte path: all four points exist and the keyframe's arrays are 16-byte aligned
+};
+
+__device__ __forceinline__ Tile tile_of(int N, int tiles) {
+    Tile t;
+    t.k = blockIdx.x / tiles;
+    t.n0 = (blockIdx.x - t.k * tiles) * kTile + threadIdx.x * kPts;
+    t.vec = false;
+    return t;
+}
+
+// Average confidence of the thread's points (C / N_k, IEEE divide) and the bits of those that pass the strict test.
+__device__ __forceinline__ unsigned conf_pass(const float *__restrict__ Ck, const Tile &t, int N, float nk, int use_thresh,
+                                              float thresh, float (&avg)[kPts]) {
+    float c[kPts];
+    if (t.vec) {
+        const float4 v = *(const float4 *)(Ck + t.n0);
+        c[0] = v.x; c[1] = v.y; c[2] = v.z; c[3] = v.w;
+    } else {
+#pragma unroll
+        for (int j = 0; j < kPts; ++j) c[j] = t.n0 + j < N ? Ck[t.n0 + j] : 0.f;
+    }
+    unsigned pass = 0;
+#pragma unroll
+    for (int j = 0; j < kPts; ++j) {
+        avg[j] = c[j] / nk;
+        if (t.n0 + j < N && (!use_thresh || avg[j] > thresh)) pass |= 1u << j;
+    }
+    return pass;
+}
+
+// World points of the thread's points whose bit is set in `want`; returns the bits whose world point is finite.
+__device__ __forceinline__ unsigned world_points(const float *__restrict__ Xk, const Tile &t, const Pose<float> &T,
+                                                 unsigned want, V3<float> (&p)[kPts]) {
+    float x[3 * kPts];
+    if (t.vec) {
+        const float4 *src = (const float4 *)(Xk + (size_t)3 * t.n0);
+        const float4 a = src[0], b = src[1], c = src[2];
+        x[0] = a.x; x[1] = a.y; x[2] = a.z; x[3] = a.w; x[4] = b.x; x[5] = b.y; x[6] = b.z; x[7] = b.w;
+        x[8] = c.x; x[9] = c.y; x[10] = c.z; x[11] = c.w;
+    } else {
+#pragma unroll
+        for (int j = 0; j < kPts; ++j) {
+            const bool on = (want >> j) & 1u;
+#pragma unroll
+            for (int d = 0; d < 3; ++d) x[3 * j + d] = on ? Xk[(size_t)3 * (t.n0 + j) + d] : 0.f;
+        }
+    }
+    unsigned keep = 0;
+#pragma unroll
+    for (int j = 0; j < kPts; ++j) {
+        p[j] = act(T, V3<float>{x[3 * j], x[3 * j + 1], x[3 * j + 2]});
+        if (((want >> j) & 1u) && isfinite(p[j].x) && isfinite(p[j].y) && isfinite(p[j].z)) keep |= 1u << j;
+    }
+    return keep;
+}
+
+__device__ __forceinline__ unsigned char to_u8(float v) {
+    return (unsigned char)floorf(fminf(fmaxf(v, 0.f), 1.f) * 255.0f);        // fmaxf(NaN, 0) = 0
+}
+
+// Kept points per workgroup.  X is only read by threads with a point that passed the confidence test.
+__global__ void __launch_bounds__(kThreads) k_export_count(const float *const *__restrict__ X,
+                                                            const float *const *__restrict__ C,
+                                                            const float *__restrict__ poses, const int32_t *__restrict__ Nk,
+                                                            int N, int tiles, int use_thresh, float thresh,
+                                                            int32_t *__restrict__ cnt) {
+    Tile t = tile_of(N, tiles);
+    const float *Xk = X[t.k], *Ck = C[t.k];
+    t.vec = t.n0 + kPts <= N && N % 4 == 0 && aligned16(Xk) && aligned16(Ck);
+    float avg[kPts];
+    unsigned keep = conf_pass(Ck, t, N, (float)Nk[t.k], use_thresh, thresh, avg);
+    if (keep) {
+        V3<float> p[kPts];
+        keep = world_points(Xk, t, load_pose<float>(poses + 8 * t.k), keep, p);
+    }
+    int total;
+    block_prefix(keep, total);
+    if (threadIdx.x == 0) cnt[blockIdx.x] = total;
+}
+
+// Exclusive scan of cnt[0..B) in place, one workgroup; hdr[0] = the total.
+__global__ void __launch_bounds__(kScanThreads) k_export_scan(int32_t *__restrict__ cnt, int B, int32_t *__restrict__ hdr) {
+    __shared__ int wsum[kScanThreads / M3_WAVE];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    int carry = 0;
+    for (int i0 = 0; i0 < B; i0 += kScanThreads * 4) {
+        const int i = i0 + threadIdx.x * 4;
+        int v[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = i + j < B ? cnt[i + j] : 0;
+        const int mine = (v[0] + v[1]) + (v[2] + v[3]);
+        int incl = mine;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const int o = __shfl_up(incl, off, 64);
+            if (lane >= off) incl += o;
+        }
+        if (lane == 63) wsum[w] = incl;
+        __syncthreads();
+        int base = carry, all = 0;
+#pragma unroll
+        for (int ww = 0; ww < kScanThreads / M3_WAVE; ++ww) {
+            base += ww < w ? wsum[ww] : 0;
+            all += wsum[ww];
+        }
+        int run = base + incl - mine;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (i + j < B) cnt[i + j] = run;
+            run += v[j];
+        }
+        carry += all;
+        __syncthreads();                               // wsum is rewritten by the next round
+    }
+    if (threadIdx.x == 0) hdr[0] = carry;
+}
+
+// LAYOUT 0: float32 [3,H,W] planes in [0,1]; 1: uint8 [H,W,3].
+template <int LAYOUT>
+__global__ void __launch_bounds__(kThreads) k_export_scatter(const float *const *__restrict__ X,
+                                                              const float *const *__restrict__ C,
+                                                              const void *const *__restrict__ img,
+                                                              const float *__restrict__ poses, const int32_t *__restrict__ Nk,
+                                                              int N, int tiles, int use_thresh, float thresh,
+                                                              const int32_t *__restrict__ offs, int64_t M,
+                                                              float *__restrict__ points, unsigned char *__restrict__ colors,
+                                                              int64_t *__restrict__ index, float *__restrict__ conf) {
+    Tile t = tile_of(N, tiles);
+    const float *Xk = X[t.k], *Ck = C[t.k];
+    const void *Ik = img[t.k];
+    t.vec = t.n0 + kPts <= N && N % 4 == 0 && aligned16(Xk) && aligned16(Ck);
+    float avg[kPts];
+    unsigned keep = conf_pass(Ck, t, N, (float)Nk[t.k], use_thresh, thresh, avg);
+    V3<float> p[kPts];
+    if (keep) keep = world_points(Xk, t, load_pose<float>(poses + 8 * t.k), keep, p);
+    int total;
+    int64_t o = (int64_t)offs[blockIdx.x] + block_prefix(keep, total);
+    if (!keep) return;
+    unsigned char rgb[kPts][3];
+    if constexpr (LAYOUT == 0) {
+        const float *I = (const float *)Ik;
+        if (t.vec && aligned16(I)) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const float4 v = *(const float4 *)(I + (size_t)c * N + t.n0);
+                rgb[0][c] = to_u8(v.x); rgb[1][c] = to_u8(v.y); rgb[2][c] = to_u8(v.z); rgb[3][c] = to_u8(v.w);
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < kPts; ++j)
+#pragma unroll
+                for (int c = 0; c < 3; ++c) rgb[j][c] = (keep >> j) & 1u ? to_u8(I[(size_t)c * N + t.n0 + j]) : 0;
+        }
+    } else {
+        const unsigned char *I = (const unsigned char *)Ik;
+        if (t.vec && ((uintptr_t)I & 3) == 0) {                                 // 12 bytes from a 4-byte aligned address
+            const unsigned *src = (const unsigned *)(I + (size_t)3 * t.n0);
+            const unsigned w[3] = {src[0], src[1], src[2]};
+#pragma unroll
+            for (int b = 0; b < 12; ++b) rgb[b / 3][b % 3] = (unsigned char)(w[b / 4] >> (8 * (b % 4)));
+        } else {
+#pragma unroll
+            for (int j = 0; j < kPts; ++j)
+#pragma unroll
+                for (int c = 0; c < 3; ++c) rgb[j][c] = (keep >> j) & 1u ? I[(size_t)3 * (t.n0 + j) + c] : 0;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < kPts; ++j) {
+        if (!((keep >> j) & 1u) || o >= M) continue;                            // o < M always holds for a ws from the same inputs
+        points[3 * o] = p[j].x; points[3 * o + 1] = p[j].y; points[3 * o + 2] = p[j].z;
+        colors[3 * o] = rgb[j][0]; colors[3 * o + 1] = rgb[j][1]; colors[3 * o + 2] = rgb[j][2];
+        if (index) index[o] = (int64_t)t.k * N + t.n0 + j;
+        if (conf) conf[o] = avg[j];
+        ++o;
+    }
+}
+
+// ---- stage B -----------------------------------------------------------------------------------------------------
+struct VoxelWs {
+    int32_t *hdr, *offs;
+    uint32_t *slot;                  // [M] table slot of each point, 0xffffffff = dropped
+    unsigned long long *keys, *vals; // [slots]
+    int64_t slots, blocks, bytes;
+};
+
+inline int64_t voxel_slots(int64_t M) {
+    int64_t s = 1024;
+    while (s < 2 * M) s *= 2;        // at most half full
+    return s;
+}
+
+inline VoxelWs voxel_ws(void *ws, int64_t M) {
+    VoxelWs v;
+    v.blocks = (M + kTile - 1) / kTile;
+    v.slots = voxel_slots(M);
+    char *p = (char *)ws;
+    v.hdr = (int32_t *)p;
+    v.offs = v.hdr + kHdrWords;
+    int64_t off = (kHdrWords + (v.blocks + 3) / 4 * 4) * 4;
+    v.slot = (uint32_t *)(p + off);
+    off += (M + 3) / 4 * 4 * 4;
+    v.keys = (unsigned long long *)(p + off);
+    off += v.slots * 8;
+    v.vals = (unsigned long long *)(p + off);
+    v.bytes = off + v.slots * 8;
+    return v;
+}
+
+// Order-preserving unsigned key of a float (-0 = +0; NaN ranks below every number).
+__device__ __forceinline__ unsigned conf_key(float c) {
+    if (c != c) return 0u;
+    const unsigned u = __float_as_uint(c + 0.f);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+__device__ __forceinline__ unsigned long long mix64(unsigned long long x) {
+    x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ull;
+    x ^= x >> 27; x *= 0x94d049bb133111ebull;
+    return x ^ (x >> 31);
+}
+
+// One point per thread: claim the voxel's slot (CAS on the key) and raise its value to (confidence key, ~i): the
+// largest confidence wins, equal confidences go to the smaller i.  Both atomics commute, so the winner does not depend
+// on the order in which points arrive (the slot a voxel lands in does; nothing that is output depends on it).
+__global__ void __launch_bounds__(kThreads) k_voxel_insert(const float *__restrict__ points, const float *__restrict__ conf,
+                                                            int64_t M, float voxel, unsigned long long *__restrict__ keys,
+                                                            unsigned long long *__restrict__ vals, int64_t slots,
+                                                            uint32_t *__restrict__ slot, int32_t *__restrict__ hdr) {
+    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= M) return;
+    const float vx = floorf(points[3 * i] / voxel), vy = floorf(points[3 * i + 1] / voxel),
+                vz = floorf(points[3 * i + 2] / voxel);
+    constexpr float kLim = 1048576.f;                                           // 2^20: 21 bits per axis after the offset
+    if (!(fabsf(vx) < kLim && fabsf(vy) < kLim && fabsf(vz) < kLim)) {
+        slot[i] = 0xffffffffu;
+        atomicAdd(&hdr[1], 1);
+        return;
+    }
+    const unsigned long long key = ((unsigned long long)((int)vx + 1048576) << 42) |
+                                   ((unsigned long long)((int)vy + 1048576) << 21) |
+                                   (unsigned long long)((int)vz + 1048576);
+    const unsigned long long val = ((unsigned long long)conf_key(conf[i]) << 32) | (unsigned)~(unsigned)i;
+    unsigned long long s = mix64(key) & (unsigned long long)(slots - 1);
+    for (int64_t probe = 0; probe < slots; ++probe) {                           // the table is at most half full
+        unsigned long long cur = keys[s];
+        if (cur == kEmpty) cur = atomicCAS(&keys[s], kEmpty, key);
+        if (cur == kEmpty || cur == key) {
+            atomicMax(&vals[s], val);
+            slot[i] = (uint32_t)s;
+            return;
+        }
+        s = (s + 1) & (unsigned long long)(slots - 1);
+    }
+    slot[i] = 0xffffffffu;                                                      // unreachable: slots >= 2 M
+    atomicAdd(&hdr[1], 1);
+}
+
+// Bits of the thread's four consecutive points that won their voxel.
+__device__ __forceinline__ unsigned voxel_winners(const uint32_t *__restrict__ slot,
+                                                  const unsigned long long *__restrict__ vals, int64_t i0, int64_t M) {
+    unsigned keep = 0;
+#pragma unroll
+    for (int j = 0; j < kPts; ++j) {
+        const int64_t i = i0 + j;
+        if (i >= M) continue;
+        const uint32_t s = slot[i];
+        if (s != 0xffffffffu && (unsigned)vals[s] == (unsigned)~(unsigned)i) keep |= 1u << j;
+    }
+    return keep;
+}
+
+__global__ void __launch_bounds__(kThreads) k_voxel_count(const uint32_t *__restrict__ slot,
+                                                           const unsigned long long *__restrict__ vals, int64_t M,
+                                                           int32_t *__restrict__ cnt) {
+    const unsigned keep = voxel_winners(slot, vals, (int64_t)blockIdx.x * kTile + threadIdx.x * kPts, M);
+    int total;
+    block_prefix(keep, total);
+    if (threadIdx.x == 0) cnt[blockIdx.x] = total;
+}
+
+__global__ void __launch_bounds__(kThreads) k_voxel_scatter(const float *__restrict__ points,
+                                                             const unsigned char *__restrict__ colors,
+                                                             const int64_t *__restrict__ index,
+                                                             const uint32_t *__restrict__ slot,
+                                                             const unsigned long long *__restrict__ vals, int64_t M,
+                                                             const int32_t *__restrict__ offs, int64_t M2,
+                                                             float *__restrict__ points_out,
+                                                             unsigned char *__restrict__ colors_out,
+                                                             int64_t *__restrict__ index_out) {
+    const int64_t i0 = (int64_t)blockIdx.x * kTile + threadIdx.x * kPts;
+    const unsigned keep = voxel_winners(slot, vals, i0, M);
+    int total;
+    int64_t o = (int64_t)offs[blockIdx.x] + block_prefix(keep, total);
+#pragma unroll
+    for (int j = 0; j < kPts; ++j) {
+        if (!((keep >> j) & 1u) || o >= M2) continue;
+        const int64_t i = i0 + j;
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            points_out[3 * o + d] = points[3 * i + d];
+            colors_out[3 * o + d] = colors[3 * i + d];
+        }
+        if (index_out) index_out[o] = index ? index[i] : i;
+        ++o;
+    }
+}
+
+inline bool export_shape_ok(int K, int N) {
+    return K >= 1 && N >= 1 && (int64_t)K * N <= 0x7fffffff && (int64_t)K * m3_cdiv(N, kTile) <= (1 << 30);
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t m3_map_export_ws_bytes(int K, int N) {
+    if (!export_shape_ok(K, N)) return 0;
+    const int64_t blocks = (int64_t)K * m3_cdiv(N, kTile);
+    return (kHdrWords + (blocks + 3) / 4 * 4) * 4;
+}
+
+int m3_map_export_count(const float *const *X, const float *const *C, const float *poses, const int32_t *Nk, int K, int N,
+                        int use_thresh, float thresh, void *ws, int64_t ws_bytes, void *stream) {
+    M3_REQUIRE(X && C && poses && Nk && ws && export_shape_ok(K, N));
+    M3_REQUIRE((use_thresh == 0 || use_thresh == 1) && ((uintptr_t)ws & 15) == 0 && ws_bytes >= m3_map_export_ws_bytes(K, N));
+    hipStream_t st = (hipStream_t)stream;
+    const int tiles = m3_cdiv(N, kTile), blocks = K * tiles;
+    int32_t *hdr = (int32_t *)ws;
+    hipLaunchKernelGGL(k_export_count, dim3(blocks), dim3(kThreads), 0, st, X, C, poses, Nk, N, tiles, use_thresh, thresh,
+                       hdr + kHdrWords);
+    hipLaunchKernelGGL(k_export_scan, dim3(1), dim3(kScanThreads), 0, st, hdr + kHdrWords, blocks, hdr);
+    M3_CHECK_LAUNCH("m3_map_export_count");
+    return M3_OK;
+}
+
+int m3_map_export_scatter(const float *const *X, const float *const *C, const void *const *img, const float *poses,
+                          const int32_t *Nk, int K, int N, int use_thresh, float thresh, int layout, const void *ws,
+                          int64_t ws_bytes, int64_t M, float *points, uint8_t *colors, int64_t *index, float *conf,
+                          void *stream) {
+    M3_REQUIRE(X && C && img && poses && Nk && ws && points && colors && export_shape_ok(K, N));
+    M3_REQUIRE((use_thresh == 0 || use_thresh == 1) && ((uintptr_t)ws & 15) == 0 && ws_bytes >= m3_map_export_ws_bytes(K, N));
+    M3_REQUIRE(M >= 1 && M <= (int64_t)K * N);
+    M3_REQUIRE(layout == M3_MAP_IMG_F32_CHW || layout == M3_MAP_IMG_U8_HWC);
+    hipStream_t st = (hipStream_t)stream;
+    const int tiles = m3_cdiv(N, kTile), blocks = K * tiles;
+    const int32_t *offs = (const int32_t *)ws + kHdrWords;
+    if (layout == M3_MAP_IMG_F32_CHW)
+        hipLaunchKernelGGL(k_export_scatter<0>, dim3(blocks), dim3(kThreads), 0, st, X, C, img, poses, Nk, N, tiles,
+                           use_thresh, thresh, offs, M, points, colors, index, conf);
+    else
+        hipLaunchKernelGGL(k_export_scatter<1>, dim3(blocks), dim3(kThreads), 0, st, X, C, img, poses, Nk, N, tiles,
+                           use_thresh, thresh, offs, M, points, colors, index, conf);
+    M3_CHECK_LAUNCH("m3_map_export_scatter");
+    return M3_OK;
+}
+
+int64_t m3_map_voxel_table_slots(int64_t M) {
+    return M >= 1 && M <= 0x7fffffff ? voxel_slots(M) : 0;
+}
+
+int64_t m3_map_voxel_ws_bytes(int64_t M) {
+    return M >= 1 && M <= 0x7fffffff ? voxel_ws(nullptr, M).bytes : 0;
+}
+
+int m3_map_voxel_count(const float *points, const float *conf, int64_t M, float voxel_size, void *ws, int64_t ws_bytes,
+                       void *stream) {
+    M3_REQUIRE(points && conf && ws && M >= 1 && M <= 0x7fffffff && voxel_size > 0.f && voxel_size < INFINITY);
+    M3_REQUIRE(((uintptr_t)ws & 15) == 0 && ws_bytes >= m3_map_voxel_ws_bytes(M));
+    hipStream_t st = (hipStream_t)stream;
+    const VoxelWs v = voxel_ws(ws, M);
+    M3_CHECK_HIP(hipMemsetAsync(v.hdr, 0, kHdrWords * 4, st), "m3_map_voxel_count/memset");
+    M3_CHECK_HIP(hipMemsetAsync(v.keys, 0xff, v.slots * 8, st), "m3_map_voxel_count/memset");
+    M3_CHECK_HIP(hipMemsetAsync(v.vals, 0, v.slots * 8, st), "m3_map_voxel_count/memset");
+    hipLaunchKernelGGL(k_voxel_insert, dim3(m3_cdiv(M, kThreads)), dim3(kThreads), 0, st, points, conf, M, voxel_size,
+                       v.keys, v.vals, v.slots, v.slot, v.hdr);
+    hipLaunchKernelGGL(k_voxel_count, dim3((int)v.blocks), dim3(kThreads), 0, st, v.slot, v.vals, M, v.offs);
+    hipLaunchKernelGGL(k_export_scan, dim3(1), dim3(kScanThreads), 0, st, v.offs, (int)v.blocks, v.hdr);
+    M3_CHECK_LAUNCH("m3_map_voxel_count");
+    return M3_OK;
+}
+
+int m3_map_voxel_scatter(const float *points, const uint8_t *colors, const int64_t *index, int64_t M, const void *ws,
+                         int64_t ws_bytes, int64_t M2, float *points_out, uint8_t *colors_out, int64_t *index_out,
+                         void *stream) {
+    M3_REQUIRE(points && colors && ws && points_out && colors_out && M >= 1 && M <= 0x7fffffff && M2 >= 1 && M2 <= M);
+    M3_REQUIRE(((uintptr_t)ws & 15) == 0 && ws_bytes >= m3_map_voxel_ws_bytes(M));
+    const VoxelWs v = voxel_ws(const_cast<void *>(ws), M);
+    hipLaunchKernelGGL(k_voxel_scatter, dim3((int)v.blocks), dim3(kThreads), 0, (hipStream_t)stream, points, colors, index,
+                       v.slot, v.vals, M, v.offs, M2, points_out, colors_out, index_out);
+    M3_CHECK_LAUNCH("m3_map_voxel_scatter");
+    return M3_OK;
+}
+
+}  // extern "C"

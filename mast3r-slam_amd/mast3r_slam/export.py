@@ -1,0 +1,193 @@
+"""Dense map export: what the reference's slam.py:320-415 (_get_results, save_trajectory, save_pointcloud) hands a user,
+a coloured point cloud and a trajectory on disk.
+
+collect_map gathers the world points and colours of every keyframe in ONE batched device pass (csrc/map_export.hip):
+Sim(3) act, a test on the average confidence, the colour conversion and an ordered stream compaction, optionally
+followed by voxel thinning.  The number of launches does not depend on the number of keyframes, the host reads one
+integer (the kept count M) before it allocates exact-size outputs, and two calls give identical bytes.
+
+    kept(k, n)  <=>  C[k][n] / N_k > c_conf_threshold   (fp32 divide as Frame.get_average_conf; strict; NaN fails)
+                     and the world point s R X + t is finite
+    order       =    ascending k * N + n
+    colours     =    float [3,H,W]: (uint8)floor(clip(v, 0, 1) * 255), NaN -> 0;  uint8 [H,W,3]: passed through
+
+`c_conf_threshold` defaults to 1.5, the value DEFAULT_CONFIG already uses for its Q_conf gates.  It is this project's
+choice and a function argument, not a config key: the reference exports every point and has no such constant.  The
+reference also writes ASCII PLY in a Python loop; here the body is one structured numpy array written in binary
+(`binary=False` keeps the ASCII form for small clouds).  CPU tensors raise RuntimeError: there is no CPU path.
+"""
+from __future__ import annotations
+
+import os
+from typing import Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import _ffi
+
+__all__ = ["collect_map", "save_ply", "save_trajectory"]
+
+IMG_F32_CHW, IMG_U8_HWC = 0, 1                                         # include/m3slam.h
+_PLY_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")])
+
+last_voxel_stats: dict = {}           # table slots / occupied voxels of the most recent voxel pass (tools/bench_map_export.py)
+
+
+def _empty(device, return_index: bool):
+    out = (torch.empty((0, 3), dtype=torch.float32, device=device), torch.empty((0, 3), dtype=torch.uint8, device=device))
+    return out + (torch.empty((0,), dtype=torch.int64, device=device),) if return_index else out
+
+
+def _image(f, n: int):
+    """(layout, contiguous image) of a frame; ValueError for anything but float32 [3,H,W] / uint8 [H,W,3] with H*W = n."""
+    img = f.img
+    if not isinstance(img, torch.Tensor) or img.dim() != 3:
+        raise ValueError(f"frame {f.frame_id}: image must be a [3,H,W] float32 or [H,W,3] uint8 tensor")
+    if img.dtype == torch.float32 and img.shape[0] == 3:
+        layout, hw = IMG_F32_CHW, img.shape[1] * img.shape[2]
+    elif img.dtype == torch.uint8 and img.shape[2] == 3:
+        layout, hw = IMG_U8_HWC, img.shape[0] * img.shape[1]
+    else:
+        raise ValueError(f"frame {f.frame_id}: unsupported image {img.dtype} {tuple(img.shape)}; expected float32 [3,H,W] "
+                         "or uint8 [H,W,3]")
+    if hw != n:
+        raise ValueError(f"frame {f.frame_id}: image has {hw} pixels, pointmap has {n} points")
+    return layout, img
+
+
+def collect_map(keyframes, c_conf_threshold: Optional[float] = 1.5, voxel_size: Optional[float] = None,
+                return_index: bool = False):
+    """World points float32 [M,3], colours uint8 [M,3] and (return_index) source indices int64 [M] of `keyframes`
+    (a Keyframes or a sequence of Frame; frames without a pointmap are skipped), as device tensors.
+
+    c_conf_threshold None keeps every finite point.  voxel_size > 0 keeps one point per occupied voxel
+    floor(p / voxel_size): the one with the largest average confidence, ties to the smaller source index; ValueError
+    when a voxel coordinate reaches 2^20 (voxel_size too small for the extent of the map)."""
+    frames = [f for f in (keyframes._frames if hasattr(keyframes, "_frames") else list(keyframes)) if f.X_canon is not None]
+    if voxel_size is not None and not float(voxel_size) > 0.0:
+        raise ValueError(f"voxel_size must be positive, got {voxel_size}")
+    if not frames:
+        return _empty("cuda" if torch.cuda.is_available() else "cpu", return_index)
+    n = frames[0].X_canon.reshape(-1, 3).shape[0]
+    layouts, hold = set(), []
+    for f in frames:
+        X = f.X_canon.reshape(-1, 3)
+        if X.shape[0] != n:
+            raise ValueError(f"frame {f.frame_id}: {X.shape[0]} points, the first keyframe has {n}")
+        if f.C is None or f.C.numel() != n:
+            raise ValueError(f"frame {f.frame_id}: confidence does not have one value per point")
+        layout, img = _image(f, n)
+        layouts.add(layout)
+        hold.append((X, f.C.reshape(-1), img))
+    if len(layouts) != 1:
+        raise ValueError("keyframes mix float32 [3,H,W] and uint8 [H,W,3] images")
+    layout = layouts.pop()
+    dev = frames[0].X_canon.device
+    # contiguous device tensors, kept alive until the launches are queued (the kernel takes scalar loads for a keyframe
+    # whose arrays are not 16-byte aligned)
+    hold = [(_ffi.check(X, torch.float32, "X_canon"), _ffi.check(C, torch.float32, "C"),
+             _ffi.check(img, (torch.float32, torch.uint8), "img")) for X, C, img in hold]
+    k = len(hold)
+    L = _ffi.lib()
+    ws_bytes = int(L.m3_map_export_ws_bytes(k, n))
+    if ws_bytes <= 0:
+        raise ValueError(f"map of {k} x {n} points is too large for one export (limit 2^31 - 1 points)")
+    table = torch.tensor([[t.data_ptr() for t in col] for col in zip(*hold)], dtype=torch.int64).to(dev)   # [3,K]
+    nk = torch.tensor([int(f.N) for f in frames], dtype=torch.int32).to(dev)
+    poses = torch.cat([_ffi.check(f.T_WC.reshape(1, 8), torch.float32, "T_WC") for f in frames])
+    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+    use, thr = (0, 0.0) if c_conf_threshold is None else (1, float(c_conf_threshold))
+    st = _ffi.stream_ptr()
+    _ffi.call("m3_map_export_count", _ffi.ptr(table[0]), _ffi.ptr(table[1]), _ffi.ptr(poses), _ffi.ptr(nk), k, n, use, thr,
+              _ffi.ptr(ws), ws_bytes, st)
+    m = int(ws[:4].view(torch.int32).item())                           # the one synchronisation of stage A
+    if m == 0:
+        return _empty(dev, return_index)
+    thin = voxel_size is not None
+    points = torch.empty((m, 3), dtype=torch.float32, device=dev)
+    colors = torch.empty((m, 3), dtype=torch.uint8, device=dev)
+    index = torch.empty((m,), dtype=torch.int64, device=dev) if return_index else None
+    conf = torch.empty((m,), dtype=torch.float32, device=dev) if thin else None
+    _ffi.call("m3_map_export_scatter", _ffi.ptr(table[0]), _ffi.ptr(table[1]), _ffi.ptr(table[2]), _ffi.ptr(poses),
+              _ffi.ptr(nk), k, n, use, thr, layout, _ffi.ptr(ws), ws_bytes, m, _ffi.ptr(points), _ffi.ptr(colors),
+              _ffi.ptr(index), _ffi.ptr(conf), st)
+    if thin:
+        points, colors, index = _voxel_thin(points, colors, index, conf, float(voxel_size))
+    return (points, colors, index) if return_index else (points, colors)
+
+
+def _voxel_thin(points, colors, index, conf, voxel_size: float):
+    L = _ffi.lib()
+    m, dev = points.shape[0], points.device
+    ws_bytes = int(L.m3_map_voxel_ws_bytes(m))
+    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+    st = _ffi.stream_ptr()
+    _ffi.call("m3_map_voxel_count", _ffi.ptr(points), _ffi.ptr(conf), m, voxel_size, _ffi.ptr(ws), ws_bytes, st)
+    m2, dropped = ws[:8].view(torch.int32).tolist()
+    if dropped:
+        raise ValueError(f"voxel_size {voxel_size} is too small for this map: {dropped} points have a voxel coordinate "
+                         "beyond +-2^20")
+    last_voxel_stats.update(points=m, slots=int(L.m3_map_voxel_table_slots(m)), voxels=m2)
+    p2 = torch.empty((m2, 3), dtype=torch.float32, device=dev)
+    c2 = torch.empty((m2, 3), dtype=torch.uint8, device=dev)
+    i2 = torch.empty((m2,), dtype=torch.int64, device=dev) if index is not None else None
+    _ffi.call("m3_map_voxel_scatter", _ffi.ptr(points), _ffi.ptr(colors), _ffi.ptr(index), m, _ffi.ptr(ws), ws_bytes, m2,
+              _ffi.ptr(p2), _ffi.ptr(c2), _ffi.ptr(i2), st)
+    return p2, c2, i2
+
+
+def _host(a, dtype) -> np.ndarray:
+    if isinstance(a, torch.Tensor):
+        a = a.detach().cpu().numpy()
+    return np.ascontiguousarray(a, dtype=dtype)
+
+
+def save_ply(path, points, colors, binary: bool = True) -> int:
+    """PLY with the reference's vertex properties (float x y z, uchar red green blue; slam.py:395-412).  binary: one
+    structured array written in `binary_little_endian 1.0`; else the reference's ASCII lines (%.6f).  Returns M."""
+    p = _host(points, np.float32).reshape(-1, 3)
+    c = _host(colors, np.uint8).reshape(-1, 3)
+    if p.shape[0] != c.shape[0]:
+        raise ValueError(f"{p.shape[0]} points but {c.shape[0]} colours")
+    m = p.shape[0]
+    header = ("ply\nformat {} 1.0\nelement vertex {}\nproperty float x\nproperty float y\nproperty float z\n"
+              "property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n"
+              ).format("binary_little_endian" if binary else "ascii", m)
+    with open(os.fspath(path), "wb") as f:
+        f.write(header.encode("ascii"))
+        if binary:
+            body = np.empty(m, dtype=_PLY_DTYPE)
+            body["x"], body["y"], body["z"] = p[:, 0], p[:, 1], p[:, 2]
+            body["red"], body["green"], body["blue"] = c[:, 0], c[:, 1], c[:, 2]
+            body.tofile(f)
+        elif m:
+            rows = np.concatenate([p.astype(np.float64), c.astype(np.float64)], axis=1)
+            np.savetxt(f, rows, fmt="%.6f %.6f %.6f %d %d %d")
+    return m
+
+
+def _sim3_rows(poses: np.ndarray) -> np.ndarray:
+    """[F,8] (t, q xyzw, s) -> [F,12]: the first three rows of [sR | t], float64, the reference's quaternion formula
+    (liegroups/so3.py:174-205, no normalisation)."""
+    t, (x, y, z, w), s = poses[:, :3], poses[:, 3:7].T, poses[:, 7]
+    R = np.stack([1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y),
+                  2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x),
+                  2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)], axis=1).reshape(-1, 3, 3)
+    return np.concatenate([s[:, None, None] * R, t[:, :, None]], axis=2).reshape(-1, 12)
+
+
+def save_trajectory(path, timestamps: Sequence, poses, format: str = "tum") -> int:
+    """slam.py:354-381 on [F,8] pose rows.  "tum": `ts tx ty tz qx qy qz qw`; "kitti": the 12 numbers of [sR | t] row by
+    row; all %.6f.  Any other format raises ValueError (the reference writes nothing).  Returns the line count."""
+    if format not in ("tum", "kitti"):
+        raise ValueError(f"unknown trajectory format {format!r}; expected 'tum' or 'kitti'")
+    P = _host(poses, np.float64).reshape(-1, 8)
+    ts = np.asarray([float(t) for t in timestamps], dtype=np.float64)
+    if format == "tum" and ts.shape[0] != P.shape[0]:
+        raise ValueError(f"{ts.shape[0]} timestamps but {P.shape[0]} poses")
+    rows = np.concatenate([ts[:, None], P[:, :7]], axis=1) if format == "tum" else _sim3_rows(P)
+    with open(os.fspath(path), "w") as f:
+        for r in rows:
+            f.write(" ".join("%.6f" % v for v in r) + "\n")
+    return rows.shape[0]

@@ -160,6 +160,22 @@ class Keyframes:
         for row, k in zip(T_WCs.reshape(-1, 8), ids):
             self._frames[int(k)].T_WC = row.reshape(1, 8).clone()
 
+    def get_poses(self) -> torch.Tensor:
+        """frame.py:223-232: every keyframe's pose, [K,8] (the identity, [1,8], when there is no keyframe)."""
+        if not self._frames:
+            return torch.tensor([[0, 0, 0, 0, 0, 0, 1, 1]], dtype=torch.float32)
+        return torch.cat([f.T_WC.reshape(1, 8) for f in self._frames])
+
+    def get_points(self) -> torch.Tensor:
+        """frame.py:234-242: canonical pointmaps stacked, [K,N,3] (keyframes without a pointmap are skipped)."""
+        X = [f.X_canon.reshape(-1, 3) for f in self._frames if f.X_canon is not None]
+        return torch.stack(X) if X else torch.zeros((0, 0, 3), dtype=torch.float32)
+
+    def get_confidences(self) -> torch.Tensor:
+        """frame.py:244-252: average confidences stacked, [K,N,1]."""
+        C = [f.get_average_conf().reshape(-1, 1) for f in self._frames if f.C is not None]
+        return torch.stack(C) if C else torch.zeros((0, 0, 1), dtype=torch.float32)
+
     def set_intrinsics(self, K: torch.Tensor) -> None:
         self.K = K
         for f in self._frames:

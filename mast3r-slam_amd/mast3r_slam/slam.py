@@ -1,7 +1,8 @@
 """Minimal SLAM driver over the hot-path operators: the control flow of
 /root/reference/src/mlx_mast3r_slam/slam.py (:124-153 main loop, :159-214 INIT / TRACKING,
 :216-290 RELOC, :292-318 backend).  It exists to show the operator API dropping in under the loop and to
-test it end to end; dataset readers, trajectory writers and visualisation stay out of scope.
+test it end to end; dataset readers and visualisation stay out of scope.  The map and trajectory writers
+(:320-415) are save_pointcloud / save_trajectory / reconstruction over mast3r_slam/export.py.
 
 Relocalization is opt-in: SLAM(model, retrieval=db_or_True) keeps a keyframe retrieval database
 (mast3r_slam/retrieval.py) fed on INIT and on every new keyframe, and a frame that cannot be tracked is matched
@@ -17,6 +18,7 @@ from typing import Callable, Iterable, Optional
 
 import torch
 
+from . import export
 from .config import get_config
 from .frame import Keyframes, create_frame
 from .global_opt import FactorGraph
@@ -170,3 +172,28 @@ class SLAM:
             "points": torch.cat(pts) if pts else torch.empty((0, 3)),
             "keyframe_indices": [kf.frame_id for kf in self.keyframes._frames],
         }
+
+    # ------------------------------------------------------------------ slam.py:320-415
+    def reconstruction(self, c_conf_threshold: Optional[float] = 1.5, voxel_size: Optional[float] = None,
+                       return_index: bool = False):
+        """export.collect_map over the keyframes: (points [M,3] float32, colours [M,3] uint8[, index [M] int64])."""
+        return export.collect_map(self.keyframes, c_conf_threshold=c_conf_threshold, voxel_size=voxel_size,
+                                  return_index=return_index)
+
+    def save_pointcloud(self, path, c_conf_threshold: Optional[float] = 1.5, voxel_size: Optional[float] = None,
+                        binary: bool = True) -> int:
+        """:383-415 as a filtered (and optionally voxel-thinned) PLY; returns the number of vertices written."""
+        points, colors = self.reconstruction(c_conf_threshold, voxel_size)
+        return export.save_ply(path, points, colors, binary=binary)
+
+    def save_trajectory(self, path, format: str = "tum", keyframes_only: bool = False) -> int:
+        """:354-381.  Default: every processed frame at the pose it was given (results()["poses"]).  keyframes_only:
+        the keyframes' current, backend-optimised poses at their own timestamps."""
+        if keyframes_only:
+            kfs = self.keyframes._frames
+            ts = [self.timestamps[kf.frame_id] for kf in kfs]
+            poses = self.keyframes.get_poses() if kfs else torch.empty((0, 8))
+        else:
+            ts = self.timestamps
+            poses = torch.cat(self.poses) if self.poses else torch.empty((0, 8))
+        return export.save_trajectory(path, ts, poses, format=format)
