@@ -95,7 +95,8 @@ typedef struct m3_gemm_desc {
     int32_t rope_max_pos;              /* RoPE: > 0 promises that every entry of rope_pos is in [0, rope_max_pos) and rope_max_pos <= 64  */
                                        /* (a 1024-pixel side): each workgroup then builds the rope_max_pos x 16 cos / sin table once in   */
                                        /* LDS instead of eight v_sin / v_cos per lane, row and 32-column block (same values bit for bit). */
-                                       /* 0 (or > 64): computed per element.  A position outside the promise takes the last table row.    */
+                                       /* 0 (or > 64): computed per element.  A position outside the promise is clamped to the table's    */
+                                       /* first / last row (ops.rope_bound checks the promise on the host).                               */
 } m3_gemm_desc;
 int m3_gemm_ex(const m3_gemm_desc *desc, void *stream);
 /* Which kernel m3_gemm_ex dispatches a dense [M,N] problem of `groups` groups to: 256 or 192 = the 256-row ping-pong kernel

@@ -278,7 +278,8 @@ __device__ __forceinline__ void rope_load(const GemmArgs &g, RopeCoef (&cf)[NJ /
         const int axis = ((n_base + 32 * blk) >> 5) & 1;                 // 0: y, 1: x
         if (ropet) {                                                     // kernel-uniform: the workgroup's LDS table
             int p = axis ? pyx.y : pyx.x;
-            p = p < g.rope_pmax ? p : g.rope_pmax - 1;                   // (a position outside the promised range: no stray read)
+            p = p < g.rope_pmax ? p : g.rope_pmax - 1;                   // (a position outside the promised range, above or
+            p = p > 0 ? p : 0;                                           //  below: no stray LDS read - one v_med3_i32)
             const float *row = ropet + p * 32 + fi;
             cf[blk].c = *reinterpret_cast<const float4 *>(row);
             cf[blk].s = *reinterpret_cast<const float4 *>(row + 16);

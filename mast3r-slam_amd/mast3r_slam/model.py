@@ -242,6 +242,7 @@ class Mast3rFull:
         if not torch.cuda.is_available():
             raise RuntimeError("Mast3rFull needs a ROCm device; there is no CPU path")
         self.cfg = dict(cfg or FULL_CFG)
+        self.embed_dim = int(self.cfg["enc_dim"])                                 # 1024 for every shipped configuration
         self.device = torch.device(device)
         self.resolution = resolution
         self.precision = precision
@@ -257,6 +258,11 @@ class Mast3rFull:
         # 7-10 % of the fp16 trunk's error budget (tools/experiments/emul_lnfold.py: rounding the raw stream instead of the
         # normalised values; the bf16 trunk cannot afford it and keeps the kernels).
         self.ln_fold = self.tdt == torch.float16 and os.environ.get("M3_LN_FOLD", "1") != "0"
+        # ... and only for stream widths whose statistics have a canonical sum tree (m3_ln_slot_count > 0: multiples of 192 or 256
+        # with at most four top nodes - 768, 1024; not e.g. 1280 or 1536): other widths keep the LayerNorm kernels
+        if self.ln_fold:
+            L = ops._ffi.lib()
+            self.ln_fold = all(int(L.m3_ln_slot_count(2, int(self.cfg[k]), g)) > 0 for k, g in (("enc_dim", 1), ("dec_dim", 2)))
         self.host_weights = weights if weights is not None else init_random_weights(self.cfg, seed)
         self._prepare(self.host_weights)
         self._rope_cache = {}

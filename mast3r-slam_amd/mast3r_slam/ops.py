@@ -101,9 +101,18 @@ _ROPE_BOUND = WeakTensorKeyDictionary()       # keyed by tensor identity, droppe
 def rope_bound(pos_yx, bound: int):
     """Promise that every entry of the int32 position tensor `pos_yx` is in [0, bound): the RoPE epilogues given this tensor then
     build their cos / sin table once per workgroup in LDS (m3_gemm_desc.rope_max_pos; same values, ~12 us less per 16384-row
-    projection).  Returns the tensor.  Without the promise (or bound > 64) the coefficients are computed per element."""
-    if pos_yx.dtype != torch.int32 or bound < 1:
+    projection).  Returns the tensor.  Without the promise (or bound > 64) the coefficients are computed per element.
+    The promise is checked here, once (one device-to-host read: call it outside graph capture, as the model does when it builds
+    a grid's positions): a tensor that breaks it raises ValueError and is not recorded.  It covers the tensor's contents at
+    this moment - positions are written once and not modified afterwards."""
+    if not isinstance(pos_yx, torch.Tensor) or pos_yx.dtype != torch.int32 or bound < 1:
         raise ValueError("rope_bound: int32 positions and a positive bound")
+    if pos_yx.numel():
+        lo, hi = int(pos_yx.min()), int(pos_yx.max())
+        if lo < 0:
+            raise ValueError(f"rope_bound: negative position {lo}")
+        if hi >= bound:
+            raise ValueError(f"rope_bound: position {hi} is outside the promised bound [0, {int(bound)})")
     _ROPE_BOUND[pos_yx] = int(bound)
     return pos_yx
 

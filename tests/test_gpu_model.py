@@ -404,6 +404,29 @@ def test_two_view_network_vs_cpu_oracle(tiny, dev):
     assert torch.equal(s1["pts3d"][0], o1["pts3d"][1]) and torch.equal(s2["desc"][0], o2["desc"][1])
 
 
+def test_width_without_fold_statistics_keeps_the_layernorm_kernels(dev):
+    """The LayerNorm fold needs a canonical sum tree for the stream width (m3_ln_slot_count > 0: 768, 1024).  An fp16 model of
+    another width (encoder 1280) must build with the fold off - for BOTH streams, the decoder's 768 included - and run the
+    LayerNorm kernels: one forward against the fp32 oracle, the tolerances of test_two_view_network_vs_cpu_oracle."""
+    from mast3r_slam import _ffi
+    assert int(_ffi.lib().m3_ln_slot_count(2, 1280, 1)) == 0 and int(_ffi.lib().m3_ln_slot_count(2, 1536, 2)) == 0
+    assert int(_ffi.lib().m3_ln_slot_count(2, 768, 2)) > 0
+    cfg = dict(M.TINY_CFG, enc_dim=1280, enc_heads=20)
+    w = M.init_random_weights(cfg, seed=3)
+    net = M.Mast3rFull(weights=w, cfg=cfg, device=dev, precision="fp16")
+    assert net.ln_fold is False and not any(k.endswith(".fw") for k in net.P)
+    assert M.Mast3rFull(weights=M.init_random_weights(M.TINY_CFG, seed=1), cfg=M.TINY_CFG, device=dev, precision="fp16").ln_fold is True
+    h, wd = 128, 256
+    im1, im2 = synthetic.textured_image(h, wd, 0)[None], synthetic.textured_image(h, wd, 1)[None]
+    o1, o2 = net.reconstruct_batch(im1, im2)
+    r1, r2 = OM.reconstruct(w, torch.from_numpy(im1), torch.from_numpy(im2), cfg)
+    for o, r in ((o1, r1), (o2, r2)):
+        assert _rel(o["pts3d"], r["pts3d"]) < 1e-3
+        assert _rel(o["conf"], r["conf"]) < 1e-4
+        assert _rel(o["desc"], r["desc"]) < 6e-3
+        assert _rel(o["desc_conf"], r["desc_conf"]) < 6e-3
+
+
 def test_graphed_reconstruct_equals_eager(tiny, dev):
     """The hipGraph-replayed network (fixed shape, static buffers) returns the same bits as eager launches,
     call after call with different images."""
