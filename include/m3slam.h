@@ -417,6 +417,29 @@ int m3_map_voxel_scatter(const float *points, const uint8_t *colors, const int64
                          int64_t ws_bytes, int64_t M2, float *points_out, uint8_t *colors_out, int64_t *index_out,
                          void *stream);
 
+/* -------------------------------------------------------------- preprocessing */
+
+/* Frame preprocessing in front of m3_patchify16_dt (mast3r_utils.py:132-207 resize_img).  Host side:
+ * mast3r_slam/preprocess.py, which builds the tables.
+ *
+ * src uint8 [B,Hs,Ws,3] interleaved RGB is resampled to [Hr,Wr] with the 8-bit arithmetic of Pillow's Image.resize and
+ * the box [crop_y0, crop_y0 + Hc) x [crop_x0, crop_x0 + Wc) of the result is written: dst uint8 [B,Hc,Wc,3] and, when
+ * img is not NULL, img float [B,Hc,Wc,3] = (v / 255.0f - 0.5f) / 0.5f (three separately rounded fp32 operations).
+ * Per axis and output index o the host gives bounds[o] = (first source index, tap count n <= ksize) and n int32
+ * coefficients in 2^22 fixed point; a pass is out = clamp((2^21 + sum_t src[first + t] * k[t]) >> 22, 0, 255) in int32
+ * (the host guarantees 255 * sum|k| + 2^21 < 2^31 and |k| < 2^23: products are formed by the 24-bit multiplier).  The horizontal pass runs first and its result is rounded to uint8
+ * before the vertical pass.  Wr == Ws / Hr == Hs: no pass on that axis, its tables are ignored (may be NULL).
+ *   bounds_h int32 [Wr,2], coef_h int32 [ksize_h,Wr] (TAP-major: 64 neighbouring columns read 256 contiguous bytes
+ *   per tap); bounds_v int32 [Hr,2], coef_v int32 [Hr,ksize_v] (a wave owns one output row: uniform reads).
+ * One launch, no workspace, no atomics; nothing depends on the image content.  A workgroup stages the source rows of a
+ * 64-column x TH-row output tile through LDS; TH (16 ... 1) and the staging depth follow from the sizes alone, and a
+ * problem whose single-row tile does not fit 64 KiB of LDS is M3_ERR_UNSUPPORTED (a source edge of 8192 fits for every
+ * target the host produces).  Table entries are clamped before they address anything.  src, dst and img 16-byte
+ * aligned; B <= 65535; sizes <= 65536. */
+int m3_resize_crop_u8(const uint8_t *src, const int32_t *bounds_h, const int32_t *coef_h, int ksize_h,
+                      const int32_t *bounds_v, const int32_t *coef_v, int ksize_v, uint8_t *dst, float *img, int B, int Hs,
+                      int Ws, int Hr, int Wr, int crop_x0, int crop_y0, int Hc, int Wc, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

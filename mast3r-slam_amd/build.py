@@ -32,6 +32,8 @@ PER_FILE = {
     # float64-fold-bound kernels nothing, so it stays off for both Gauss-Newton sources
     "tracking.hip": ["-fno-slp-vectorize"],
     "gn_rays.hip": ["-fno-slp-vectorize"],
+    # the float image is (v / 255 - 0.5) / 0.5 with three roundings, bit-exact against numpy
+    "preprocess.hip": ["-ffp-contract=off"],
 }
 
 

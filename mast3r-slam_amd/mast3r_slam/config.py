@@ -11,7 +11,7 @@ from typing import Any
 
 DEFAULT_CONFIG: dict[str, Any] = {
     "use_calib": False,
-    "dataset": {"img_size": 512, "img_downsample": 1},
+    "dataset": {"img_size": 512, "img_downsample": 1, "subsample": 1, "reverse": False},
     "matching": {
         "use_simple": True,
         "max_iter": 10,

@@ -12,7 +12,8 @@ Differences, on purpose:
     identity matches / zeros (:556-569, :611-616).
   * cached `frame.feat` is reused; the reference re-encodes both images on every call (:345-355).
   * *_batch variants take P pairs at once (the data-parallel unit that shards across GPUs).
-resize_img (:132-207) is the same host-side PIL preprocessing.  The retrieval database (load_retriever :83-114,
+resize_img (:132-207) is the same host-side PIL preprocessing; resize_img_device (mast3r_slam/preprocess.py) computes
+the same bytes on the device.  The retrieval database (load_retriever :83-114,
 RetrievalDatabase :640-795, simple retrieval only) lives in mast3r_slam/retrieval.py and is re-exported here, as are
 the map and trajectory writers of mast3r_slam/export.py (collect_map, save_ply, save_trajectory; slam.py:320-415).
 """
@@ -28,12 +29,14 @@ from .model import Mast3rFull
 from . import matching
 from .retrieval import RetrievalDatabase, load_retriever
 from .export import collect_map, save_ply, save_trajectory
+from .preprocess import adjust_intrinsics, resample_tables, resize_geometry, resize_img_device
 
 __all__ = [
     "load_mast3r", "resize_img", "frame_to_numpy", "downsample", "mast3r_inference_mono", "mast3r_asymmetric_inference",
     "mast3r_symmetric_inference", "mast3r_match_asymmetric", "mast3r_match_symmetric",
     "mast3r_decode_symmetric_batch", "mast3r_match_asymmetric_batch", "load_retriever", "RetrievalDatabase",
     "collect_map", "save_ply", "save_trajectory",
+    "resize_img_device", "resize_geometry", "resample_tables", "adjust_intrinsics",
 ]
 
 

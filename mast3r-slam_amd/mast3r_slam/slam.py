@@ -1,7 +1,8 @@
 """Minimal SLAM driver over the hot-path operators: the control flow of
 /root/reference/src/mlx_mast3r_slam/slam.py (:124-153 main loop, :159-214 INIT / TRACKING,
 :216-290 RELOC, :292-318 backend).  It exists to show the operator API dropping in under the loop and to
-test it end to end; dataset readers and visualisation stay out of scope.  The map and trajectory writers
+test it end to end; visualisation stays out of scope.  run_dataset reads a dataset (mast3r_slam/dataloader.py) and
+resizes its frames on the device (mast3r_slam/preprocess.py).  The map and trajectory writers
 (:320-415) are save_pointcloud / save_trajectory / reconstruction over mast3r_slam/export.py.
 
 Relocalization is opt-in: SLAM(model, retrieval=db_or_True) keeps a keyframe retrieval database
@@ -20,9 +21,11 @@ import torch
 
 from . import export
 from .config import get_config
+from .dataloader import Dataset, load_dataset
 from .frame import Keyframes, create_frame
 from .global_opt import FactorGraph
 from .mast3r_utils import mast3r_inference_mono, mast3r_match_asymmetric, mast3r_match_symmetric
+from .preprocess import adjust_intrinsics, resize_geometry
 from .retrieval import RetrievalDatabase, load_retriever
 from .tracker import FrameTracker, sim3_act
 
@@ -36,6 +39,7 @@ class SLAM:
         self.keyframes = Keyframes()
         if K is not None:
             self.keyframes.set_intrinsics(K)
+        self._K_raw = K                               # as given: run_dataset adjusts it to the preprocessed frames
         self.tracker = FrameTracker(model, self.keyframes)
         self.factor_graph = FactorGraph(model, self.keyframes, K if self.config.get("use_calib") else None)
         self.mode = INIT
@@ -72,6 +76,19 @@ class SLAM:
                 callback(frame, self.keyframes)
             self._run_backend()
         return self.results()
+
+    def run_dataset(self, dataset_or_path, dataset_type: Optional[str] = None, callback: Optional[Callable] = None) -> dict:
+        """slam.py:93-96 of the reference: load a dataset (a path, or a Dataset), resize and crop its frames on the
+        device to config["dataset"]["img_size"], move the intrinsics the driver was given to the preprocessed image,
+        and run."""
+        ds = dataset_or_path if isinstance(dataset_or_path, Dataset) else load_dataset(dataset_or_path, dataset_type)
+        if self._K_raw is not None and len(ds):
+            h, w = ds[0][1].shape[:2]
+            K = adjust_intrinsics(self._K_raw, resize_geometry(h, w, self.config["dataset"]["img_size"])[3])
+            self.keyframes.set_intrinsics(K)
+            if self.factor_graph.K is not None:
+                self.factor_graph.K = K
+        return self.run(ds.frames(self.model.device, size=self.config["dataset"]["img_size"]), callback)
 
     def _mono(self, frame) -> None:
         X, C, feat, pos = mast3r_inference_mono(self.model, frame)
