@@ -417,6 +417,40 @@ int m3_map_voxel_scatter(const float *points, const uint8_t *colors, const int64
                          int64_t ws_bytes, int64_t M2, float *points_out, uint8_t *colors_out, int64_t *index_out,
                          void *stream);
 
+/* ------------------------------------------------------------- map rendering */
+
+/* Headless renderer of the keyframe map.  Host side: mast3r_slam/render.py.
+ *
+ * The map arrives as for m3_map_export_*: device tables X / C / img with one entry per keyframe, poses [K,8], Nk [K],
+ * layout M3_MAP_IMG_*; K = 0 draws the background (the tables may then be NULL).  The camera is view_pose, 8 floats
+ * (t, q xyzw, s) of T_WC in DEVICE memory, read by the kernel, and a pinhole (fx, fy, cx, cy) of an Hv x Wv image.
+ *
+ *   candidate(k, n)  <=>  the export rule: C[k][n] / (float)Nk[k] > thresh (use_thresh = 0 skips it) and the world
+ *                         point p = s R X + t finite (fp32, as the exporter computes it)
+ *   camera point     c = (R_v^T (p - t_v)) * (1 / s_v): the nine entries of R_v^T (quaternion formula, no
+ *                         normalisation) and 1 / s_v are formed in float64 per workgroup and rounded to fp32; then
+ *                         d = p - t_v, c.x = ((r00 d.x + r01 d.y) + r02 d.z) * inv_s, ... separately rounded
+ *   kept             <=>  near < c.z < far (strict, NaN fails)
+ *   pixel            px = floorf((fx * (c.x / c.z) + cx) + 0.5f), py likewise: integer coordinates are pixel centres
+ *   footprint        the point_size x point_size square centred on (px, py), every pixel of it inside the image
+ *   winner per pixel the smallest key (bits of c.z as uint32) << 32 | (k * N + n): nearest, ties to the smaller index
+ *   outputs          rgb uint8 [Hv,Wv,3] (the winner's colour by the export's colour rule, else bg), depth float
+ *                    [Hv,Wv] (c.z of the winner, else +inf), index int64 [Hv,Wv] (k * N + n, else -1; may be NULL)
+ *
+ * m3_render_launches(K) launches are queued (3: clear, splat, resolve; 2 for K = 0), whatever K is; there is no host
+ * synchronisation and no allocation, so the call can be captured into a graph.  The only atomics are 64-bit unsigned
+ * minima on the key buffer: the bytes of every output are the same on every call.
+ * ws: m3_render_ws_bytes(Hv, Wv) = Hv * Wv * 8 bytes (0 = unsupported: 1 <= Hv, Wv <= 16384), 16-byte aligned, contents
+ * ignored on entry.  K * N < 2^31 as for the export; point_size 1, 3, 5 or 7; fx, fy > 0; 0 <= near < far (far may be
+ * +inf); bg_* in 0 ... 255. */
+int64_t m3_render_ws_bytes(int Hv, int Wv);
+int m3_render_launches(int K);
+int m3_render_map(const float *const *X, const float *const *C, const void *const *img, const float *poses,
+                  const int32_t *Nk, int K, int N, int use_thresh, float thresh, int layout, const float *view_pose,
+                  float fx, float fy, float cx, float cy, int Hv, int Wv, float near, float far, int point_size, int bg_r,
+                  int bg_g, int bg_b, void *ws, int64_t ws_bytes, uint8_t *rgb, float *depth, int64_t *index,
+                  void *stream);
+
 /* -------------------------------------------------------------- preprocessing */
 
 /* Frame preprocessing in front of m3_patchify16_dt (mast3r_utils.py:132-207 resize_img).  Host side:

@@ -1,0 +1,206 @@
+// Headless map renderer (mast3r_slam/render.py): the keyframe map drawn into an image from any pinhole camera, with a
+// z-buffer of 64-bit keys (bits of the camera depth << 32 | source index).  clear -> splat -> resolve; the splat's only
+// atomics are 64-bit integer minima, which commute, so two calls give identical bytes.  Nothing here waits for the
+// host: the view pose is read from device memory and the call can be captured into a graph.
+//
+// Compiled with -ffp-contract=off: the camera transform and the projection are separately rounded fp32 operations
+// (tests/render_twin.py restates them).  The world point is the exporter's: map_points.h is included with contraction
+// on, as map_export.hip compiles it.
+#include "common.h"
+#pragma clang fp contract(fast)
+#include "sim3_dev.h"
+#include "map_points.h"
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr unsigned long long kNoKey = ~0ull;  // no source: a depth with these bits is a NaN and never a candidate
+constexpr int kViewWords = 13;                // rows of R_v^T (9), t_v (3), 1 / s_v
+
+// Inverse of the view pose (t, q xyzw, s), formed in float64 and rounded to fp32.  The rotation is the quaternion
+// formula of liegroups/so3.py without normalisation, as export.save_trajectory writes it.
+__device__ __forceinline__ void view_inverse(const float *__restrict__ T, float *__restrict__ o) {
+    const double x = T[3], y = T[4], z = T[5], w = T[6];
+    o[0] = (float)(1.0 - 2.0 * (y * y + z * z)); o[1] = (float)(2.0 * (x * y + w * z)); o[2] = (float)(2.0 * (x * z - w * y));
+    o[3] = (float)(2.0 * (x * y - w * z)); o[4] = (float)(1.0 - 2.0 * (x * x + z * z)); o[5] = (float)(2.0 * (y * z + w * x));
+    o[6] = (float)(2.0 * (x * z + w * y)); o[7] = (float)(2.0 * (y * z - w * x)); o[8] = (float)(1.0 - 2.0 * (x * x + y * y));
+    o[9] = T[0]; o[10] = T[1]; o[11] = T[2];
+    o[12] = (float)(1.0 / (double)T[7]);
+}
+
+// Key buffer to all ones, 16-byte stores.
+__global__ void __launch_bounds__(kThreads) k_render_clear(unsigned long long *__restrict__ keys, int64_t P) {
+    const int64_t i = ((int64_t)blockIdx.x * kThreads + threadIdx.x) * 2;
+    if (i + 2 <= P) *(ulonglong2 *)(keys + i) = ulonglong2{kNoKey, kNoKey};
+    else if (i < P) keys[i] = kNoKey;
+}
+
+// Grid as k_export_count.  A thread owns 4 consecutive points; X is only read when one of them passed the confidence
+// test.  Per footprint pixel: a plain load of the current key, and the atomic minimum only when the new key is smaller
+// (keys only ever decrease, so a stale value read here costs an atomic and never a result).
+template <int PS>
+__global__ void __launch_bounds__(kThreads) k_render_splat(const float *const *__restrict__ X,
+                                                            const float *const *__restrict__ C,
+                                                            const float *__restrict__ poses, const int32_t *__restrict__ Nk,
+                                                            int N, int tiles, int use_thresh, float thresh,
+                                                            const float *__restrict__ view, float fx, float fy, float cx,
+                                                            float cy, int Hv, int Wv, float near, float far,
+                                                            unsigned long long *keys) {
+    __shared__ float sv[kViewWords];
+    if (threadIdx.x == 0) view_inverse(view, sv);
+    Tile t = tile_of(N, tiles);
+    const float *Xk = X[t.k], *Ck = C[t.k];
+    t.vec = t.n0 + kPts <= N && N % 4 == 0 && aligned16(Xk) && aligned16(Ck);
+    float avg[kPts];
+    unsigned keep = conf_pass(Ck, t, N, (float)Nk[t.k], use_thresh, thresh, avg);
+    __syncthreads();
+    if (!keep) return;
+    V3<float> p[kPts];
+    keep = world_points(Xk, t, load_pose<float>(poses + 8 * t.k), keep, p);
+    constexpr int R = PS / 2;
+    const float inv_s = sv[12];
+#pragma unroll
+    for (int j = 0; j < kPts; ++j) {
+        if (!((keep >> j) & 1u)) continue;
+        const float dx = p[j].x - sv[9], dy = p[j].y - sv[10], dz = p[j].z - sv[11];
+        const float x = ((sv[0] * dx + sv[1] * dy) + sv[2] * dz) * inv_s;
+        const float y = ((sv[3] * dx + sv[4] * dy) + sv[5] * dz) * inv_s;
+        const float z = ((sv[6] * dx + sv[7] * dy) + sv[8] * dz) * inv_s;
+        if (!(z > near && z < far)) continue;                                   // NaN fails; near >= 0: z is positive
+        const float fu = floorf((fx * (x / z) + cx) + 0.5f), fv = floorf((fy * (y / z) + cy) + 0.5f);
+        if (!(fu >= (float)-R && fu < (float)(Wv + R) && fv >= (float)-R && fv < (float)(Hv + R))) continue;
+        const int px = (int)fu, py = (int)fv;
+        const unsigned long long key = ((unsigned long long)__float_as_uint(z) << 32) | (unsigned)(t.k * N + t.n0 + j);
+#pragma unroll
+        for (int oy = -R; oy <= R; ++oy) {
+            const int yy = py + oy;
+            if (yy < 0 || yy >= Hv) continue;
+#pragma unroll
+            for (int ox = -R; ox <= R; ++ox) {
+                const int xx = px + ox;
+                if (xx < 0 || xx >= Wv) continue;
+                unsigned long long *slot = keys + ((int64_t)yy * Wv + xx);
+                if (key < __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+                    __hip_atomic_fetch_min(slot, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+    }
+}
+
+// A thread owns 4 consecutive output pixels.  LAYOUT as k_export_scatter.
+template <int LAYOUT>
+__global__ void __launch_bounds__(kThreads) k_render_resolve(const unsigned long long *__restrict__ keys,
+                                                              const void *const *__restrict__ img, int N, int64_t P,
+                                                              unsigned bg, unsigned char *__restrict__ rgb,
+                                                              float *__restrict__ depth, int64_t *__restrict__ index) {
+    const int64_t i0 = ((int64_t)blockIdx.x * kThreads + threadIdx.x) * 4;
+    if (i0 >= P) return;
+    const bool vec = i0 + 4 <= P && ((uintptr_t)rgb & 3) == 0 && aligned16(depth) && aligned16(index);
+    unsigned long long key[4];
+    if (vec) {
+        const ulonglong2 a = *(const ulonglong2 *)(keys + i0), b = *(const ulonglong2 *)(keys + i0 + 2);
+        key[0] = a.x; key[1] = a.y; key[2] = b.x; key[3] = b.y;
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) key[j] = i0 + j < P ? keys[i0 + j] : kNoKey;
+    }
+    unsigned char c[4][3];
+    float z[4];
+    int64_t src[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        if (key[j] == kNoKey) {
+            c[j][0] = (unsigned char)bg; c[j][1] = (unsigned char)(bg >> 8); c[j][2] = (unsigned char)(bg >> 16);
+            z[j] = INFINITY;
+            src[j] = -1;
+            continue;
+        }
+        const unsigned s = (unsigned)key[j];
+        const unsigned k = s / (unsigned)N, n = s - k * (unsigned)N;
+        z[j] = __uint_as_float((unsigned)(key[j] >> 32));
+        src[j] = (int64_t)s;
+        if constexpr (LAYOUT == 0) {
+            const float *I = (const float *)img[k];
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) c[j][ch] = to_u8(I[(size_t)ch * N + n]);
+        } else {
+            const unsigned char *I = (const unsigned char *)img[k];
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) c[j][ch] = I[(size_t)3 * n + ch];
+        }
+    }
+    if (vec) {
+        unsigned w[3] = {0u, 0u, 0u};
+#pragma unroll
+        for (int b = 0; b < 12; ++b) w[b / 4] |= (unsigned)c[b / 3][b % 3] << (8 * (b % 4));
+        unsigned *dst = (unsigned *)(rgb + 3 * i0);
+        dst[0] = w[0]; dst[1] = w[1]; dst[2] = w[2];
+        *(float4 *)(depth + i0) = float4{z[0], z[1], z[2], z[3]};
+        if (index) {
+            *(longlong2 *)(index + i0) = longlong2{src[0], src[1]};
+            *(longlong2 *)(index + i0 + 2) = longlong2{src[2], src[3]};
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (i0 + j >= P) continue;
+            rgb[3 * (i0 + j)] = c[j][0]; rgb[3 * (i0 + j) + 1] = c[j][1]; rgb[3 * (i0 + j) + 2] = c[j][2];
+            depth[i0 + j] = z[j];
+            if (index) index[i0 + j] = src[j];
+        }
+    }
+}
+
+inline bool view_ok(int Hv, int Wv) { return Hv >= 1 && Wv >= 1 && Hv <= 16384 && Wv <= 16384; }
+
+inline bool map_ok(int K, int N) {
+    return K == 0 || (K >= 1 && N >= 1 && (int64_t)K * N <= 0x7fffffff && (int64_t)K * m3_cdiv(N, kTile) <= (1 << 30));
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t m3_render_ws_bytes(int Hv, int Wv) { return view_ok(Hv, Wv) ? (int64_t)Hv * Wv * 8 : 0; }
+
+int m3_render_launches(int K) { return K > 0 ? 3 : 2; }
+
+int m3_render_map(const float *const *X, const float *const *C, const void *const *img, const float *poses,
+                  const int32_t *Nk, int K, int N, int use_thresh, float thresh, int layout, const float *view_pose,
+                  float fx, float fy, float cx, float cy, int Hv, int Wv, float near, float far, int point_size, int bg_r,
+                  int bg_g, int bg_b, void *ws, int64_t ws_bytes, uint8_t *rgb, float *depth, int64_t *index,
+                  void *stream) {
+    M3_REQUIRE(view_ok(Hv, Wv) && map_ok(K, N) && ws && rgb && depth);
+    M3_REQUIRE(K == 0 || (X && C && img && poses && Nk && view_pose));
+    M3_REQUIRE((use_thresh == 0 || use_thresh == 1) && ((uintptr_t)ws & 15) == 0 && ws_bytes >= m3_render_ws_bytes(Hv, Wv));
+    M3_REQUIRE(layout == M3_MAP_IMG_F32_CHW || layout == M3_MAP_IMG_U8_HWC);
+    M3_REQUIRE(point_size == 1 || point_size == 3 || point_size == 5 || point_size == 7);
+    M3_REQUIRE(fx > 0.f && fy > 0.f && fx < INFINITY && fy < INFINITY && cx == cx && cy == cy && near >= 0.f && near < far);
+    M3_REQUIRE(((bg_r | bg_g | bg_b) & ~255) == 0);
+    hipStream_t st = (hipStream_t)stream;
+    unsigned long long *keys = (unsigned long long *)ws;
+    const int64_t P = (int64_t)Hv * Wv;
+    hipLaunchKernelGGL(k_render_clear, dim3(m3_cdiv(P, 2 * kThreads)), dim3(kThreads), 0, st, keys, P);
+    if (K > 0) {
+        const int tiles = m3_cdiv(N, kTile);
+        const dim3 grid(K * tiles), block(kThreads);
+#define M3_SPLAT(PS)                                                                                                    \
+    hipLaunchKernelGGL(k_render_splat<PS>, grid, block, 0, st, X, C, poses, Nk, N, tiles, use_thresh, thresh, view_pose, \
+                       fx, fy, cx, cy, Hv, Wv, near, far, keys)
+        if (point_size == 1) M3_SPLAT(1);
+        else if (point_size == 3) M3_SPLAT(3);
+        else if (point_size == 5) M3_SPLAT(5);
+        else M3_SPLAT(7);
+#undef M3_SPLAT
+    }
+    const unsigned bg = (unsigned)bg_r | ((unsigned)bg_g << 8) | ((unsigned)bg_b << 16);
+    const dim3 rgrid(m3_cdiv(P, 4 * kThreads));
+    if (layout == M3_MAP_IMG_F32_CHW)
+        hipLaunchKernelGGL(k_render_resolve<0>, rgrid, dim3(kThreads), 0, st, keys, img, K > 0 ? N : 1, P, bg, rgb, depth, index);
+    else
+        hipLaunchKernelGGL(k_render_resolve<1>, rgrid, dim3(kThreads), 0, st, keys, img, K > 0 ? N : 1, P, bg, rgb, depth, index);
+    M3_CHECK_LAUNCH("m3_render_map");
+    return M3_OK;
+}
+
+}  // extern "C"

@@ -56,19 +56,19 @@ def _image(f, n: int):
     return layout, img
 
 
-def collect_map(keyframes, c_conf_threshold: Optional[float] = 1.5, voxel_size: Optional[float] = None,
-                return_index: bool = False):
-    """World points float32 [M,3], colours uint8 [M,3] and (return_index) source indices int64 [M] of `keyframes`
-    (a Keyframes or a sequence of Frame; frames without a pointmap are skipped), as device tensors.
+class _MapTables:
+    """Device tables of per-keyframe pointers for csrc/map_export.hip and csrc/render.hip: table int64 [3,K] (X, C, image),
+    nk int32 [K], poses float32 [K,8].  `hold` keeps the contiguous tensors alive until the launches are queued."""
+    __slots__ = ("k", "n", "layout", "device", "table", "nk", "poses", "hold", "frames")
 
-    c_conf_threshold None keeps every finite point.  voxel_size > 0 keeps one point per occupied voxel
-    floor(p / voxel_size): the one with the largest average confidence, ties to the smaller source index; ValueError
-    when a voxel coordinate reaches 2^20 (voxel_size too small for the extent of the map)."""
+
+def _map_tables(keyframes) -> Optional[_MapTables]:
+    """Tables of `keyframes` (a Keyframes or a sequence of Frame; frames without a pointmap are skipped), None when no
+    frame has a pointmap.  ValueError for mixed layouts / mismatched sizes or a map beyond 2^31 - 1 points, RuntimeError
+    for CPU tensors."""
     frames = [f for f in (keyframes._frames if hasattr(keyframes, "_frames") else list(keyframes)) if f.X_canon is not None]
-    if voxel_size is not None and not float(voxel_size) > 0.0:
-        raise ValueError(f"voxel_size must be positive, got {voxel_size}")
     if not frames:
-        return _empty("cuda" if torch.cuda.is_available() else "cpu", return_index)
+        return None
     n = frames[0].X_canon.reshape(-1, 3).shape[0]
     layouts, hold = set(), []
     for f in frames:
@@ -82,20 +82,38 @@ def collect_map(keyframes, c_conf_threshold: Optional[float] = 1.5, voxel_size: 
         hold.append((X, f.C.reshape(-1), img))
     if len(layouts) != 1:
         raise ValueError("keyframes mix float32 [3,H,W] and uint8 [H,W,3] images")
-    layout = layouts.pop()
-    dev = frames[0].X_canon.device
+    m = _MapTables()
+    m.frames, m.n, m.layout = frames, n, layouts.pop()
+    m.device = dev = frames[0].X_canon.device
     # contiguous device tensors, kept alive until the launches are queued (the kernel takes scalar loads for a keyframe
     # whose arrays are not 16-byte aligned)
-    hold = [(_ffi.check(X, torch.float32, "X_canon"), _ffi.check(C, torch.float32, "C"),
-             _ffi.check(img, (torch.float32, torch.uint8), "img")) for X, C, img in hold]
-    k = len(hold)
+    m.hold = [(_ffi.check(X, torch.float32, "X_canon"), _ffi.check(C, torch.float32, "C"),
+               _ffi.check(img, (torch.float32, torch.uint8), "img")) for X, C, img in hold]
+    m.k = len(m.hold)
+    if int(_ffi.lib().m3_map_export_ws_bytes(m.k, n)) <= 0:
+        raise ValueError(f"map of {m.k} x {n} points is too large for one export (limit 2^31 - 1 points)")
+    m.table = torch.tensor([[t.data_ptr() for t in col] for col in zip(*m.hold)], dtype=torch.int64).to(dev)   # [3,K]
+    m.nk = torch.tensor([int(f.N) for f in frames], dtype=torch.int32).to(dev)
+    m.poses = torch.cat([_ffi.check(f.T_WC.reshape(1, 8), torch.float32, "T_WC") for f in frames])
+    return m
+
+
+def collect_map(keyframes, c_conf_threshold: Optional[float] = 1.5, voxel_size: Optional[float] = None,
+                return_index: bool = False):
+    """World points float32 [M,3], colours uint8 [M,3] and (return_index) source indices int64 [M] of `keyframes`
+    (a Keyframes or a sequence of Frame; frames without a pointmap are skipped), as device tensors.
+
+    c_conf_threshold None keeps every finite point.  voxel_size > 0 keeps one point per occupied voxel
+    floor(p / voxel_size): the one with the largest average confidence, ties to the smaller source index; ValueError
+    when a voxel coordinate reaches 2^20 (voxel_size too small for the extent of the map)."""
+    if voxel_size is not None and not float(voxel_size) > 0.0:
+        raise ValueError(f"voxel_size must be positive, got {voxel_size}")
+    m_ = _map_tables(keyframes)
+    if m_ is None:
+        return _empty("cuda" if torch.cuda.is_available() else "cpu", return_index)
+    k, n, layout, dev, table, nk, poses = m_.k, m_.n, m_.layout, m_.device, m_.table, m_.nk, m_.poses
     L = _ffi.lib()
     ws_bytes = int(L.m3_map_export_ws_bytes(k, n))
-    if ws_bytes <= 0:
-        raise ValueError(f"map of {k} x {n} points is too large for one export (limit 2^31 - 1 points)")
-    table = torch.tensor([[t.data_ptr() for t in col] for col in zip(*hold)], dtype=torch.int64).to(dev)   # [3,K]
-    nk = torch.tensor([int(f.N) for f in frames], dtype=torch.int32).to(dev)
-    poses = torch.cat([_ffi.check(f.T_WC.reshape(1, 8), torch.float32, "T_WC") for f in frames])
     ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
     use, thr = (0, 0.0) if c_conf_threshold is None else (1, float(c_conf_threshold))
     st = _ffi.stream_ptr()

@@ -1,0 +1,264 @@
+"""Headless map renderer: colour, depth and index views of the keyframe map, drawn on the device (csrc/render.hip).
+
+The reference shows its map in a desktop GUI (thirdparty/in3d) fed by the `callback` of SLAM.run; an MI355X has no
+display.  render_map draws the map as it stands on the device into an image from any pinhole camera:
+
+    candidate(k, n)  <=>  export.collect_map's rule: C[k][n] / N_k > c_conf_threshold (None: no test), world point finite
+    camera point     c = R_v^T (p - t_v) / s_v          (inverse of the view pose formed in float64, rounded to fp32)
+    kept             <=>  near < c.z < far               (strict)
+    pixel            floor(fx * c.x / c.z + cx + 0.5), floor(fy * c.y / c.z + cy + 0.5): integers are pixel centres
+    footprint        point_size x point_size pixels around it
+    winner           the nearest candidate per pixel, equal depths go to the smaller source index k * N + n
+
+One call queues three launches whatever the number of keyframes, reads nothing back and allocates nothing when `out`
+and `workspace` are given; the view pose is read on the device, so a tracked pose can be used as it is and the call
+can be captured into a graph.  Two calls give identical bytes.  CPU tensors raise RuntimeError: there is no CPU path.
+"""
+from __future__ import annotations
+
+import math
+import os
+from typing import Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import _ffi
+from .export import _MapTables, _map_tables
+
+__all__ = ["render_map", "default_intrinsics", "look_at", "behind", "depth_to_rgb", "save_image", "ViewRecorder"]
+
+POINT_SIZES = (1, 3, 5, 7)
+
+
+def default_intrinsics(size: Sequence[int], fov_deg: float = 60.0):
+    """(fx, fy, cx, cy) of a pinhole with square pixels and a horizontal field of view of `fov_deg` for size = (H, W);
+    the principal point is the image centre in pixel-centre coordinates."""
+    h, w = int(size[0]), int(size[1])
+    if h <= 0 or w <= 0:
+        raise ValueError(f"size must be positive, got {tuple(size)}")
+    if not 0.0 < float(fov_deg) < 180.0:
+        raise ValueError(f"fov_deg must lie in (0, 180), got {fov_deg}")
+    f = 0.5 * w / math.tan(math.radians(float(fov_deg)) / 2.0)
+    return (f, f, (w - 1) / 2.0, (h - 1) / 2.0)
+
+
+def look_at(eye, target, up=(0.0, -1.0, 0.0)) -> torch.Tensor:
+    """[1,8] float32 pose (t, q xyzw, s = 1) of a camera at `eye` whose +z axis points at `target`, +x to the right and
+    +y down (the image convention of the projection above), computed on the host in float64.  `up` is the world's up
+    direction; the default suits a map whose first camera is upright (y down)."""
+    e, t, u = (np.asarray(v, dtype=np.float64).reshape(3) for v in (eye, target, up))
+    z = t - e
+    if not np.linalg.norm(z) > 0.0:
+        raise ValueError("look_at: eye and target coincide")
+    z = z / np.linalg.norm(z)
+    x = np.cross(z, u)
+    if not np.linalg.norm(x) > 1e-12 * max(1.0, np.linalg.norm(u)):
+        raise ValueError("look_at: up is parallel to the viewing direction")
+    x = x / np.linalg.norm(x)
+    y = np.cross(z, x)
+    R = np.stack([x, y, z], axis=1)                                      # columns: the camera axes in the world
+    # quaternion of a rotation matrix, the branch with the largest pivot; w >= 0
+    tr = R[0, 0] + R[1, 1] + R[2, 2]
+    if tr > 0.0:
+        s = 2.0 * math.sqrt(1.0 + tr)
+        q = [(R[2, 1] - R[1, 2]) / s, (R[0, 2] - R[2, 0]) / s, (R[1, 0] - R[0, 1]) / s, 0.25 * s]
+    else:
+        i = int(np.argmax([R[0, 0], R[1, 1], R[2, 2]]))
+        j, k = (i + 1) % 3, (i + 2) % 3
+        s = 2.0 * math.sqrt(1.0 + R[i, i] - R[j, j] - R[k, k])
+        q = [0.0, 0.0, 0.0, (R[k, j] - R[j, k]) / s]
+        q[i], q[j], q[k] = 0.25 * s, (R[j, i] + R[i, j]) / s, (R[k, i] + R[i, k]) / s
+    q = np.asarray(q)
+    if q[3] < 0.0:
+        q = -q
+    return torch.from_numpy(np.concatenate([e, q, [1.0]])[None]).to(torch.float32)
+
+
+def behind(T_WC: torch.Tensor, distance: float = 1.0, height: float = 0.25) -> torch.Tensor:
+    """Chase camera for a tracked pose: the same orientation, moved `distance` back along the camera's viewing axis and
+    `height` up (against its +y axis), unit scale: t' = t + R (0, -height, -distance), q' = q, s' = 1.  Plain tensor
+    operations on T_WC's own device: a tracked pose needs no host round trip."""
+    T = T_WC.reshape(-1, 8)[:1]
+    t, qv, w = T[:, :3], T[:, 3:6], T[:, 6:7]
+    v = torch.tensor([[0.0, -float(height), -float(distance)]], dtype=T.dtype, device=T.device)
+    u = 2.0 * torch.linalg.cross(qv, v)
+    return torch.cat([t + v + w * u + torch.linalg.cross(qv, u), T[:, 3:7], torch.ones_like(w)], dim=1)
+
+
+def _pinhole(K, size):
+    if K is None:
+        return default_intrinsics(size)
+    if isinstance(K, torch.Tensor):
+        K = K.detach().cpu().tolist()
+    K = np.asarray(K, dtype=np.float64)
+    if K.shape == (3, 3):
+        K = np.array([K[0, 0], K[1, 1], K[0, 2], K[1, 2]])
+    if K.shape != (4,):
+        raise ValueError(f"K must be (fx, fy, cx, cy) or a 3 x 3 matrix, got shape {K.shape}")
+    fx, fy, cx, cy = (float(v) for v in K)
+    if not (0.0 < fx < math.inf and 0.0 < fy < math.inf and math.isfinite(cx) and math.isfinite(cy)):
+        raise ValueError(f"focal lengths must be positive and the principal point finite, got {(fx, fy, cx, cy)}")
+    return fx, fy, cx, cy
+
+
+def map_tables(keyframes):
+    """The device tables render_map builds from `keyframes` on every call (three small host-to-device copies), built once:
+    pass the result as `keyframes` to draw the same map again without them, e.g. inside a graph capture, where a copy
+    from host memory is not allowed.  Valid while the keyframes' tensors are neither reallocated nor freed; None for an
+    empty map."""
+    return _map_tables(keyframes)
+
+
+def workspace_bytes(size: Sequence[int]) -> int:
+    """Bytes of the key buffer render_map needs for size = (H, W)."""
+    n = int(_ffi.lib().m3_render_ws_bytes(int(size[0]), int(size[1])))
+    if n <= 0:
+        raise ValueError(f"unsupported view size {tuple(size)} (each side 1 ... 16384)")
+    return n
+
+
+def render_map(keyframes, T_WC, K, size, c_conf_threshold: Optional[float] = 1.5, point_size: int = 1,
+               near: float = 1e-3, far: float = math.inf, background=(0, 0, 0), return_index: bool = False, out=None,
+               workspace: Optional[torch.Tensor] = None):
+    """(rgb uint8 [H,W,3], depth float32 [H,W][, index int64 [H,W]]) of `keyframes` (as collect_map takes them) seen from
+    the Sim(3) pose T_WC ([1,8] or [8] float32 DEVICE tensor, read by the kernel) through the pinhole K = (fx, fy, cx,
+    cy) (or a 3 x 3 matrix; None: default_intrinsics(size)), size = (H, W).
+
+    depth is the camera-frame z of the winning point (+inf where nothing was drawn), index its source index k * N + n
+    (-1 where nothing was drawn).  `keyframes` may also be the result of map_tables(keyframes).  `out`: a tuple of tensors to write into instead of allocating; `workspace`: a uint8
+    device tensor of workspace_bytes(size).  An empty map gives the background image."""
+    if len(size) != 2 or int(size[0]) <= 0 or int(size[1]) <= 0:
+        raise ValueError(f"size must be (H, W) with positive entries, got {size}")
+    hv, wv = int(size[0]), int(size[1])
+    if point_size not in POINT_SIZES:
+        raise ValueError(f"point_size must be one of {POINT_SIZES}, got {point_size}")
+    fx, fy, cx, cy = _pinhole(K, (hv, wv))
+    near, far = float(near), float(far)
+    if not (0.0 <= near < far):
+        raise ValueError(f"need 0 <= near < far, got near={near}, far={far}")
+    bg = tuple(int(v) for v in background)
+    if len(bg) != 3 or any(v < 0 or v > 255 for v in bg):
+        raise ValueError(f"background must be three values in 0 ... 255, got {background}")
+    ws_bytes = workspace_bytes((hv, wv))
+    m = keyframes if isinstance(keyframes, _MapTables) else _map_tables(keyframes)
+    view = _ffi.check(T_WC, torch.float32, "T_WC").reshape(-1)
+    if view.numel() != 8:
+        raise ValueError(f"T_WC must have 8 elements (t, q xyzw, s), got {tuple(T_WC.shape)}")
+    dev = view.device
+    if m is not None and m.device != dev:
+        raise ValueError(f"T_WC lives on {dev}, the map on {m.device}")
+    if out is None:
+        out = (torch.empty((hv, wv, 3), dtype=torch.uint8, device=dev), torch.empty((hv, wv), dtype=torch.float32, device=dev))
+        if return_index:
+            out += (torch.empty((hv, wv), dtype=torch.int64, device=dev),)
+    if len(out) != (3 if return_index else 2):
+        raise ValueError(f"out must hold {'rgb, depth and index' if return_index else 'rgb and depth'}")
+    shapes = ((hv, wv, 3), (hv, wv), (hv, wv))
+    for t, dt, name, shape in zip(out, (torch.uint8, torch.float32, torch.int64), ("rgb", "depth", "index"), shapes):
+        if _ffi.check(t, dt, f"out {name}", shape).data_ptr() != t.data_ptr():
+            raise ValueError(f"out {name} must be contiguous")
+    if workspace is None:
+        workspace = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+    _ffi.check(workspace, torch.uint8, "workspace")
+    if workspace.numel() < ws_bytes or not workspace.is_contiguous() or workspace.data_ptr() % 16:
+        raise ValueError(f"workspace must be a contiguous, 16-byte aligned uint8 tensor of at least {ws_bytes} bytes")
+    use, thr = (0, 0.0) if c_conf_threshold is None else (1, float(c_conf_threshold))
+    if m is None:
+        tabs, poses, nk, k, n, layout = (None, None, None), None, None, 0, 1, 0
+    else:
+        tabs, poses, nk, k, n, layout = m.table, m.poses, m.nk, m.k, m.n, m.layout
+    _ffi.call("m3_render_map", _ffi.ptr(tabs[0]), _ffi.ptr(tabs[1]), _ffi.ptr(tabs[2]), _ffi.ptr(poses), _ffi.ptr(nk), k, n,
+              use, thr, layout, _ffi.ptr(view), fx, fy, cx, cy, hv, wv, near, far, int(point_size), bg[0], bg[1], bg[2],
+              _ffi.ptr(workspace), ws_bytes, _ffi.ptr(out[0]), _ffi.ptr(out[1]), _ffi.ptr(out[2]) if return_index else None,
+              _ffi.stream_ptr())
+    return tuple(out)
+
+
+def depth_to_rgb(depth: torch.Tensor, near: Optional[float] = None, far: Optional[float] = None) -> torch.Tensor:
+    """Grey image uint8 [H,W,3] of a rendered depth: near -> white, far -> dark grey (32), nothing drawn (+inf) -> black.
+    near / far default to the smallest / largest finite depth."""
+    d = depth.to(torch.float32)
+    ok = torch.isfinite(d)
+    lo = torch.where(ok, d, torch.full_like(d, math.inf)).min() if near is None else torch.tensor(float(near), device=d.device)
+    hi = torch.where(ok, d, torch.full_like(d, -math.inf)).max() if far is None else torch.tensor(float(far), device=d.device)
+    t = ((d - lo) / (hi - lo).clamp_min(1e-30)).clamp(0.0, 1.0)
+    g = torch.where(ok, 255.0 - 223.0 * torch.nan_to_num(t, nan=0.0, posinf=1.0), torch.zeros_like(d)).floor().to(torch.uint8)
+    return g[..., None].expand(*g.shape, 3).contiguous()
+
+
+def save_image(path, rgb) -> None:
+    """PNG of a uint8 [H,W,3] image (one device-to-host copy)."""
+    from PIL import Image
+    a = rgb.detach().cpu().numpy() if isinstance(rgb, torch.Tensor) else np.asarray(rgb)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError(f"expected a uint8 [H,W,3] image, got {a.dtype} {a.shape}")
+    Image.fromarray(np.ascontiguousarray(a), "RGB").save(os.fspath(path), format="PNG")
+
+
+def scaled_intrinsics(K, from_size: Sequence[int], to_size: Sequence[int]):
+    """(fx, fy, cx, cy) of `K` (given for an image of from_size = (H, W)) moved to to_size, pixel-centre coordinates."""
+    fx, fy, cx, cy = _pinhole(K, from_size)
+    sy, sx = to_size[0] / from_size[0], to_size[1] / from_size[1]
+    return fx * sx, fy * sy, (cx + 0.5) * sx - 0.5, (cy + 0.5) * sy - 0.5
+
+
+def _frame_size(img: torch.Tensor):
+    return (int(img.shape[1]), int(img.shape[2])) if img.dtype != torch.uint8 else (int(img.shape[0]), int(img.shape[1]))
+
+
+class ViewRecorder:
+    """callback(frame, keyframes) for SLAM.run / run_dataset: renders the map after every `every`-th frame and writes
+    directory/view_%06d.png (numbered by frame_id).
+
+    camera: "follow" (behind(frame.T_WC, follow_distance, follow_height)), "frame" (the frame's own pose) or a fixed
+    [1,8] pose.  K None: the frame's intrinsics moved to `size`, else default_intrinsics(size).  The output tensors
+    and the workspace are allocated once; per frame the host reads back the finished image and nothing else."""
+
+    def __init__(self, directory, every: int = 1, camera="follow", size: Sequence[int] = (480, 640), K=None,
+                 follow_distance: float = 1.0, follow_height: float = 0.25, **render_kwargs) -> None:
+        if int(every) < 1:
+            raise ValueError(f"every must be >= 1, got {every}")
+        if isinstance(camera, str) and camera not in ("follow", "frame"):
+            raise ValueError(f"camera must be 'follow', 'frame' or a pose, got {camera!r}")
+        if "return_index" in render_kwargs or "out" in render_kwargs or "workspace" in render_kwargs:
+            raise ValueError("the recorder owns its outputs: return_index / out / workspace cannot be passed")
+        self.directory = os.fspath(directory)
+        os.makedirs(self.directory, exist_ok=True)
+        self.every, self.camera, self.size, self.K = int(every), camera, (int(size[0]), int(size[1])), K
+        self.follow = (float(follow_distance), float(follow_height))
+        self.render_kwargs = render_kwargs
+        self.calls = 0
+        self.paths: list[str] = []
+        self.last_pose: Optional[torch.Tensor] = None
+        self._out = self._ws = None
+
+    def view_pose(self, frame) -> torch.Tensor:
+        if isinstance(self.camera, str):
+            return behind(frame.T_WC, *self.follow) if self.camera == "follow" else frame.T_WC.reshape(1, 8)
+        return torch.as_tensor(self.camera, dtype=torch.float32).reshape(1, 8).to(frame.T_WC.device)
+
+    def intrinsics(self, frame):
+        if self.K is not None:
+            return _pinhole(self.K, self.size)
+        if getattr(frame, "K", None) is not None:
+            return scaled_intrinsics(frame.K, _frame_size(frame.img), self.size)
+        return default_intrinsics(self.size)
+
+    def __call__(self, frame, keyframes) -> Optional[str]:
+        self.calls += 1
+        if (self.calls - 1) % self.every:
+            return None
+        pose = self.view_pose(frame).to(torch.float32).contiguous()
+        if self._out is None:
+            dev = pose.device
+            self._out = (torch.empty((*self.size, 3), dtype=torch.uint8, device=dev),
+                         torch.empty(self.size, dtype=torch.float32, device=dev))
+            self._ws = torch.empty((workspace_bytes(self.size),), dtype=torch.uint8, device=dev)
+        rgb, _ = render_map(keyframes, pose, self.intrinsics(frame), self.size, out=self._out, workspace=self._ws,
+                            **self.render_kwargs)
+        path = os.path.join(self.directory, "view_%06d.png" % int(frame.frame_id))
+        save_image(path, rgb)
+        self.last_pose = pose.clone()
+        self.paths.append(path)
+        return path

@@ -19,7 +19,7 @@ from typing import Callable, Iterable, Optional
 
 import torch
 
-from . import export
+from . import export, render
 from .config import get_config
 from .dataloader import Dataset, load_dataset
 from .frame import Keyframes, create_frame
@@ -214,3 +214,27 @@ class SLAM:
             ts = self.timestamps
             poses = torch.cat(self.poses) if self.poses else torch.empty((0, 8))
         return export.save_trajectory(path, ts, poses, format=format)
+
+    # ------------------------------------------------------------------ headless views (no counterpart: the reference
+    # hands its callback to a desktop GUI)
+    def render_view(self, T_WC: Optional[torch.Tensor] = None, K=None, size=None, **kw):
+        """render.render_map over the keyframes: (rgb uint8 [H,W,3], depth float32 [H,W][, index]).  Defaults: the pose
+        the last processed frame was given, the keyframes' own image size, and the keyframes' intrinsics moved to
+        `size` (render.default_intrinsics without calibration)."""
+        frames = [kf for kf in self.keyframes._frames if kf.X_canon is not None]
+        if T_WC is None:
+            if not self.poses:
+                raise ValueError("render_view: no frame has been processed yet; pass T_WC")
+            T_WC = self.poses[-1]
+        own = render._frame_size(frames[0].img) if frames else None
+        if size is None:
+            if own is None:
+                raise ValueError("render_view: the map is empty; pass size")
+            size = own
+        if K is None and own is not None and self.keyframes.get_intrinsics() is not None:
+            K = render.scaled_intrinsics(self.keyframes.get_intrinsics(), own, size)
+        return render.render_map(self.keyframes, T_WC, K, size, **kw)
+
+    def save_view(self, path, T_WC: Optional[torch.Tensor] = None, K=None, size=None, **kw) -> None:
+        """render_view written as a PNG."""
+        render.save_image(path, self.render_view(T_WC, K, size, **kw)[0])
