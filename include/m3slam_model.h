@@ -40,8 +40,8 @@ enum {
     M3_EPI_BF16_RELU = 4,  /* C(bf16) = relu(acc + bias) */
     M3_EPI_BF16_ADD = 5,   /* C(bf16) = R(bf16) + acc + bias  (C may alias R) */
     M3_EPI_BF16_ROPE = 6,  /* C(bf16) = rope2d(acc + bias) on the leading rope_cols columns */
-    /* flag, OR-ed into the epilogue of m3_conv3x3_dt / m3_conv3x3_grouped2_dt: the convolution reads relu(X) - the
-     * ReLU is applied to the operand fragments in registers, relu(X) is never written (DPT residual unit: relu -> conv1) */
+    /* flag, OR-ed into the epilogue of m3_conv3x3_grouped2_dt / m3_conv3x3_direct_grouped2_dt: the convolution reads relu(X);
+     * the ReLU is applied to the operand fragments in registers, relu(X) is never written (DPT residual unit: relu -> conv1) */
     M3_EPI_INPUT_RELU = 0x100
 };
 
@@ -115,20 +115,16 @@ int m3_gemm_set_tile(int tile);
 int m3_ln_slot_count(int M, int N, int groups);
 
 /* 3x3 convolution, padding 1, stride 1 or 2, as an implicit GEMM: X 16-bit NHWC [B,H,W,Cin],
- * W 16-bit [Cout,3,3,Cin], Y NHWC [B,OH,OW,Cout].  Cin % 64 == 0, Cout % 4 == 0.  zero16: 16
- * zero bytes in device memory (source of the padding taps). */
-int m3_conv3x3_dt(const void *X, const void *W, const float *bias, void *Y, const void *R,
-                  const void *zero16, int B, int H, int Wd, int Cin, int Cout, int stride,
-                  int epilogue, void *splitk_ws, int64_t splitk_ws_bytes, int dtype, void *stream);
-
-/* Two same-shape convolutions in one launch (the two DPT heads): X [2,B,H,W,Cin], Y / R [2,B,OH,OW,Cout], group g
- * uses (W_g, bias_g).  Split-K scratch: 2 x m3_conv3x3_splitk_bytes(B, ...). */
+ * W0 16-bit [Cout,3,3,Cin], Y (and R) NHWC [B,OH,OW,Cout].  Cin % 64 == 0, Cout % 4 == 0.  zero16: 16
+ * zero bytes in device memory (source of the padding taps).  W1 == NULL: a single group (bias1 is ignored).
+ * W1 != NULL: two same-shape convolutions in one launch (the two DPT heads): X [2,B,H,W,Cin], Y / R [2,B,OH,OW,Cout],
+ * group g uses (W_g, bias_g).  Split-K scratch: groups x m3_conv3x3_splitk_bytes(B, ...). */
 int m3_conv3x3_grouped2_dt(const void *X, const void *W0, const void *W1, const float *bias0, const float *bias1,
                            void *Y, const void *R, const void *zero16, int B, int H, int Wd, int Cin, int Cout,
                            int stride, int epilogue, void *splitk_ws, int64_t splitk_ws_bytes, int dtype,
                            void *stream);
 
-/* Split-K scratch of m3_conv3x3_dt: small feature maps with a long K (the 16x16 / 32x32 DPT maps,
+/* Split-K scratch of m3_conv3x3_grouped2_dt, per group: small feature maps with a long K (the 16x16 / 32x32 DPT maps,
  * K = 9*Cin up to 6912) cannot fill the chip with output tiles, so they are multiplied in K-slices
  * into fp32 partial planes which a second kernel sums in a fixed order before applying the epilogue.
  * The slice count depends on the per-image geometry only (not on B): a pair's result does not depend
@@ -139,7 +135,7 @@ int64_t m3_conv3x3_splitk_bytes(int B, int H, int Wd, int Cin, int Cout, int str
  * post-processing): pts [B,H,W,3] = xyz/|xyz| * expm1(|xyz|), conf [B,H,W] = 1 + exp(c) with
  * (xyz, c) = W4 . relu(conv3x3(X, W) + bias) + b4.  W [128,3,3,Cin], W4 [4,128] 16-bit; the
  * 128-channel full-resolution map is never written and never rounded to 16 bits (the unfused chain
- * m3_conv3x3(RELU) -> m3_gemm(F32) -> m3_pts_post rounds it once: that rounding was the largest
+ * m3_conv3x3_grouped2_dt(RELU) -> m3_gemm_ex(F32) -> m3_pts_post rounds it once: that rounding was the largest
  * single term of the pointmap error against the fp32 oracle). */
 int m3_conv3x3_relu_head4_dt(const void *X, const void *W, const float *bias, const void *W4, const float *b4,
                              float *pts, float *conf, const void *zero16, int B, int H, int Wd, int Cin,
@@ -149,12 +145,9 @@ int m3_conv3x3_relu_head4_dt(const void *X, const void *W, const float *bias, co
  * (public DPT head: head.0 -> Upsample(x2) -> head.2 conv3x3 + ReLU -> head.4 1x1; oracle/model.py dpt_head):
  * X NHWC [B,H/2,W/2,128] when upsample != 0, else [B,H,W,128]; W [128,3,3,128], W4 [4,128] in the 16-bit dtype.
  * A workgroup stages the 18x18x128 halo of its 16x16 output tile once in LDS (interpolating it on the way in),
- * so the full-resolution 128-channel map is neither written nor re-read.  H, W multiples of 16. */
-int m3_dpt_tail_dt(const void *X, const void *W, const float *bias, const void *W4, const float *b4,
-                   float *pts, float *conf, const void *zero16, int B, int H, int Wd, int upsample,
-                   int dtype, void *stream);
-
-/* m3_dpt_tail_dt for both heads in one launch: X [2,B,h,w,128], pts [2,B,H,W,3], conf [2,B,H,W]. */
+ * so the full-resolution 128-channel map is neither written nor re-read.  H, W multiples of 16.
+ * Wc1 == NULL and W41 == NULL: one head (bias1 / b41 are ignored).  Otherwise both heads in one launch: X [2,B,h,w,128],
+ * pts [2,B,H,W,3], conf [2,B,H,W]; head g uses (Wc_g, bias_g, W4_g, b4_g). */
 int m3_dpt_tail_grouped2_dt(const void *X, const void *Wc0, const void *Wc1, const float *bias0, const float *bias1,
                             const void *W40, const void *W41, const float *b40, const float *b41, float *pts,
                             float *conf, const void *zero16, int B, int H, int Wd, int upsample, int dtype,
@@ -162,11 +155,10 @@ int m3_dpt_tail_grouped2_dt(const void *X, const void *Wc0, const void *Wc1, con
 
 /* head.0 of the public DPT head with ITS x2 upsample fused in, as the same direct convolution (oracle/model.py
  * dpt_head: refinenet1's trailing x2 interpolation -> head.0 conv3x3 256 -> 128): X NHWC [B,H/2,W/2,Cin] when upsample
- * != 0, else [B,H,W,Cin]; W [128,3,3,Cin] (Cin = 256 or 128); Y NHWC [B,H,W,128] = conv(up(X)) + bias in the 16-bit
- * dtype.  The upsampled Cin-channel map is neither written nor re-read.  H, W multiples of 16. */
-int m3_conv3x3_up_direct_dt(const void *X, const void *W, const float *bias, void *Y, const void *zero16, int B, int H,
-                            int Wd, int Cin, int upsample, int dtype, void *stream);
-/* ... for both heads in one launch: X [2,B,h,w,Cin], Y [2,B,H,W,128]; head g uses (W_g, bias_g). */
+ * != 0, else [B,H,W,Cin]; W0 [128,3,3,Cin] (Cin = 256 or 128); Y NHWC [B,H,W,128] = conv(up(X)) + bias in the 16-bit
+ * dtype.  The upsampled Cin-channel map is neither written nor re-read.  H, W multiples of 16.
+ * W1 == NULL: one head (bias1 is ignored).  Otherwise both heads in one launch: X [2,B,h,w,Cin], Y [2,B,H,W,128]; head g
+ * uses (W_g, bias_g). */
 int m3_conv3x3_up_direct_grouped2_dt(const void *X, const void *W0, const void *W1, const float *bias0,
                                      const float *bias1, void *Y, const void *zero16, int B, int H, int Wd, int Cin,
                                      int upsample, int dtype, void *stream);
@@ -175,7 +167,7 @@ int m3_conv3x3_up_direct_grouped2_dt(const void *X, const void *W0, const void *
  * fusion blocks, 256 -> 256 channels at 128 x 128 / 64 x 64): X NHWC [(2,)B,H,W,Cin], W_g [Cout,3,3,Cin], Y (and R) NHWC
  * [(2,)B,H,W,Cout], Cin, Cout in {128, 256}, H, W multiples of 16; epilogue M3_EPI_BF16 | M3_EPI_BF16_RELU |
  * M3_EPI_BF16_ADD, optionally | M3_EPI_INPUT_RELU.  W1 == NULL: a single group.  Returns THE SAME BITS as
- * m3_conv3x3_dt / m3_conv3x3_grouped2_dt on the same operands (both walk K as (64-channel slice, tap, k-step) and apply
+ * m3_conv3x3_grouped2_dt on the same operands and group count (both walk K as (64-channel slice, tap, k-step) and apply
  * the epilogue in the same order): the caller picks by problem size - the direct form pays once the grid
  * (H/16 * ceil(W/32) * B * Cout/128 * groups workgroups) fills the chip. */
 int m3_conv3x3_direct_grouped2_dt(const void *X, const void *W0, const void *W1, const float *bias0, const float *bias1,

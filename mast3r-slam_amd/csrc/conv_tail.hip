@@ -517,18 +517,14 @@ static int dpt_tail_launch(const void *X, const void *Wc, const float *bias, con
     return M3_OK;
 }
 
-int m3_dpt_tail_dt(const void *X, const void *Wc, const float *bias, const void *W4, const float *b4, float *pts,
-                   float *conf, const void *zero16, int B, int H, int W, int upsample, int dtype, void *stream) {
-    M3_REQUIRE(pts && conf);
-    return dpt_tail_launch(X, Wc, bias, W4, b4, nullptr, nullptr, nullptr, nullptr, pts, conf, nullptr, nullptr, zero16, B, H, W,
-                           128, 128, EP_TAIL, 0, upsample, dtype, stream);
-}
-
-// Both heads in one launch: X [2,B,h,w,128], pts [2,B,H,W,3], conf [2,B,H,W]; head g uses (Wc_g, bias_g, W4_g, b4_g).
+// The fused tail.  Wc1 == NULL (and W41 == NULL): one head - X [B,h,w,128], pts [B,H,W,3], conf [B,H,W]; bias1 / b41 are
+// ignored.  Otherwise both heads in one launch: X [2,B,h,w,128], pts [2,B,H,W,3], conf [2,B,H,W]; head g uses
+// (Wc_g, bias_g, W4_g, b4_g).
 int m3_dpt_tail_grouped2_dt(const void *X, const void *Wc0, const void *Wc1, const float *bias0, const float *bias1,
                             const void *W40, const void *W41, const float *b40, const float *b41, float *pts,
                             float *conf, const void *zero16, int B, int H, int W, int upsample, int dtype, void *stream) {
-    M3_REQUIRE(Wc1 != nullptr && pts && conf);
+    M3_REQUIRE(pts && conf && (Wc1 == nullptr) == (W41 == nullptr));
+    if (!Wc1) bias1 = b41 = nullptr;
     return dpt_tail_launch(X, Wc0, bias0, W40, b40, Wc1, bias1, W41, b41, pts, conf, nullptr, nullptr, zero16, B, H, W, 128, 128,
                            EP_TAIL, 0, upsample, dtype, stream);
 }
@@ -536,25 +532,19 @@ int m3_dpt_tail_grouped2_dt(const void *X, const void *Wc0, const void *Wc1, con
 // Direct 3x3 convolution to 128 output channels with the x2 upsample of its input fused in (head.0 of the DPT head:
 // Cin = 256; Cin = 128 also accepted): X NHWC [B, H/2, W/2, Cin] (upsample) or [B, H, W, Cin], Wc [128][3][3][Cin],
 // Y NHWC [B, H, W, 128] = conv(up(X)) + bias, 16-bit.  H, W multiples of 16 (of 2 as well with the upsample).
-int m3_conv3x3_up_direct_dt(const void *X, const void *Wc, const float *bias, void *Y, const void *zero16, int B, int H,
-                            int W, int Cin, int upsample, int dtype, void *stream) {
-    M3_REQUIRE(Y != nullptr);
-    return dpt_tail_launch(X, Wc, bias, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, Y, nullptr, zero16,
-                           B, H, W, Cin, 128, EP_PLAIN, 0, upsample, dtype, stream);
-}
-
-// ... for both heads in one launch: X [2,B,h,w,Cin], Y [2,B,H,W,128]; head g uses (Wc_g, bias_g).
+// Wc1 == NULL: one head (bias1 ignored); otherwise both heads in one launch: X [2,B,h,w,Cin], Y [2,B,H,W,128]; head g
+// uses (Wc_g, bias_g).
 int m3_conv3x3_up_direct_grouped2_dt(const void *X, const void *Wc0, const void *Wc1, const float *bias0, const float *bias1,
                                      void *Y, const void *zero16, int B, int H, int W, int Cin, int upsample, int dtype,
                                      void *stream) {
-    M3_REQUIRE(Y != nullptr && Wc1 != nullptr);
-    return dpt_tail_launch(X, Wc0, bias0, nullptr, nullptr, Wc1, bias1, nullptr, nullptr, nullptr, nullptr, Y, nullptr, zero16, B,
-                           H, W, Cin, 128, EP_PLAIN, 0, upsample, dtype, stream);
+    M3_REQUIRE(Y != nullptr);
+    return dpt_tail_launch(X, Wc0, bias0, nullptr, nullptr, Wc1, Wc1 ? bias1 : nullptr, nullptr, nullptr, nullptr, nullptr, Y,
+                           nullptr, zero16, B, H, W, Cin, 128, EP_PLAIN, 0, upsample, dtype, stream);
 }
 
 // The same direct convolution as a general 3x3 / padding 1 / stride 1 operator for the wide DPT maps (the residual units
 // of the fusion blocks: 256 -> 256 at 128 x 128 and 64 x 64): Cin, Cout in {128, 256}; epilogue M3_EPI_BF16 | _RELU | _ADD
-// (R = residual, laid out as Y), optionally OR-ed with M3_EPI_INPUT_RELU.  SAME BITS as m3_conv3x3_dt on the same
+// (R = residual, laid out as Y), optionally OR-ed with M3_EPI_INPUT_RELU.  SAME BITS as m3_conv3x3_grouped2_dt on the same
 // operands: both walk K as (64-channel slice, tap, k-step) and apply the epilogue in the same order, so a caller may pick
 // either by problem size.  H, W multiples of 16.  W1 == NULL: one group.
 int m3_conv3x3_direct_grouped2_dt(const void *X, const void *W0, const void *W1, const float *bias0, const float *bias1,

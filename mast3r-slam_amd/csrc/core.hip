@@ -15,7 +15,9 @@ extern "C" {
 // against a 1xxx header must be rebuilt (tests assert the exact value).
 // 3000: m3_gemm_ex is the only dense GEMM entry point (RoPE from positions only; the per-token table is gone), and the
 // bf16-only aliases of the _dt operators are removed.
-int m3_abi_version(void) { return 3000; }
+// 4000: the one-group convolution entry points (m3_conv3x3_dt, m3_dpt_tail_dt, m3_conv3x3_up_direct_dt) are removed; the
+// *_grouped2_dt forms take W1 == NULL for one group.
+int m3_abi_version(void) { return 4000; }
 
 const char *m3_status_string(int status) {
     switch (status) {

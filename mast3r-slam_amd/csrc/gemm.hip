@@ -562,58 +562,37 @@ int64_t m3_conv3x3_splitk_bytes(int B, int H, int Wd, int Cin, int Cout, int str
     return S > 1 ? (int64_t)S * B * OH * OW * Cout * 4 : 0;
 }
 
-int m3_conv3x3_dt(const void *X, const void *W, const float *bias, void *Y, const void *R, const void *zero16,
-                  int B, int H, int Wd, int Cin, int Cout, int stride, int epilogue, void *splitk_ws,
-                  int64_t splitk_ws_bytes, int dtype, void *stream) {
-    const int relu_in = (epilogue & 0x100) ? 1 : 0;           // M3_EPI_INPUT_RELU
-    epilogue &= 0xff;
-    M3_REQUIRE(X && W && Y && zero16 && B > 0 && H > 0 && Wd > 0 && Cin > 0 && Cout > 0 && dt_ok(dtype));
-    M3_REQUIRE(Cin % BK == 0 && Cout % 4 == 0 && (stride == 1 || stride == 2) && epilogue != EPI_BF16_ROPE);
-    M3_REQUIRE(!((epilogue == EPI_F32_ACCUM || epilogue == EPI_BF16_ADD) && !R));
-    GemmArgs a{};
-    a.relu_a = relu_in;
-    a.A = (const bf16_t *)X; a.W = (const bf16_t *)W; a.bias = bias; a.C = Y; a.R = R;
-    a.zero16 = (const bf16_t *)zero16;
-    a.H = H; a.Wd = Wd; a.Cin = Cin; a.stride = stride;
-    a.OH = (H + 2 - 3) / stride + 1; a.OW = (Wd + 2 - 3) / stride + 1;
-    a.M = B * a.OH * a.OW; a.N = Cout; a.K = 9 * Cin; a.ldc = Cout; a.dt = dtype;
-    // split-K is decided by the per-image geometry alone; a shape that wants it must be given its scratch
-    const int S = pick_splits(a.OH * a.OW, Cout, a.K);
-    if (S > 1) {
-        M3_REQUIRE(splitk_ws && (reinterpret_cast<size_t>(splitk_ws) & 15) == 0 &&
-                   splitk_ws_bytes >= (int64_t)S * a.M * a.N * 4);
-        return run_split<1>(a, S, epilogue, splitk_ws, (hipStream_t)stream);
-    }
-    if (use_256(a.M, a.N)) return m3_launch_gemm256_conv(a, epilogue, (hipStream_t)stream);
-    return launch<1>(a, epilogue, (hipStream_t)stream);
-}
-
-// Two convolutions of identical shape in one launch (the two DPT heads: same maps, different weights):
-// X [2,B,H,W,Cin], W0 / W1, bias0 / bias1, Y (and R) [2,B,OH,OW,Cout].  Split-K scratch: twice m3_conv3x3_splitk_bytes.
+// One convolution, or two of identical shape in one launch (the two DPT heads: same maps, different weights).
+// W1 == NULL: one group - X [B,H,W,Cin], Y (and R) [B,OH,OW,Cout], bias1 ignored.  Otherwise X [2,B,H,W,Cin], W0 / W1,
+// bias0 / bias1, Y (and R) [2,B,OH,OW,Cout].  Split-K scratch: groups x m3_conv3x3_splitk_bytes.
 int m3_conv3x3_grouped2_dt(const void *X, const void *W0, const void *W1, const float *bias0, const float *bias1,
                            void *Y, const void *R, const void *zero16, int B, int H, int Wd, int Cin, int Cout,
                            int stride, int epilogue, void *splitk_ws, int64_t splitk_ws_bytes, int dtype, void *stream) {
     const int relu_in = (epilogue & 0x100) ? 1 : 0;           // M3_EPI_INPUT_RELU
     epilogue &= 0xff;
-    M3_REQUIRE(X && W0 && W1 && Y && zero16 && B > 0 && H > 0 && Wd > 0 && Cin > 0 && Cout > 0 && dt_ok(dtype));
+    M3_REQUIRE(X && W0 && Y && zero16 && B > 0 && H > 0 && Wd > 0 && Cin > 0 && Cout > 0 && dt_ok(dtype));
     M3_REQUIRE(Cin % BK == 0 && Cout % 4 == 0 && (stride == 1 || stride == 2) && epilogue != EPI_BF16_ROPE);
     M3_REQUIRE(!((epilogue == EPI_F32_ACCUM || epilogue == EPI_BF16_ADD) && !R));
-    M3_REQUIRE((bias0 == nullptr) == (bias1 == nullptr));
+    M3_REQUIRE(!W1 || (bias0 == nullptr) == (bias1 == nullptr));
     GemmArgs a{};
     a.relu_a = relu_in;
-    a.A = (const bf16_t *)X; a.W = (const bf16_t *)W0; a.W2 = (const bf16_t *)W1; a.bias = bias0; a.bias2 = bias1;
-    a.C = Y; a.R = R; a.zero16 = (const bf16_t *)zero16;
+    a.A = (const bf16_t *)X; a.W = (const bf16_t *)W0; a.bias = bias0; a.C = Y; a.R = R;
+    a.zero16 = (const bf16_t *)zero16;
     a.H = H; a.Wd = Wd; a.Cin = Cin; a.stride = stride;
     a.OH = (H + 2 - 3) / stride + 1; a.OW = (Wd + 2 - 3) / stride + 1;
     a.M = B * a.OH * a.OW; a.N = Cout; a.K = 9 * Cin; a.ldc = Cout; a.dt = dtype;
-    a.groups = 2; a.a_gstride = (long long)B * H * Wd * Cin; a.c_gstride = (long long)a.M * Cout;
+    if (W1) {
+        a.W2 = (const bf16_t *)W1; a.bias2 = bias1;
+        a.groups = 2; a.a_gstride = (long long)B * H * Wd * Cin; a.c_gstride = (long long)a.M * Cout;
+    }
+    // split-K is decided by the per-image geometry alone; a shape that wants it must be given its scratch
     const int S = pick_splits(a.OH * a.OW, Cout, a.K);
     if (S > 1) {
         M3_REQUIRE(splitk_ws && (reinterpret_cast<size_t>(splitk_ws) & 15) == 0 &&
-                   splitk_ws_bytes >= 2 * (int64_t)S * a.M * a.N * 4);
+                   splitk_ws_bytes >= (W1 ? 2 : 1) * (int64_t)S * a.M * a.N * 4);
         return run_split<1>(a, S, epilogue, splitk_ws, (hipStream_t)stream);
     }
-    if (use_256(a.M, a.N, 2)) return m3_launch_gemm256_conv(a, epilogue, (hipStream_t)stream);
+    if (use_256(a.M, a.N, W1 ? 2 : 1)) return m3_launch_gemm256_conv(a, epilogue, (hipStream_t)stream);
     return launch<1>(a, epilogue, (hipStream_t)stream);
 }
 

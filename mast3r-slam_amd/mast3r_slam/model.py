@@ -401,16 +401,26 @@ class Mast3rFull:
             raise ValueError(f"images must be [B,H,W,3] with H,W multiples of 16, got {tuple(img.shape)}")
         return img.to(self.device).contiguous()
 
-    def _self_attn(self, xn, p, heads, nb, t, rtok):
-        P = self.P
+    def _attn_qkv(self, qkv, nb, t, heads):
+        """Self-attention of nb images of t tokens on a packed q|k|v projection [..., 3c] (q|k rotated, q pre-scaled by
+        ops.QK_PRESCALE; c = heads * 64): the kernel reads the three column blocks through strides.  -> [..., c]."""
         c = heads * 64
-        # [M,3c], q|k rotated; q additionally carries softmax scale * log2(e) (folded in before the 16-bit rounding)
-        qkv = ops.gemm_rope(xn, P[p + ".qkv.w"], P[p + ".qkv.b"], rtok, 2 * c, q_cols=c, q_scale=ops.QK_PRESCALE,
-                            pv_bf16=self.pv_bf16)
-        out = torch.empty((nb * t, c), dtype=xn.dtype, device=xn.device)
-        ops.attention(qkv, qkv[:, c:], qkv[:, 2 * c:], out, nbatch=nb, heads=heads, tq=t, tk=t,
-                      q_row_stride=3 * c, kv_row_stride=3 * c, o_row_stride=c, q_batch_stride=t * 3 * c,
-                      kv_batch_stride=t * 3 * c, o_batch_stride=t * c, prescaled=True, pv_bf16=self.pv_bf16)
+        out = torch.empty(qkv.shape[:-1] + (c,), dtype=qkv.dtype, device=qkv.device)
+        f = qkv.view(-1, 3 * c)
+        ops.attention(f, f[:, c:], f[:, 2 * c:], out, nbatch=nb, heads=heads, tq=t, tk=t, q_row_stride=3 * c, kv_row_stride=3 * c,
+                      o_row_stride=c, q_batch_stride=t * 3 * c, kv_batch_stride=t * 3 * c, o_batch_stride=t * c, prescaled=True,
+                      pv_bf16=self.pv_bf16)
+        return out
+
+    def _attn_q_kv(self, q, kv, nb, t, heads):
+        """Cross-attention of nb images of t tokens: q [..., c] (rotated, pre-scaled) on a packed k|v projection [..., 2c]
+        (k rotated) of the same row order.  -> [..., c]."""
+        c = heads * 64
+        out = torch.empty(q.shape, dtype=q.dtype, device=q.device)
+        f = kv.view(-1, 2 * c)
+        ops.attention(q.view(-1, c), f, f[:, c:], out, nbatch=nb, heads=heads, tq=t, tk=t, q_row_stride=c, kv_row_stride=2 * c,
+                      o_row_stride=c, q_batch_stride=t * c, kv_batch_stride=t * 2 * c, o_batch_stride=t * c, prescaled=True,
+                      pv_bf16=self.pv_bf16)
         return out
 
     # ------------------------------------------------------------------ encoder
@@ -434,11 +444,15 @@ class Mast3rFull:
             b = 2 * b
         if self.ln_fold and patches.shape[0] % 2 == 0:           # (the fold works on row PAIRS: an odd row count - one image with an
             return self._encode_fold(patches, b, t, rtok), (gh, gw)   #  odd token grid, e.g. 21 x 21 - takes the LayerNorm kernels)
+        E = c["enc_dim"]
         x = ops.gemm(patches, P["patch.w"], P["patch.b"], ops.EPI_F32)                        # fp32 residual stream
         for i in range(c["enc_depth"]):
             p = f"enc_blocks.{i}"
             xn = ops.layernorm(x, P[p + ".norm1.g"], P[p + ".norm1.b"], dtype=dt)
-            a = self._self_attn(xn, p + ".attn", c["enc_heads"], b, t, rtok)
+            # [M,3E], q|k rotated; q additionally carries softmax scale * log2(e) (folded in before the 16-bit rounding)
+            qkv = ops.gemm_rope(xn, P[p + ".attn.qkv.w"], P[p + ".attn.qkv.b"], rtok, 2 * E, q_cols=E, q_scale=ops.QK_PRESCALE,
+                                pv_bf16=self.pv_bf16)
+            a = self._attn_qkv(qkv, b, t, c["enc_heads"])
             ops.gemm(a, P[p + ".attn.proj.w"], P[p + ".attn.proj.b"], ops.EPI_F32_ACCUM, out=x, resid=x)
             xn = ops.layernorm(x, P[p + ".norm2.g"], P[p + ".norm2.b"], dtype=dt)
             hdn = ops.gemm(xn, P[p + ".mlp.fc1.w"], P[p + ".mlp.fc1.b"], ops.EPI_BF16_GELU)
@@ -460,10 +474,7 @@ class Mast3rFull:
             p = f"enc_blocks.{i}"
             qkv = ops.gemm_ex(x16, P[p + ".attn.qkv.fw"], P[p + ".attn.qkv.fb"], ops.EPI_BF16_ROPE,
                               rope=(rtok, 2 * E, E, ops.QK_PRESCALE), pv_bf16=self.pv_bf16, fold_in=(st, P[p + ".attn.qkv.fcs"]))
-            a = torch.empty((b * t, E), dtype=dt, device=x16.device)
-            ops.attention(qkv, qkv[:, E:], qkv[:, 2 * E:], a, nbatch=b, heads=heads, tq=t, tk=t,
-                          q_row_stride=3 * E, kv_row_stride=3 * E, o_row_stride=E, q_batch_stride=t * 3 * E,
-                          kv_batch_stride=t * 3 * E, o_batch_stride=t * E, prescaled=True, pv_bf16=self.pv_bf16)
+            a = self._attn_qkv(qkv, b, t, heads)
             ops.gemm_ex(a, P[p + ".attn.proj.w"], P[p + ".attn.proj.b"], ops.EPI_F32_ACCUM, hl=hl)
             hdn = ops.gemm_ex(x16, P[p + ".mlp.fc1.fw"], P[p + ".mlp.fc1.fb"], ops.EPI_BF16_GELU, fold_in=(st, P[p + ".mlp.fc1.fcs"]))
             ops.gemm_ex(hdn, P[p + ".mlp.fc2.w"], P[p + ".mlp.fc2.b"], ops.EPI_F32_ACCUM, hl=hl)
@@ -488,7 +499,6 @@ class Mast3rFull:
         rtok = self._rope(gh, gw)
         D, heads = c["dec_dim"], c["dec_heads"]
         m = npairs * t
-        dev = f1.device
         dt, hdt = self.tdt, self.hdt
         if f1.dtype != dt or f2.dtype != dt:
             raise TypeError(f"encoder features must be {dt} (precision={self.precision!r}), got {f1.dtype}")
@@ -520,21 +530,14 @@ class Mast3rFull:
                                    rope=(rtok, D), pv_bf16=pv)                      # [2,M,2D], k rotated
             # self-attention
             qkv = ops.gemm_grouped2(xn, *W(i, "attn.qkv.w"), *W(i, "attn.qkv.b"), ops.EPI_BF16_ROPE,
-                                    rope=(rtok, 2 * D, D, ops.QK_PRESCALE), pv_bf16=pv).view(2 * m, 3 * D)
-            a = torch.empty((2, m, D), dtype=dt, device=dev)
-            ops.attention(qkv, qkv[:, D:], qkv[:, 2 * D:], a, nbatch=2 * npairs, heads=heads, tq=t, tk=t,
-                          q_row_stride=3 * D, kv_row_stride=3 * D, o_row_stride=D, q_batch_stride=t * 3 * D,
-                          kv_batch_stride=t * 3 * D, o_batch_stride=t * D, prescaled=True, pv_bf16=pv)
+                                    rope=(rtok, 2 * D, D, ops.QK_PRESCALE), pv_bf16=pv)
+            a = self._attn_qkv(qkv, 2 * npairs, t, heads)
             ops.gemm_grouped2(a, *W(i, "attn.proj.w"), *W(i, "attn.proj.b"), ops.EPI_F32_ACCUM, out=x, resid=x)
             # cross-attention
             xn = ops.layernorm_grouped2(x, W(i, "norm2.g")[0], W(i, "norm2.b")[0], W(i, "norm2.g")[1], W(i, "norm2.b")[1], dtype=dt)
             q = ops.gemm_grouped2(xn, *W(i, "cross_attn.projq.w"), *W(i, "cross_attn.projq.b"), ops.EPI_BF16_ROPE,
-                                  rope=(rtok, D, D, ops.QK_PRESCALE)).view(2 * m, D)
-            kvf = kv.view(2 * m, 2 * D)
-            a = torch.empty((2, m, D), dtype=dt, device=dev)
-            ops.attention(q, kvf, kvf[:, D:], a, nbatch=2 * npairs, heads=heads, tq=t, tk=t, q_row_stride=D,
-                          kv_row_stride=2 * D, o_row_stride=D, q_batch_stride=t * D, kv_batch_stride=t * 2 * D,
-                          o_batch_stride=t * D, prescaled=True, pv_bf16=pv)
+                                  rope=(rtok, D, D, ops.QK_PRESCALE))
+            a = self._attn_q_kv(q, kv, 2 * npairs, t, heads)
             ops.gemm_grouped2(a, *W(i, "cross_attn.proj.w"), *W(i, "cross_attn.proj.b"), ops.EPI_F32_ACCUM, out=x, resid=x)
             # MLP
             xn = ops.layernorm_grouped2(x, W(i, "norm3.g")[0], W(i, "norm3.b")[0], W(i, "norm3.g")[1], W(i, "norm3.b")[1], dtype=dt)
@@ -582,19 +585,10 @@ class Mast3rFull:
         for i in range(c["dec_depth"]):
             # cross-attention memory: norm_y of the OTHER view's previous-layer tokens, then the k|v projection
             kv = consume(i, "cross_attn.kv", ops.EPI_BF16_ROPE, rope=(rtok, D), pv_bf16=pv, a_swap=True)   # [2,M,2D], k rotated
-            qkv = consume(i, "attn.qkv", ops.EPI_BF16_ROPE, rope=(rtok, 2 * D, D, ops.QK_PRESCALE), pv_bf16=pv).view(2 * m, 3 * D)
-            a = torch.empty((2, m, D), dtype=dt, device=dev)
-            ops.attention(qkv, qkv[:, D:], qkv[:, 2 * D:], a, nbatch=2 * npairs, heads=heads, tq=t, tk=t,
-                          q_row_stride=3 * D, kv_row_stride=3 * D, o_row_stride=D, q_batch_stride=t * 3 * D,
-                          kv_batch_stride=t * 3 * D, o_batch_stride=t * D, prescaled=True, pv_bf16=pv)
-            produce(i, "attn.proj", a)
-            q = consume(i, "cross_attn.projq", ops.EPI_BF16_ROPE, rope=(rtok, D, D, ops.QK_PRESCALE)).view(2 * m, D)
-            kvf = kv.view(2 * m, 2 * D)
-            a = torch.empty((2, m, D), dtype=dt, device=dev)
-            ops.attention(q, kvf, kvf[:, D:], a, nbatch=2 * npairs, heads=heads, tq=t, tk=t, q_row_stride=D,
-                          kv_row_stride=2 * D, o_row_stride=D, q_batch_stride=t * D, kv_batch_stride=t * 2 * D,
-                          o_batch_stride=t * D, prescaled=True, pv_bf16=pv)
-            produce(i, "cross_attn.proj", a)
+            qkv = consume(i, "attn.qkv", ops.EPI_BF16_ROPE, rope=(rtok, 2 * D, D, ops.QK_PRESCALE), pv_bf16=pv)
+            produce(i, "attn.proj", self._attn_qkv(qkv, 2 * npairs, t, heads))
+            q = consume(i, "cross_attn.projq", ops.EPI_BF16_ROPE, rope=(rtok, D, D, ops.QK_PRESCALE))
+            produce(i, "cross_attn.proj", self._attn_q_kv(q, kv, 2 * npairs, t, heads))
             hdn = consume(i, "mlp.fc1", ops.EPI_BF16_GELU)
             produce(i, "mlp.fc2", hdn)
             layer = i + 1
@@ -610,147 +604,103 @@ class Mast3rFull:
         return taps
 
     # ------------------------------------------------------------------ heads
-    def _rcu(self, x, q):
-        P = self.P
-        c1 = ops.conv3x3(x, P[q + ".conv1.w"], P[q + ".conv1.b"], ops.EPI_BF16_RELU, relu_input=True)   # conv1(relu(x))
-        return ops.conv3x3(c1, P[q + ".conv2.w"], P[q + ".conv2.b"], ops.EPI_BF16_ADD, resid=x)
-
-    def _fusion(self, q, x0, x1=None):
-        """DPT FeatureFusionBlock WITHOUT its trailing x2 upsample: returns the out_conv output at the block's own
-        resolution.  With a skip connection x1, x0 is the previous block's (coarser) output: it is upsampled, cropped
-        to x1's size (odd token grids, oracle/model.py dpt_head: path[:, :, :h, :w]) and added to the refined x1 in one
-        launch (ops.add_upsample2x) - the upsampled map is never materialised."""
-        P = self.P
-        out = x0 if x1 is None else ops.add_upsample2x(x0, self._rcu(x1, q + ".resConfUnit1"))
-        # out_conv is 1x1 and the align_corners bilinear weights sum to one, so conv(upsample(x)) ==
-        # upsample(conv(x)): run the GEMM on the low-resolution map (4x fewer rows); the consumer upsamples.
-        out = self._rcu(out, q + ".resConfUnit2")
-        b, h, w, ch = out.shape
-        return ops.gemm(out.view(-1, ch), P[q + ".out_conv.w"], P[q + ".out_conv.b"], ops.EPI_BF16).view(b, h, w, -1)
-
-    def head(self, hname: str, taps, npairs: int, grid):
-        """taps: 4 [P*T,C] tensors in the head 16-bit type -> dict(pts3d [P,H,W,3], conf [P,H,W], desc [P,H,W,24], desc_conf [P,H,W])."""
-        P, c = self.P, self.cfg
+    def _heads(self, names, taps_per_head, npairs: int, grid):
+        """The DPT head + local-feature head of one head (names = (hname,)) or of both as 2-group launches (blockIdx.y =
+        head: same shapes, different weights).  Every tensor carries `lead` in front: () for one head, (2,) for two - the
+        operators take the second head's weights as w1 / bias1 (None = one group).  taps_per_head: per head, 4 tensors
+        [P*T,C] (head 16-bit type).  Returns one dict(pts3d, conf, desc, desc_conf) per head."""
+        P, ld = self.P, self.cfg["layer_dims"]
         gh, gw = grid
         m = npairs * gh * gw
-        p = hname + ".dpt"
-        ld = c["layer_dims"]
-        dev = taps[0].device
+        G = len(names)
+        lead = (2,) if G == 2 else ()
+        dev = taps_per_head[0][0].device
+        T = [_pair2(a, b) for a, b in zip(*taps_per_head)] if G == 2 else taps_per_head[0]    # [2,M,C]: a view when the halves are adjacent
+        W = lambda s: (P[names[0] + s], P[names[1] + s] if G == 2 else None)
+        flat = lambda x: x.reshape((-1,) + tuple(x.shape[-3:]))                      # heads folded into the batch axis (a view)
+
+        def gem(x, s, epi=ops.EPI_BF16, out=None):
+            (w0, w1), (b0, b1) = W(s + ".w"), W(s + ".b")
+            return ops.gemm_ex(x, w0, b0, epi, out=out, w1=w1, bias1=b1)
+
+        def conv(x, s, epi=ops.EPI_BF16, **kw):
+            (w0, w1), (b0, b1) = W(s + ".w"), W(s + ".b")
+            return ops.conv3x3_ex(x, w0, b0, epi, w1=w1, bias1=b1, **kw)
+
+        def rcu(x, q):
+            c1 = conv(x, q + ".conv1", ops.EPI_BF16_RELU, relu_input=True)           # conv1(relu(x))
+            return conv(c1, q + ".conv2", ops.EPI_BF16_ADD, resid=x)
+
+        def fusion(q, x0, x1=None):
+            """DPT FeatureFusionBlock WITHOUT its trailing x2 upsample: returns the out_conv output at the block's own
+            resolution.  With a skip connection x1, x0 is the previous block's (coarser) output: it is upsampled, cropped
+            to x1's size (odd token grids, oracle/model.py dpt_head: path[:, :, :h, :w]) and added to the refined x1 in one
+            launch (ops.add_upsample2x) - the upsampled map is never materialised."""
+            out = x0
+            if x1 is not None:
+                y = rcu(x1, q + ".resConfUnit1")
+                out = ops.add_upsample2x(flat(x0), flat(y)).view(y.shape)
+            # out_conv is 1x1 and the align_corners bilinear weights sum to one, so conv(upsample(x)) ==
+            # upsample(conv(x)): run the GEMM on the low-resolution map (4x fewer rows); the consumer upsamples.
+            out = rcu(out, q + ".resConfUnit2")
+            return gem(out.view(lead + (-1, out.shape[-1])), q + ".out_conv").view(out.shape[:-1] + (-1,))
+
+        def up2(x):
+            return ops.upsample2x(flat(x)).view(lead + (npairs, 2 * x.shape[-3], 2 * x.shape[-2], x.shape[-1]))
+
+        d = ".dpt"
         # act_postprocess
-        k0 = _ceil64(ld[0])
-        t0 = torch.zeros((m, k0), dtype=self.hdt, device=dev) if k0 != ld[0] else None
-        t0 = ops.gemm(taps[0], P[p + ".act_postprocess.0.0.w"], P[p + ".act_postprocess.0.0.b"], ops.EPI_BF16, out=t0)
-        u0 = ops.gemm(t0, P[p + ".act_postprocess.0.1.w"], P[p + ".act_postprocess.0.1.b"], ops.EPI_BF16)
-        l0 = ops.unshuffle(u0, npairs, gh, gw, 4, ld[0], _ceil64(ld[0]))
-        k1 = _ceil64(ld[1])
-        t1 = torch.zeros((m, k1), dtype=self.hdt, device=dev) if k1 != ld[1] else None
-        t1 = ops.gemm(taps[1], P[p + ".act_postprocess.1.0.w"], P[p + ".act_postprocess.1.0.b"], ops.EPI_BF16, out=t1)
-        u1 = ops.gemm(t1, P[p + ".act_postprocess.1.1.w"], P[p + ".act_postprocess.1.1.b"], ops.EPI_BF16)
-        l1 = ops.unshuffle(u1, npairs, gh, gw, 2, ld[1], _ceil64(ld[1]))
-        l2 = ops.gemm(taps[2], P[p + ".act_postprocess.2.0.w"], P[p + ".act_postprocess.2.0.b"], ops.EPI_BF16)
-        l2 = l2.view(npairs, gh, gw, ld[2])
-        t3 = ops.gemm(taps[3], P[p + ".act_postprocess.3.0.w"], P[p + ".act_postprocess.3.0.b"], ops.EPI_BF16)
-        l3 = ops.conv3x3(t3.view(npairs, gh, gw, ld[3]), P[p + ".act_postprocess.3.1.w"],
-                         P[p + ".act_postprocess.3.1.b"], ops.EPI_BF16, stride=2)
-        rn = [ops.conv3x3(l, P[p + f".scratch.layer_rn.{i}.w"], None, ops.EPI_BF16)
-              for i, l in enumerate((l0, l1, l2, l3))]
-        path = self._fusion(p + ".scratch.refinenet4", rn[3])
-        path = self._fusion(p + ".scratch.refinenet3", path, rn[2])
-        path = self._fusion(p + ".scratch.refinenet2", path, rn[1])
-        path = self._fusion(p + ".scratch.refinenet1", path, rn[0])
+        k0, k1 = _ceil64(ld[0]), _ceil64(ld[1])
+        t0 = gem(T[0], d + ".act_postprocess.0.0", out=torch.zeros(lead + (m, k0), dtype=self.hdt, device=dev) if k0 != ld[0] else None)
+        u0 = gem(t0, d + ".act_postprocess.0.1")
+        l0 = ops.unshuffle(u0.view(G * m, -1), G * npairs, gh, gw, 4, ld[0], k0).view(lead + (npairs, 4 * gh, 4 * gw, k0))
+        t1 = gem(T[1], d + ".act_postprocess.1.0", out=torch.zeros(lead + (m, k1), dtype=self.hdt, device=dev) if k1 != ld[1] else None)
+        u1 = gem(t1, d + ".act_postprocess.1.1")
+        l1 = ops.unshuffle(u1.view(G * m, -1), G * npairs, gh, gw, 2, ld[1], k1).view(lead + (npairs, 2 * gh, 2 * gw, k1))
+        l2 = gem(T[2], d + ".act_postprocess.2.0").view(lead + (npairs, gh, gw, ld[2]))
+        t3 = gem(T[3], d + ".act_postprocess.3.0").view(lead + (npairs, gh, gw, ld[3]))
+        l3 = conv(t3, d + ".act_postprocess.3.1", stride=2)
+        rn = [conv(l, d + f".scratch.layer_rn.{i}") for i, l in enumerate((l0, l1, l2, l3))]
+        path = fusion(d + ".scratch.refinenet4", rn[3])
+        path = fusion(d + ".scratch.refinenet3", path, rn[2])
+        path = fusion(d + ".scratch.refinenet2", path, rn[1])
+        path = fusion(d + ".scratch.refinenet1", path, rn[0])
         if self._direct_head0_ok(path):
             # refinenet1's trailing x2 upsample + head.0 as ONE direct-convolution launch (the 256-channel full-size map is
             # neither written nor gathered nine times)
-            h0 = ops.conv3x3_up_direct(path, P[p + ".head.0.w"], P[p + ".head.0.b"], upsample=True)
+            (w0, w1), (b0, b1) = W(d + ".head.0.w"), W(d + ".head.0.b")
+            h0 = ops.conv3x3_up_direct_ex(path, w0, b0, upsample=True, w1=w1, bias1=b1)
         else:
-            h0 = ops.conv3x3(ops.upsample2x(path), P[p + ".head.0.w"], P[p + ".head.0.b"], ops.EPI_BF16)
-        ch = P[p + ".head.2.w"].shape[0]
-        if ch == 128 and h0.shape[-1] == 128 and P[p + ".head.4.w"].shape == (4, 128):
+            h0 = conv(up2(path), d + ".head.0")
+        (w2, w21), (w4, w41) = W(d + ".head.2.w"), W(d + ".head.4.w")
+        if tuple(w2.shape) == (128, 3, 3, 128) and tuple(w4.shape) == (4, 128):
             # x2 upsample + head.2 conv + ReLU + head.4 1x1 + pointmap post-processing in ONE direct-convolution launch:
             # the full-resolution 128-channel map (537 MB per head at 8 pairs) is never written or read
-            pts, conf = ops.dpt_tail(h0, P[p + ".head.2.w"], P[p + ".head.2.b"], P[p + ".head.4.w"], P[p + ".head.4.b"], upsample=True)
-        else:
-            h0 = ops.upsample2x(h0)
-            h2 = ops.conv3x3(h0, P[p + ".head.2.w"], P[p + ".head.2.b"], ops.EPI_BF16_RELU)
-            b, h, w, ch = h2.shape
-            raw = ops.gemm(h2.view(-1, ch), P[p + ".head.4.w"], P[p + ".head.4.b"], ops.EPI_F32)
-            pts, conf = ops.pts_post(raw.view(b, h, w, 4))
+            (b2, b21), (b4, b41) = W(d + ".head.2.b"), W(d + ".head.4.b")
+            pts, conf = ops.dpt_tail_ex(h0, w2, b2, w4, b4, upsample=True, w1=w21, bias1=b21, w41=w41, b41=b41)
+        else:                                                                        # another tail geometry: the unfused chain
+            h2 = conv(up2(h0), d + ".head.2", ops.EPI_BF16_RELU)
+            raw = gem(h2.view(lead + (-1, h2.shape[-1])), d + ".head.4", ops.EPI_F32)
+            pts, conf = ops.pts_post(raw.view(h2.shape[:-1] + (4,)))
         # local features
-        q = hname + ".head_local_features"
-        cat = ops.concat2(taps[0], taps[3])
-        f = ops.gemm(cat, P[q + ".fc1.w"], P[q + ".fc1.b"], ops.EPI_BF16_GELU)
-        f = ops.gemm(f, P[q + ".fc2.w"], P[q + ".fc2.b"], ops.EPI_BF16)
-        desc, dconf = ops.desc_post(f, npairs, gh * 16, gw * 16, self.desc_dtype)
-        return dict(pts3d=pts, conf=conf, desc=desc, desc_conf=dconf)
+        q = ".head_local_features"
+        cat = ops.concat2(T[0].reshape(G * m, -1), T[3].reshape(G * m, -1)).view(lead + (m, -1))
+        f = gem(gem(cat, q + ".fc1", ops.EPI_BF16_GELU), q + ".fc2")
+        H, Wd = gh * 16, gw * 16
+        desc, dconf = ops.desc_post(f.view(G * m, -1), G * npairs, H, Wd, self.desc_dtype)
+        out = dict(pts3d=pts, conf=conf, desc=desc.view(lead + (npairs, H, Wd, 24)), desc_conf=dconf.view(lead + (npairs, H, Wd)))
+        return (out,) if G == 1 else tuple({k: t[v] for k, t in out.items()} for v in range(2))
 
-    # ------------------------------------------------------------------ both heads as 2-group launches
-    def _rcu2(self, x, q):
-        P, h1, h2 = self.P, "downstream_head1", "downstream_head2"
-        W = lambda s: (P[h1 + q + s], P[h2 + q + s])
-        c1 = ops.conv3x3_grouped2(x, *W(".conv1.w"), *W(".conv1.b"), ops.EPI_BF16_RELU, relu_input=True)   # conv1(relu(x))
-        return ops.conv3x3_grouped2(c1, *W(".conv2.w"), *W(".conv2.b"), ops.EPI_BF16_ADD, resid=x)
-
-    def _fusion2(self, q, x0, x1=None):
-        """`_fusion` for both heads at once: tensors [2 (head), B, h, w, C], weights per head."""
-        P, h1, h2 = self.P, "downstream_head1", "downstream_head2"
-        if x1 is None:
-            out = x0
-        else:
-            y = self._rcu2(x1, q + ".resConfUnit1")
-            out = ops.add_upsample2x(x0.flatten(0, 1), y.flatten(0, 1)).view(y.shape)
-        out = self._rcu2(out, q + ".resConfUnit2")
-        g, b, h, w, ch = out.shape
-        out = ops.gemm_grouped2(out.view(2, -1, ch), P[h1 + q + ".out_conv.w"], P[h2 + q + ".out_conv.w"],
-                                P[h1 + q + ".out_conv.b"], P[h2 + q + ".out_conv.b"], ops.EPI_BF16)
-        return out.view(2, b, h, w, -1)
+    def head(self, hname: str, taps, npairs: int, grid):
+        """taps: 4 [P*T,C] tensors in the head 16-bit type -> dict(pts3d [P,H,W,3], conf [P,H,W], desc [P,H,W,24], desc_conf [P,H,W])."""
+        return self._heads((hname,), (taps,), npairs, grid)[0]
 
     def heads(self, taps1, taps2, npairs: int, grid):
-        """Both heads (DPT + local features) with every operator as ONE 2-group launch (blockIdx.y = head: same
-        shapes, different weights) - the form the decoder already uses.  No side stream: a stream fork here was a
-        second-level fork whenever the caller captured on a forked stream, which segfaults inside ROCm 7.2
-        (tools/incident_r01/nested_capture.py), and the small maps now fill twice the CUs.
-        taps*: 4 tensors [P*T,C] each (head 16-bit type).  Returns (out1, out2) dicts as `head`."""
-        P, c = self.P, self.cfg
-        gh, gw = grid
-        m = npairs * gh * gw
-        h1, h2 = "downstream_head1", "downstream_head2"
-        d = ".dpt"
-        ld = c["layer_dims"]
-        dev = taps1[0].device
-        W = lambda s: (P[h1 + s], P[h2 + s])
-        T = [_pair2(a, b) for a, b in zip(taps1, taps2)]                               # [2, M, C], a view when the halves are adjacent
-        gem = lambda x, s, epi=ops.EPI_BF16, out=None: ops.gemm_grouped2(x, *W(s + ".w"), *W(s + ".b"), epi, out=out)
-        k0, k1 = _ceil64(ld[0]), _ceil64(ld[1])
-        t0 = gem(T[0], d + ".act_postprocess.0.0", out=torch.zeros((2, m, k0), dtype=self.hdt, device=dev) if k0 != ld[0] else None)
-        u0 = gem(t0, d + ".act_postprocess.0.1")
-        l0 = ops.unshuffle(u0.view(2 * m, -1), 2 * npairs, gh, gw, 4, ld[0], k0).view(2, npairs, 4 * gh, 4 * gw, k0)
-        t1 = gem(T[1], d + ".act_postprocess.1.0", out=torch.zeros((2, m, k1), dtype=self.hdt, device=dev) if k1 != ld[1] else None)
-        u1 = gem(t1, d + ".act_postprocess.1.1")
-        l1 = ops.unshuffle(u1.view(2 * m, -1), 2 * npairs, gh, gw, 2, ld[1], k1).view(2, npairs, 2 * gh, 2 * gw, k1)
-        l2 = gem(T[2], d + ".act_postprocess.2.0").view(2, npairs, gh, gw, ld[2])
-        t3 = gem(T[3], d + ".act_postprocess.3.0").view(2, npairs, gh, gw, ld[3])
-        l3 = ops.conv3x3_grouped2(t3, *W(d + ".act_postprocess.3.1.w"), *W(d + ".act_postprocess.3.1.b"), ops.EPI_BF16, stride=2)
-        rn = [ops.conv3x3_grouped2(l, *W(d + f".scratch.layer_rn.{i}.w"), None, None, ops.EPI_BF16)
-              for i, l in enumerate((l0, l1, l2, l3))]
-        path = self._fusion2(d + ".scratch.refinenet4", rn[3])
-        path = self._fusion2(d + ".scratch.refinenet3", path, rn[2])
-        path = self._fusion2(d + ".scratch.refinenet2", path, rn[1])
-        path = self._fusion2(d + ".scratch.refinenet1", path, rn[0])
-        g2, b2, hh, ww, cc = path.shape
-        if self._direct_head0_ok(path):
-            h0 = ops.conv3x3_up_direct_grouped2(path, *W(d + ".head.0.w"), *W(d + ".head.0.b"), upsample=True)
-        else:
-            path = ops.upsample2x(path.view(g2 * b2, hh, ww, cc)).view(g2, b2, 2 * hh, 2 * ww, cc)
-            h0 = ops.conv3x3_grouped2(path, *W(d + ".head.0.w"), *W(d + ".head.0.b"), ops.EPI_BF16)
-        pts, conf = ops.dpt_tail_grouped2(h0, *W(d + ".head.2.w"), *W(d + ".head.2.b"), *W(d + ".head.4.w"), *W(d + ".head.4.b"),
-                                          upsample=True)
-        q = ".head_local_features"
-        cat = ops.concat2(T[0].view(2 * m, -1), T[3].view(2 * m, -1)).view(2, m, -1)
-        f = gem(gem(cat, q + ".fc1", ops.EPI_BF16_GELU), q + ".fc2")
-        desc, dconf = ops.desc_post(f.view(2 * m, -1), 2 * npairs, gh * 16, gw * 16, self.desc_dtype)
-        H, Wd = gh * 16, gw * 16
-        desc, dconf = desc.view(2, npairs, H, Wd, 24), dconf.view(2, npairs, H, Wd)
-        return tuple(dict(pts3d=pts[v], conf=conf[v], desc=desc[v], desc_conf=dconf[v]) for v in range(2))
+        """Both heads (DPT + local features) with every operator as ONE 2-group launch - the form the decoder already uses.
+        No side stream: a stream fork here was a second-level fork whenever the caller captured on a forked stream, which
+        segfaults inside ROCm 7.2 (tools/incident_r01/nested_capture.py), and the small maps now fill
+        twice the CUs.  taps*: 4 tensors [P*T,C] each (head 16-bit type).  Returns (out1, out2) dicts as `head`."""
+        return self._heads(("downstream_head1", "downstream_head2"), (taps1, taps2), npairs, grid)
 
     # ------------------------------------------------------------------ public two-view API
     def reconstruct_batch(self, imgs1: torch.Tensor, imgs2: torch.Tensor):
@@ -767,20 +717,13 @@ class Mast3rFull:
     def decode_heads(self, f1, f2, npairs, grid):
         """Decoder + both heads from cached encoder tokens (bf16 [P*T,1024] each)."""
         taps = self.decode_tokens(f1.reshape(-1, self.embed_dim), f2.reshape(-1, self.embed_dim), npairs, grid)
-        if self._grouped_heads_ok():
-            return self.heads(taps[0], taps[1], npairs, grid)
-        return (self.head("downstream_head1", taps[0], npairs, grid), self.head("downstream_head2", taps[1], npairs, grid))
+        return self.heads(taps[0], taps[1], npairs, grid)
 
     def _direct_head0_ok(self, path) -> bool:
         """The direct head.0 kernel: 256 (or 128) input channels -> 128, output size (twice the input's) a multiple of 16."""
         w = self.P["downstream_head1.dpt.head.0.w"]
         return (os.environ.get("M3_DIRECT_HEAD0", "1") != "0" and w.shape[0] == 128 and w.shape[3] in (128, 256)
                 and (2 * path.shape[-3]) % 16 == 0 and (2 * path.shape[-2]) % 16 == 0)
-
-    def _grouped_heads_ok(self) -> bool:
-        """The 2-group head path needs the public head geometry (128-channel tail, 4 outputs)."""
-        P, p = self.P, "downstream_head1.dpt"
-        return P[p + ".head.2.w"].shape == (128, 3, 3, 128) and P[p + ".head.4.w"].shape == (4, 128)
 
     def reconstruct(self, img1, img2):
         """model.reconstruct(img1, img2) (mast3r_utils.py:281,355): uint8 [H,W,3] x2 -> two dicts with

@@ -132,39 +132,80 @@ def gemm_rope(a, w, bias, rope_tok, rope_cols: int, q_cols: int = 0, q_scale: fl
     return gemm_ex(a, w, bias, EPI_BF16_ROPE, rope=(rope_tok, rope_cols, q_cols, q_scale), pv_bf16=pv_bf16, rope_base=base)
 
 
+def _lead(x, w1, what: str):
+    """Leading axis of a one- or two-group convolution launch: () with w1 None (x [what]), (2,) otherwise (x [2,what])."""
+    lead = () if w1 is None else (2,)
+    if x.dim() != 4 + len(lead) or tuple(x.shape[:len(lead)]) != lead:
+        raise ValueError(f"x must be [{'2,' if lead else ''}{what}], got {tuple(x.shape)}")
+    return lead
+
+
+def _opt(t, dtype, name, shape):
+    return None if t is None else _ffi.check(t, dtype, name, shape)
+
+
+def conv3x3_ex(x, w, bias=None, epi: int = EPI_BF16, stride: int = 1, resid=None, out=None, relu_input: bool = False, direct=None,
+             w1=None, bias1=None):
+    """The 3x3 convolution behind conv3x3 / conv3x3_grouped2: one group (w1 None; x [B,H,W,Cin]) or two (x [2,B,H,W,Cin];
+    group 1 uses w1, bias1), as an implicit GEMM or - `direct` / conv3x3_direct_ok - as the direct kernel."""
+    x = _ffi.check(x, H16, "x")
+    lead = _lead(x, w1, "B,H,W,Cin")
+    g = len(lead) + 1
+    b, h, wd, cin = x.shape[-4:]
+    w = _ffi.check(w, H16, "w", (None, 3, 3, cin))
+    cout = w.shape[0]
+    w1 = _opt(w1, H16, "w1", tuple(w.shape))
+    dt = _same16(x, w, w1)
+    oh, ow = (h + 2 - 3) // stride + 1, (wd + 2 - 3) // stride + 1
+    odt = torch.float32 if epi in _F32_EPIS else x.dtype
+    bias, bias1 = _opt(bias, torch.float32, "bias", (cout,)), _opt(bias1, torch.float32, "bias1", (cout,))
+    resid = _opt(resid, odt, "resid", lead + (b, oh, ow, cout))
+    if out is None and direct is not False and epi in (EPI_BF16, EPI_BF16_RELU, EPI_BF16_ADD) and (direct or conv3x3_direct_ok(x, cout, stride)):
+        return _conv3x3_direct(x, w, w1, bias, bias1, epi, resid, relu_input)      # same bits as the implicit-GEMM form
+    if out is None:
+        out = torch.empty(lead + (b, oh, ow, cout), dtype=odt, device=x.device)
+    ws_bytes = g * int(_ffi.lib().m3_conv3x3_splitk_bytes(b, h, wd, cin, cout, stride))
+    # fp32 partial planes of the split-K path, from torch's caching allocator: stream-ordered, capture-safe
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device) if ws_bytes > 0 else None
+    e0 = _prof_begin()
+    _ffi.call("m3_conv3x3_grouped2_dt", _ffi.ptr(x), _ffi.ptr(w), _ffi.ptr(w1), _ffi.ptr(bias), _ffi.ptr(bias1), _ffi.ptr(out),
+              _ffi.ptr(resid), _ffi.ptr(zero_page(x.device)), b, h, wd, cin, cout, stride,
+              epi | (EPI_INPUT_RELU if relu_input else 0), _ffi.ptr(ws), ws_bytes, dt, _ffi.stream_ptr())
+    _prof_end(e0, "conv3x3", 2.0 * g * b * oh * ow * cout * 9 * cin,
+              g * (2.0 * (b * h * wd * cin + cout * 9 * cin) + out.element_size() * b * oh * ow * cout * (1 if resid is None else 2)),
+              f"conv3x3{' x2' if g == 2 else ''} {b}x{h}x{wd} {cin}->{cout} s{stride} epi{epi} splitk_ws={ws_bytes}")
+    return out
+
+
+def _conv3x3_direct(x, w0, w1, b0, b1, epi, resid, relu_input):
+    grouped = x.dim() == 5
+    b, h, wd, cin = x.shape[-4:]
+    cout = w0.shape[0]
+    dt = _same16(x, w0, w1)
+    out = torch.empty(tuple(x.shape[:-1]) + (cout,), dtype=x.dtype, device=x.device)
+    e0 = _prof_begin()
+    _ffi.call("m3_conv3x3_direct_grouped2_dt", _ffi.ptr(x), _ffi.ptr(w0), _ffi.ptr(w1), _ffi.ptr(b0), _ffi.ptr(b1), _ffi.ptr(out),
+              _ffi.ptr(resid), _ffi.ptr(zero_page(x.device)), b, h, wd, cin, cout, epi | (EPI_INPUT_RELU if relu_input else 0), dt,
+              _ffi.stream_ptr())
+    g = 2 if grouped else 1
+    _prof_end(e0, "conv_direct", 2.0 * g * b * h * wd * cout * 9 * cin,
+              g * (2.0 * (b * h * wd * cin + cout * 9 * cin) + 2.0 * b * h * wd * cout * (1 if resid is None else 2)),
+              f"conv3x3 direct{' x2' if grouped else ''} {b}x{h}x{wd} {cin}->{cout} epi{epi}")
+    return out
+
+
 def conv3x3(x: torch.Tensor, w: torch.Tensor, bias=None, epi: int = EPI_BF16, stride: int = 1, resid=None, out=None,
             relu_input: bool = False, direct=None):
     """x NHWC bf16 [B,H,W,Cin], w bf16 [Cout,3,3,Cin] -> NHWC [B,OH,OW,Cout], padding 1.  relu_input: conv(relu(x)).
     direct: None = the direct-convolution kernel when its grid fills the chip (conv3x3_direct_ok), True / False force
     one form - both return the same bits."""
-    x = _ffi.check(x, H16, "x")
-    w = _ffi.check(w, H16, "w")
-    dt = _same16(x, w)
-    b, h, wd, cin = x.shape
-    cout = w.shape[0]
-    if tuple(w.shape[1:]) != (3, 3, cin):
-        raise ValueError(f"weight must be [Cout,3,3,{cin}], got {tuple(w.shape)}")
-    oh, ow = (h + 2 - 3) // stride + 1, (wd + 2 - 3) // stride + 1
-    odt = torch.float32 if epi in _F32_EPIS else x.dtype
-    if bias is not None:
-        bias = _ffi.check(bias, torch.float32, "bias", (cout,))
-    if resid is not None:
-        resid = _ffi.check(resid, odt, "resid", (b, oh, ow, cout))
-    if out is None and direct is not False and epi in (EPI_BF16, EPI_BF16_RELU, EPI_BF16_ADD) and (direct or conv3x3_direct_ok(x, cout, stride)):
-        return _conv3x3_direct(x, w, None, bias, None, epi, resid, relu_input)      # same bits as the implicit-GEMM form
-    if out is None:
-        out = torch.empty((b, oh, ow, cout), dtype=odt, device=x.device)
-    ws_bytes = int(_ffi.lib().m3_conv3x3_splitk_bytes(b, h, wd, cin, cout, stride))
-    # fp32 partial planes of the split-K path, from torch's caching allocator: stream-ordered, capture-safe
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device) if ws_bytes > 0 else None
-    e0 = _prof_begin()
-    _ffi.call("m3_conv3x3_dt", _ffi.ptr(x), _ffi.ptr(w), _ffi.ptr(bias), _ffi.ptr(out), _ffi.ptr(resid),
-              _ffi.ptr(zero_page(x.device)), b, h, wd, cin, cout, stride, epi | (EPI_INPUT_RELU if relu_input else 0),
-              _ffi.ptr(ws), ws_bytes, dt, _ffi.stream_ptr())
-    _prof_end(e0, "conv3x3", 2.0 * b * oh * ow * cout * 9 * cin,
-              2.0 * (b * h * wd * cin + cout * 9 * cin) + out.element_size() * b * oh * ow * cout * (1 if resid is None else 2),
-              f"conv3x3 {b}x{h}x{wd} {cin}->{cout} s{stride} epi{epi} splitk_ws={ws_bytes}")
-    return out
+    return conv3x3_ex(x, w, bias, epi, stride, resid, out, relu_input, direct)
+
+
+def conv3x3_grouped2(x, w0, w1, b0, b1, epi: int = EPI_BF16, stride: int = 1, resid=None, relu_input: bool = False, direct=None):
+    """Two same-shape 3x3 convolutions in one launch (the two DPT heads): x NHWC [2,B,H,W,Cin], group g uses
+    (w_g [Cout,3,3,Cin], b_g) -> [2,B,OH,OW,Cout]."""
+    return conv3x3_ex(x, w0, b0, epi, stride, resid, None, relu_input, direct, w1=_ffi.check(w1, H16, "w1"), bias1=b1)
 
 
 def conv3x3_relu_head4(x: torch.Tensor, w: torch.Tensor, bias, w4: torch.Tensor, b4: torch.Tensor):
@@ -188,36 +229,6 @@ def conv3x3_relu_head4(x: torch.Tensor, w: torch.Tensor, bias, w4: torch.Tensor,
     return pts, conf
 
 
-def conv3x3_grouped2(x, w0, w1, b0, b1, epi: int = EPI_BF16, stride: int = 1, resid=None, relu_input: bool = False, direct=None):
-    """Two same-shape 3x3 convolutions in one launch (the two DPT heads): x NHWC [2,B,H,W,Cin], group g uses
-    (w_g [Cout,3,3,Cin], b_g) -> [2,B,OH,OW,Cout]."""
-    x = _ffi.check(x, H16, "x")
-    if x.dim() != 5 or x.shape[0] != 2:
-        raise ValueError(f"x must be [2,B,H,W,Cin], got {tuple(x.shape)}")
-    _, b, h, wd, cin = x.shape
-    w0 = _ffi.check(w0, H16, "w0", (None, 3, 3, cin))
-    w1 = _ffi.check(w1, H16, "w1", tuple(w0.shape))
-    dt = _same16(x, w0, w1)
-    cout = w0.shape[0]
-    oh, ow = (h + 2 - 3) // stride + 1, (wd + 2 - 3) // stride + 1
-    odt = torch.float32 if epi in _F32_EPIS else x.dtype
-    if resid is not None:
-        resid = _ffi.check(resid, odt, "resid", (2, b, oh, ow, cout))
-    if direct is not False and epi in (EPI_BF16, EPI_BF16_RELU, EPI_BF16_ADD) and (direct or conv3x3_direct_ok(x, cout, stride)):
-        return _conv3x3_direct(x, w0, w1, b0, b1, epi, resid, relu_input)
-    out = torch.empty((2, b, oh, ow, cout), dtype=odt, device=x.device)
-    ws_bytes = 2 * int(_ffi.lib().m3_conv3x3_splitk_bytes(b, h, wd, cin, cout, stride))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device) if ws_bytes > 0 else None
-    e0 = _prof_begin()
-    _ffi.call("m3_conv3x3_grouped2_dt", _ffi.ptr(x), _ffi.ptr(w0), _ffi.ptr(w1), _ffi.ptr(b0), _ffi.ptr(b1), _ffi.ptr(out),
-              _ffi.ptr(resid), _ffi.ptr(zero_page(x.device)), b, h, wd, cin, cout, stride,
-              epi | (EPI_INPUT_RELU if relu_input else 0), _ffi.ptr(ws), ws_bytes, dt, _ffi.stream_ptr())
-    _prof_end(e0, "conv3x3", 4.0 * b * oh * ow * cout * 9 * cin,
-              2.0 * (2.0 * (b * h * wd * cin + cout * 9 * cin) + out.element_size() * b * oh * ow * cout * (1 if resid is None else 2)),
-              f"conv3x3 x2 {b}x{h}x{wd} {cin}->{cout} s{stride} epi{epi} splitk_ws={ws_bytes}")
-    return out
-
-
 DIRECT_CONV_MIN_WGS = None     # direct convolution once its grid fills the chip (one workgroup per CU); same bits either way.
                                # None: the device's CU count (m3_device_cu_count, 256 on an MI355X); an int overrides it
 
@@ -237,105 +248,72 @@ def conv3x3_direct_ok(x, cout: int, stride: int = 1) -> bool:
     return (h // 16) * ((w + 31) // 32) * b * (cout // 128) * g >= _direct_conv_min_wgs()
 
 
-def _conv3x3_direct(x, w0, w1, b0, b1, epi, resid, relu_input):
-    grouped = x.dim() == 5
-    b, h, wd, cin = x.shape[-4:]
-    cout = w0.shape[0]
-    dt = _same16(x, w0, w1)
-    out = torch.empty(tuple(x.shape[:-1]) + (cout,), dtype=x.dtype, device=x.device)
-    e0 = _prof_begin()
-    _ffi.call("m3_conv3x3_direct_grouped2_dt", _ffi.ptr(x), _ffi.ptr(w0), _ffi.ptr(w1), _ffi.ptr(b0), _ffi.ptr(b1), _ffi.ptr(out),
-              _ffi.ptr(resid), _ffi.ptr(zero_page(x.device)), b, h, wd, cin, cout, epi | (EPI_INPUT_RELU if relu_input else 0), dt,
-              _ffi.stream_ptr())
-    g = 2 if grouped else 1
-    _prof_end(e0, "conv_direct", 2.0 * g * b * h * wd * cout * 9 * cin,
-              g * (2.0 * (b * h * wd * cin + cout * 9 * cin) + 2.0 * b * h * wd * cout * (1 if resid is None else 2)),
-              f"conv3x3 direct{' x2' if grouped else ''} {b}x{h}x{wd} {cin}->{cout} epi{epi}")
-    return out
-
-
-def dpt_tail_grouped2(x, w0, w1, b0, b1, w40, w41, b40, b41, upsample: bool = True):
-    """dpt_tail for both heads in one launch: x [2,B,h,w,128] -> (pts [2,B,H,W,3], conf [2,B,H,W])."""
+def conv3x3_up_direct_ex(x, w, bias, upsample: bool = True, w1=None, bias1=None):
+    """The launch behind conv3x3_up_direct / conv3x3_up_direct_grouped2: one head (w1 None) or both."""
     x = _ffi.check(x, H16, "x")
-    if x.dim() != 5 or x.shape[0] != 2 or x.shape[-1] != 128:
-        raise ValueError(f"x must be [2,B,h,w,128], got {tuple(x.shape)}")
-    _, b, ih, iw, _ = x.shape
-    ws = [_ffi.check(w, H16, "w", (128, 3, 3, 128)) for w in (w0, w1)]
-    w4s = [_ffi.check(w, H16, "w4", (4, 128)) for w in (w40, w41)]
-    dt = _same16(x, *ws, *w4s)
+    lead = _lead(x, w1, "B,h,w,Cin")
+    g = len(lead) + 1
+    b, ih, iw, cin = x.shape[-4:]
+    w, w1 = _ffi.check(w, H16, "w", (128, 3, 3, cin)), _opt(w1, H16, "w1", (128, 3, 3, cin))
+    dt = _same16(x, w, w1)
+    bias, bias1 = _opt(bias, torch.float32, "bias", (128,)), _opt(bias1, torch.float32, "bias1", (128,))
     h, wd = (2 * ih, 2 * iw) if upsample else (ih, iw)
-    pts = torch.empty((2, b, h, wd, 3), dtype=torch.float32, device=x.device)
-    conf = torch.empty((2, b, h, wd), dtype=torch.float32, device=x.device)
+    out = torch.empty(lead + (b, h, wd, 128), dtype=x.dtype, device=x.device)
     e0 = _prof_begin()
-    _ffi.call("m3_dpt_tail_grouped2_dt", _ffi.ptr(x), _ffi.ptr(ws[0]), _ffi.ptr(ws[1]), _ffi.ptr(b0), _ffi.ptr(b1),
-              _ffi.ptr(w4s[0]), _ffi.ptr(w4s[1]), _ffi.ptr(b40), _ffi.ptr(b41), _ffi.ptr(pts), _ffi.ptr(conf),
-              _ffi.ptr(zero_page(x.device)), b, h, wd, 1 if upsample else 0, dt, _ffi.stream_ptr())
-    _prof_end(e0, "conv_tail", 4.0 * b * h * wd * 128 * (9 * 128 + 4), 2.0 * (2.0 * (b * ih * iw * 128 + 128 * 9 * 128) + 16.0 * b * h * wd),
-              f"dpt_tail x2 {b}x{h}x{wd} 128->128->4 upsample={upsample}")
-    return pts, conf
+    _ffi.call("m3_conv3x3_up_direct_grouped2_dt", _ffi.ptr(x), _ffi.ptr(w), _ffi.ptr(w1), _ffi.ptr(bias), _ffi.ptr(bias1), _ffi.ptr(out),
+              _ffi.ptr(zero_page(x.device)), b, h, wd, cin, 1 if upsample else 0, dt, _ffi.stream_ptr())
+    _prof_end(e0, "conv_direct", 2.0 * g * b * h * wd * 128 * 9 * cin, 2.0 * g * (b * ih * iw * cin + 128 * 9 * cin + b * h * wd * 128),
+              f"conv3x3_up_direct{' x2' if g == 2 else ''} {b}x{h}x{wd} {cin}->128 upsample={upsample}")
+    return out
 
 
 def conv3x3_up_direct(x, w, bias, upsample: bool = True):
     """Direct 3x3 convolution to 128 channels with the x2 bilinear (align_corners) upsample of its input fused in
     (DPT head.0): x NHWC [B,h,w,Cin] (Cin 256 or 128) -> [B,H,W,128], H = 2h with the upsample.  The upsampled map is
     never written."""
-    x = _ffi.check(x, H16, "x")
-    b, ih, iw, cin = x.shape
-    w = _ffi.check(w, H16, "w", (128, 3, 3, cin))
-    dt = _same16(x, w)
-    if bias is not None:
-        bias = _ffi.check(bias, torch.float32, "bias", (128,))
-    h, wd = (2 * ih, 2 * iw) if upsample else (ih, iw)
-    out = torch.empty((b, h, wd, 128), dtype=x.dtype, device=x.device)
-    e0 = _prof_begin()
-    _ffi.call("m3_conv3x3_up_direct_dt", _ffi.ptr(x), _ffi.ptr(w), _ffi.ptr(bias), _ffi.ptr(out), _ffi.ptr(zero_page(x.device)),
-              b, h, wd, cin, 1 if upsample else 0, dt, _ffi.stream_ptr())
-    _prof_end(e0, "conv_direct", 2.0 * b * h * wd * 128 * 9 * cin, 2.0 * (b * ih * iw * cin + 128 * 9 * cin + b * h * wd * 128),
-              f"conv3x3_up_direct {b}x{h}x{wd} {cin}->128 upsample={upsample}")
-    return out
+    return conv3x3_up_direct_ex(x, w, bias, upsample)
 
 
 def conv3x3_up_direct_grouped2(x, w0, w1, b0, b1, upsample: bool = True):
     """conv3x3_up_direct for both heads in one launch: x [2,B,h,w,Cin] -> [2,B,H,W,128]; head g uses (w_g, b_g)."""
+    return conv3x3_up_direct_ex(x, w0, b0, upsample, w1=_ffi.check(w1, H16, "w1"), bias1=b1)
+
+
+def dpt_tail_ex(x, w, bias, w4, b4, upsample: bool = True, w1=None, bias1=None, w41=None, b41=None):
+    """The launch behind dpt_tail / dpt_tail_grouped2: one head (w1, w41 None) or both (head 1 uses w1, bias1, w41, b41)."""
     x = _ffi.check(x, H16, "x")
-    if x.dim() != 5 or x.shape[0] != 2:
-        raise ValueError(f"x must be [2,B,h,w,Cin], got {tuple(x.shape)}")
-    _, b, ih, iw, cin = x.shape
-    w0 = _ffi.check(w0, H16, "w0", (128, 3, 3, cin))
-    w1 = _ffi.check(w1, H16, "w1", (128, 3, 3, cin))
-    dt = _same16(x, w0, w1)
+    lead = _lead(x, w1, "B,h,w,128")
+    g = len(lead) + 1
+    b, ih, iw, cin = x.shape[-4:]
+    if cin != 128:
+        raise ValueError(f"dpt_tail needs 128 input channels, got {cin}")
+    w, w4 = _ffi.check(w, H16, "w", (128, 3, 3, 128)), _ffi.check(w4, H16, "w4", (4, 128))
+    b4, bias = _ffi.check(b4, torch.float32, "b4", (4,)), _opt(bias, torch.float32, "bias", (128,))
+    if g == 2:
+        w1, w41 = _ffi.check(w1, H16, "w1", (128, 3, 3, 128)), _ffi.check(w41, H16, "w41", (4, 128))
+        b41, bias1 = _ffi.check(b41, torch.float32, "b41", (4,)), _opt(bias1, torch.float32, "bias1", (128,))
+    dt = _same16(x, w, w4, w1, w41)
     h, wd = (2 * ih, 2 * iw) if upsample else (ih, iw)
-    out = torch.empty((2, b, h, wd, 128), dtype=x.dtype, device=x.device)
+    pts = torch.empty(lead + (b, h, wd, 3), dtype=torch.float32, device=x.device)
+    conf = torch.empty(lead + (b, h, wd), dtype=torch.float32, device=x.device)
     e0 = _prof_begin()
-    _ffi.call("m3_conv3x3_up_direct_grouped2_dt", _ffi.ptr(x), _ffi.ptr(w0), _ffi.ptr(w1), _ffi.ptr(b0), _ffi.ptr(b1), _ffi.ptr(out),
-              _ffi.ptr(zero_page(x.device)), b, h, wd, cin, 1 if upsample else 0, dt, _ffi.stream_ptr())
-    _prof_end(e0, "conv_direct", 4.0 * b * h * wd * 128 * 9 * cin, 4.0 * (b * ih * iw * cin + 128 * 9 * cin + b * h * wd * 128),
-              f"conv3x3_up_direct x2 {b}x{h}x{wd} {cin}->128 upsample={upsample}")
-    return out
+    _ffi.call("m3_dpt_tail_grouped2_dt", _ffi.ptr(x), _ffi.ptr(w), _ffi.ptr(w1), _ffi.ptr(bias), _ffi.ptr(bias1), _ffi.ptr(w4),
+              _ffi.ptr(w41), _ffi.ptr(b4), _ffi.ptr(b41), _ffi.ptr(pts), _ffi.ptr(conf), _ffi.ptr(zero_page(x.device)), b, h, wd,
+              1 if upsample else 0, dt, _ffi.stream_ptr())
+    _prof_end(e0, "conv_tail", 2.0 * g * b * h * wd * 128 * (9 * 128 + 4), g * (2.0 * (b * ih * iw * 128 + 128 * 9 * 128) + 16.0 * b * h * wd),
+              f"dpt_tail{' x2' if g == 2 else ''} {b}x{h}x{wd} 128->128->4 upsample={upsample}")
+    return pts, conf
 
 
 def dpt_tail(x: torch.Tensor, w: torch.Tensor, bias, w4: torch.Tensor, b4: torch.Tensor, upsample: bool = True):
     """DPT tail as one direct-convolution launch: [x2 bilinear upsample of x] -> conv3x3 128->128 + ReLU -> 1x1 -> 4
     -> (pts3d [B,H,W,3], conf [B,H,W]) f32.  x NHWC [B,H/2,W/2,128] (upsample) or [B,H,W,128]; 16-bit dtype."""
-    x = _ffi.check(x, H16, "x")
-    b, ih, iw, cin = x.shape
-    if cin != 128:
-        raise ValueError(f"dpt_tail needs 128 input channels, got {cin}")
-    w = _ffi.check(w, H16, "w", (128, 3, 3, 128))
-    w4 = _ffi.check(w4, H16, "w4", (4, 128))
-    b4 = _ffi.check(b4, torch.float32, "b4", (4,))
-    dt = _same16(x, w, w4)
-    if bias is not None:
-        bias = _ffi.check(bias, torch.float32, "bias", (128,))
-    h, wd = (2 * ih, 2 * iw) if upsample else (ih, iw)
-    pts = torch.empty((b, h, wd, 3), dtype=torch.float32, device=x.device)
-    conf = torch.empty((b, h, wd), dtype=torch.float32, device=x.device)
-    e0 = _prof_begin()
-    _ffi.call("m3_dpt_tail_dt", _ffi.ptr(x), _ffi.ptr(w), _ffi.ptr(bias), _ffi.ptr(w4), _ffi.ptr(b4), _ffi.ptr(pts),
-              _ffi.ptr(conf), _ffi.ptr(zero_page(x.device)), b, h, wd, 1 if upsample else 0, dt, _ffi.stream_ptr())
-    _prof_end(e0, "conv_tail", 2.0 * b * h * wd * 128 * (9 * 128 + 4), 2.0 * (b * ih * iw * 128 + 128 * 9 * 128) + 16.0 * b * h * wd,
-              f"dpt_tail {b}x{h}x{wd} 128->128->4 upsample={upsample}")
-    return pts, conf
+    return dpt_tail_ex(x, w, bias, w4, b4, upsample)
+
+
+def dpt_tail_grouped2(x, w0, w1, b0, b1, w40, w41, b40, b41, upsample: bool = True):
+    """dpt_tail for both heads in one launch: x [2,B,h,w,128] -> (pts [2,B,H,W,3], conf [2,B,H,W])."""
+    return dpt_tail_ex(x, w0, b0, w40, b40, upsample, w1=_ffi.check(w1, H16, "w1"), bias1=b1, w41=w41, b41=b41)
 
 
 def attention(q, k, v, out, *, nbatch, heads, tq, tk, q_row_stride, kv_row_stride, o_row_stride,

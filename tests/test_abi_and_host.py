@@ -25,11 +25,13 @@ def built_lib():
 
 
 # removed in ABI 3000: the dense GEMM forms other than m3_gemm_ex (and the per-token RoPE table they took), and the
-# dtype-less aliases of the _dt operators
+# dtype-less aliases of the _dt operators; in ABI 4000: the one-group convolution entry points (the *_grouped2_dt forms take
+# W1 == NULL for one group)
 RETIRED = ("m3_gemm_dt", "m3_gemm_bf16", "m3_gemm_rope_dt", "m3_gemm_rope_pos_dt", "m3_gemm_bf16_rope", "m3_gemm_grouped2_dt",
            "m3_gemm_grouped2_rope_pos_dt", "m3_gemm_bf16_grouped2", "m3_add_bf16", "m3_attention_bf16", "m3_rope2d_bf16",
            "m3_conv3x3_bf16", "m3_conv3x3_relu_head4", "m3_desc_post", "m3_f32_to_bf16", "m3_layernorm_bf16",
-           "m3_layernorm_bf16_grouped2", "m3_patchify16", "m3_upsample2x_bf16")
+           "m3_layernorm_bf16_grouped2", "m3_patchify16", "m3_upsample2x_bf16",
+           "m3_conv3x3_dt", "m3_dpt_tail_dt", "m3_conv3x3_up_direct_dt")
 
 
 def test_every_declared_symbol_is_exported(built_lib):
@@ -37,7 +39,7 @@ def test_every_declared_symbol_is_exported(built_lib):
     assert len(names) >= 18
     for n in names:
         assert hasattr(built_lib, n), f"{n} declared in include/ but not exported"
-    assert len(set(RETIRED)) == 19
+    assert len(set(RETIRED)) == 22
     for n in RETIRED:
         assert n not in names, f"{n} is retired but still declared in include/"
         assert not hasattr(built_lib, n), f"{n} is retired but still exported"
@@ -45,7 +47,7 @@ def test_every_declared_symbol_is_exported(built_lib):
 
 def test_metadata_entry_points(built_lib):
     L = _ffi.lib()
-    assert L.m3_abi_version() == 3000          # exact: a signature change must bump it (include/m3slam.h)
+    assert L.m3_abi_version() == 4000          # exact: a signature change must bump it (include/m3slam.h)
     assert L.m3_chol_ws_doubles(1785) == 1 + 1785 + 28 * (2 * 64 * 64 + 1) and L.m3_chol_ws_doubles(7) == 1 + 7 + 2 * 4096 + 1
     assert L.m3_status_string(0) == b"ok"
     assert b"invalid" in L.m3_status_string(-1)

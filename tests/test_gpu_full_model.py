@@ -342,6 +342,68 @@ def test_grouped_heads_equal_separate_heads(tiny, dev):
             assert torch.equal(o_main[v][k], e_main[v][k]) and torch.equal(o_side[v][k], e_side[v][k])
 
 
+_LAST64 = {}
+
+
+def _last64():
+    """dict(TINY_CFG, last_dim=64): head.2 is 128 -> 64 channels, so the fused tail kernel (128 -> 128 -> 4) does not apply.
+    Weights, one 64 x 96 pair and its fp32 oracle outputs, computed once per module run."""
+    if not _LAST64:
+        cfg = dict(M.TINY_CFG, last_dim=64)
+        w = M.init_random_weights(cfg, seed=1)
+        im1, im2 = _pair(64, 96, 0)
+        with torch.no_grad():
+            ref = OM.reconstruct(w, torch.from_numpy(im1), torch.from_numpy(im2), cfg)
+        _LAST64.update(cfg=cfg, w=w, im1=im1, im2=im2, ref=ref)
+    return _LAST64
+
+
+@pytest.mark.parametrize("prec", ["fp16", "bf16"])
+def test_heads_with_another_tail_geometry_one_and_two_groups(dev, monkeypatch, prec):
+    """A head whose tail is not the public 128 -> 128 -> 4 (last_dim = 64: head.2.w is [64,3,3,128]) takes the unfused tail
+    (upsample2x -> conv3x3 + ReLU -> gemm F32 -> pts_post) in the ONE head implementation, for one group and for two: at
+    64 x 96 (the smallest non-square size whose maps are multiples of 16 where the direct kernels need it)
+      * Mast3rFull.heads returns the bits of two Mast3rFull.head calls, for all four outputs;
+      * reconstruct_batch runs the 2-group path (every profiled convolution is a 2-group launch, none is the fused tail)
+        and returns those bits too;
+      * the same with M3_DIRECT_HEAD0=0 (read per call), i.e. head.0 as upsample2x + conv3x3 for both group counts;
+      * pair 0's pts3d / conf are within test_full_depth_network_vs_cpu_oracle's tolerance for the precision (FULL_TOL) of
+        the fp32 oracle.  The unfused tail rounds the 64-channel ReLU map to 16 bits once more than the fused one
+        (include/m3slam_model.h, m3_conv3x3_relu_head4_dt)."""
+    from mast3r_slam import ops
+    L = _last64()
+    assert L["w"]["downstream_head1.dpt.head.2.weight"].shape == (64, 128, 3, 3)
+    net = M.Mast3rFull(weights=L["w"], cfg=L["cfg"], device=dev, precision=prec)
+    assert not hasattr(net, "_grouped_heads_ok")
+    im1, im2 = L["im1"], L["im2"]
+    keys = ("pts3d", "conf", "desc", "desc_conf")
+    for head0 in ("1", "0"):
+        monkeypatch.setenv("M3_DIRECT_HEAD0", head0)
+        tok, grid = net.encode_tokens(net._as_images(im1), net._as_images(im2))
+        m = grid[0] * grid[1]
+        taps = net.decode_tokens(tok[:m], tok[m:], 1, grid)
+        g = net.heads(taps[0], taps[1], 1, grid)
+        s = net.head("downstream_head1", taps[0], 1, grid), net.head("downstream_head2", taps[1], 1, grid)
+        ops.PROFILE, ops.PROFILE_SHAPES = [], []
+        try:
+            o = net.reconstruct_batch(im1, im2)
+            torch.cuda.synchronize()
+            convs = [d for k, d in ops.PROFILE_SHAPES if k.startswith("conv")]
+        finally:
+            ops.PROFILE, ops.PROFILE_SHAPES = None, None
+        assert convs and all(" x2 " in d for d in convs) and not any(d.startswith("dpt_tail") for d in convs), convs
+        assert any(d.startswith("conv3x3_up_direct") for d in convs) == (head0 == "1"), convs
+        for v in range(2):
+            assert o[v]["pts3d"].shape == (1, 64, 96, 3)
+            for k in keys:
+                assert torch.equal(g[v][k], s[v][k]), (head0, v, k)
+                assert torch.equal(o[v][k], g[v][k]), (head0, v, k)
+            errs = {k: _rel(o[v][k][0], L["ref"][v][k][0]) for k in ("pts3d", "conf")}
+            print(f"\nlast_dim=64 {prec} M3_DIRECT_HEAD0={head0} view {v + 1} rel-L2 vs fp32 oracle", {k: f"{e:.2e}" for k, e in errs.items()})
+            for k, e in errs.items():
+                assert e < FULL_TOL[prec][k], (head0, v, k, errs)
+
+
 def test_fp16_features_through_the_operator_api(tiny, dev):
     """BASELINE configs[4] "fp16 features": a model built with features="fp16" emits half descriptors (the fp32 value
     rounded once); the symmetric match operator on them equals the numpy oracle matcher run on the half-rounded

@@ -631,7 +631,7 @@ def test_small_tile_gemm_is_race_free_at_high_occupancy(dev, shape):
 @pytest.mark.parametrize("upsample", [False, True])
 @pytest.mark.parametrize("bhw", [(2, 32, 48), (1, 64, 64), (3, 16, 16), (1, 48, 80)])
 def test_dpt_tail_direct_convolution(dev, dt, upsample, bhw):
-    """m3_dpt_tail_dt (x2 upsample fused into the LDS halo staging + conv3x3 + ReLU + 1x1 + pointmap post-processing)
+    """m3_dpt_tail_grouped2_dt (x2 upsample fused into the LDS halo staging + conv3x3 + ReLU + 1x1 + pointmap post-processing)
     against the separate operators (k_upsample2x -> m3_conv3x3_relu_head4_dt: same 16-bit rounding of the upsampled map,
     fp32 summation order differs) and against a plain torch fp32 chain."""
     b, h, w = bhw                                                     # OUTPUT size
@@ -689,7 +689,7 @@ def test_conv3x3_with_relu_on_its_input_fragments(dev, dt, bhw_c):
 @pytest.mark.parametrize("bhw_ci_co", [(2, 128, 128, 256, 256), (3, 64, 64, 256, 256), (1, 48, 80, 128, 256), (2, 16, 32, 256, 128)])
 def test_direct_convolution_returns_the_bits_of_the_implicit_gemm(dev, dt, bhw_ci_co):
     """m3_conv3x3_direct_grouped2_dt (the DPT residual units at 128 x 128 / 64 x 64 as a direct convolution: LDS halo,
-    64-channel slices, output channels split over blockIdx.z) against m3_conv3x3_dt on the same operands: BIT-identical for
+    64-channel slices, output channels split over blockIdx.z) against m3_conv3x3_grouped2_dt on the same operands: BIT-identical for
     every epilogue (plain, ReLU, residual add with one rounding), with and without ReLU on the input, single and 2-group -
     both forms walk K as (channel slice, tap, k-step).  The dispatcher may therefore choose by problem size without
     breaking "a pair gives the same bits alone or in a batch"."""
@@ -728,7 +728,7 @@ def test_direct_convolution_returns_the_bits_of_the_implicit_gemm(dev, dt, bhw_c
 @pytest.mark.parametrize("upsample", [True, False])
 @pytest.mark.parametrize("bhw", [(2, 32, 48), (1, 64, 64), (3, 16, 16), (1, 48, 80)])
 def test_head0_direct_convolution_with_fused_upsample(dev, dt, cin, upsample, bhw):
-    """m3_conv3x3_up_direct_dt (DPT head.0 with refinenet1's x2 upsample fused into the LDS halo staging, four 64-channel
+    """m3_conv3x3_up_direct_grouped2_dt (DPT head.0 with refinenet1's x2 upsample fused into the LDS halo staging, four 64-channel
     slices, LDS-transposed 16-bit output) against the operators it replaces (k_upsample2x -> implicit-GEMM m3_conv3x3:
     same 16-bit rounding of the upsampled map, fp32 summation order differs) and against a plain torch fp32 chain; the
     2-group launch equals two single launches bit for bit.  Sizes: multiple tiles, a single tile, W = 16 (mod 32)."""

@@ -176,7 +176,7 @@ def test_symbols_are_declared_and_re_exported():
 
 def test_entry_points_validate_before_any_device_call():
     L = _ffi.lib()
-    assert L.m3_abi_version() == 3000                                        # symbols were added, nothing changed
+    assert L.m3_abi_version() == 4000                                        # symbols were added, nothing changed
     assert L.m3_map_export_ws_bytes(256, 512 * 512) == (4 + 256 * 256) * 4 and L.m3_map_export_ws_bytes(1, 3) == 32
     assert L.m3_map_export_ws_bytes(0, 4) == 0 and L.m3_map_export_ws_bytes(4, 0) == 0
     assert L.m3_map_export_ws_bytes(1 << 16, 1 << 16) == 0                  # 2^32 points: beyond the int32 offsets

@@ -161,7 +161,7 @@ def test_preprocess_symbol_is_declared_and_exported():
     assert "m3_resize_crop_u8" in _ffi.declared_symbols()
     L = _ffi.lib()
     assert hasattr(ctypes.CDLL(_ffi.LIB_PATH), "m3_resize_crop_u8")
-    assert L.m3_abi_version() == 3000
+    assert L.m3_abi_version() == 4000
     # argument validation precedes every HIP call: safe without a device
     assert L.m3_resize_crop_u8(None, None, None, 1, None, None, 1, None, None, 1, 8, 8, 8, 8, 0, 0, 8, 8, None) == -1
     a16 = ctypes.c_void_p(4096)                                           # never dereferenced: the crop box is rejected first

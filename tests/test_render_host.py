@@ -201,7 +201,7 @@ def test_symbols_are_declared_exported_and_validate():
     for n in render.__all__:
         assert n in mast3r_utils.__all__ and getattr(mast3r_utils, n) is getattr(render, n)
     L = _ffi.lib()
-    assert L.m3_abi_version() == 3000                                         # symbols were added, nothing changed
+    assert L.m3_abi_version() == 4000                                         # symbols were added, nothing changed
     assert L.m3_render_ws_bytes(480, 640) == 480 * 640 * 8 and L.m3_render_ws_bytes(1, 1) == 8
     assert L.m3_render_ws_bytes(0, 640) == 0 and L.m3_render_ws_bytes(480, 16385) == 0
     assert L.m3_render_launches(1) == 3 and L.m3_render_launches(256) == 3 and L.m3_render_launches(0) == 2

@@ -85,7 +85,7 @@ def test_entry_points_reject_invalid_arguments_without_a_gpu():
     assert L.m3_retrieval_ws_bytes(10, 1, 0, 0) == 0 and L.m3_retrieval_ws_bytes(10, 1, 65, 0) == 0
     with pytest.raises(RuntimeError, match="invalid argument"):
         _ffi.call("m3_retrieval_topk", *args(k=65))
-    assert L.m3_abi_version() == 3000                                      # the retrieval symbols are part of ABI 3
+    assert L.m3_abi_version() == 4000                                      # the retrieval symbols came with ABI 3; 4000 removed the one-group conv entry points
 
 
 def test_keyframes_pop_last():
