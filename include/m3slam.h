@@ -474,6 +474,23 @@ int m3_resize_crop_u8(const uint8_t *src, const int32_t *bounds_h, const int32_t
                       const int32_t *bounds_v, const int32_t *coef_v, int ksize_v, uint8_t *dst, float *img, int B, int Hs,
                       int Ws, int Hr, int Wr, int crop_x0, int crop_y0, int Hc, int Wc, void *stream);
 
+/* Lens undistortion in front of m3_resize_crop_u8: a bilinear remap of src uint8 [B,Hs,Ws,3] through a fixed-point
+ * coordinate table int32 [Ho,Wo,2] shared by the batch, dst uint8 [B,Ho,Wo,3].  Host side: mast3r_slam/camera.py,
+ * which builds the table from a camera model in float64 (source coordinate times 256, rounded to nearest; integer
+ * coordinates are pixel centres).  Integer arithmetic only; for the entry (qx, qy) of an output pixel
+ *   ix = qx >> 8, iy = qy >> 8 (arithmetic shift = floor), a = qx & 255, b = qy & 255
+ *   out = (p00 (256-a)(256-b) + p01 a (256-b) + p10 (256-a) b + p11 a b + 2^15) >> 16      per channel, in int32
+ *   p00 = src[iy][ix], p01 = src[iy][ix+1], p10 = src[iy+1][ix], p11 = src[iy+1][ix+1]
+ * A tap outside [0,Ws) x [0,Hs) reads `border` (0 ... 255, the same for the three channels).  The sentinel entry
+ * (INT32_MIN, INT32_MIN) of a coordinate the host could not represent has every tap outside, so it writes `border`.
+ * One launch, no workspace, no atomics, no host synchronisation (capturable); the bytes depend on the inputs alone.
+ * A thread owns four neighbouring output pixels (two 16-byte table loads, three 4-byte stores; a row tail or a row
+ * that is not suitably aligned takes a per-pixel path with the same result) and reads its taps from global memory.
+ * Every tap index is clamped into the source before it addresses anything: a table that does not belong to the sizes
+ * cannot move a load or a store out of its buffers.  src, table and dst 16-byte aligned; B <= 65535; sizes <= 2^20. */
+int m3_remap_bilinear_u8(const uint8_t *src, const int32_t *table, uint8_t *dst, int B, int Hs, int Ws, int Ho, int Wo,
+                         int border, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -30,6 +30,7 @@ from .model import Mast3rFull
 from . import matching
 from .retrieval import RetrievalDatabase, load_retriever
 from .export import collect_map, save_ply, save_trajectory
+from .camera import CameraModel, load_calibration, undistort_device
 from .preprocess import adjust_intrinsics, resample_tables, resize_geometry, resize_img_device
 from .render import ViewRecorder, behind, default_intrinsics, depth_to_rgb, look_at, render_map, save_image
 

@@ -80,9 +80,19 @@ class SLAM:
     def run_dataset(self, dataset_or_path, dataset_type: Optional[str] = None, callback: Optional[Callable] = None) -> dict:
         """slam.py:93-96 of the reference: load a dataset (a path, or a Dataset), resize and crop its frames on the
         device to config["dataset"]["img_size"], move the intrinsics the driver was given to the preprocessed image,
-        and run."""
+        and run.  A dataset with a calibration is undistorted on the device first and brings its own intrinsics
+        (Dataset.intrinsics): giving the driver a K as well is an error."""
         ds = dataset_or_path if isinstance(dataset_or_path, Dataset) else load_dataset(dataset_or_path, dataset_type)
-        if self._K_raw is not None and len(ds):
+        undistort = ds.calibration is not None and bool(self.config["dataset"].get("undistort", True))
+        if undistort and self._K_raw is not None:
+            raise ValueError("run_dataset: two sources of intrinsics: SLAM(model, K=...) was given a K and the dataset "
+                             f"has a calibration ({ds.calibration!r}); drop one of them")
+        if undistort:
+            K = torch.from_numpy(ds.intrinsics(self.config["dataset"]["img_size"]))
+            self.keyframes.set_intrinsics(K)
+            if self.config.get("use_calib"):
+                self.factor_graph.K = K
+        elif self._K_raw is not None and len(ds):
             h, w = ds[0][1].shape[:2]
             K = adjust_intrinsics(self._K_raw, resize_geometry(h, w, self.config["dataset"]["img_size"])[3])
             self.keyframes.set_intrinsics(K)
