@@ -221,6 +221,85 @@ def _ceil64(n: int) -> int:
     return (n + 63) // 64 * 64
 
 
+def _lin(W, name: str, w: str = "w", b: str = "b") -> dict:
+    """gemm_ex's weight arguments of projection `name` for one or two groups (W: Mast3rFull._W)."""
+    (w0, b0), (w1, b1) = W(name, w, b)
+    return dict(w=w0, bias=b0, w1=w1, bias1=b1)
+
+
+class _F32Stream:
+    """The residual stream of Mast3rFull._block as an fp32 tensor x, [M,C] or [2,M,C] (two groups): a projection's operand
+    is a LayerNorm launch, a residual product accumulates into x in place.  Every method takes the weight lookup W of its
+    launch (Mast3rFull._W), which also says whether that launch has one group or two."""
+
+    def __init__(self, dt):
+        self.dt = dt                                             # 16-bit type of the operands
+
+    def init(self, W, name, a):
+        """The stream becomes projection `name` of a."""
+        self.x = ops.gemm_ex(a, epi=ops.EPI_F32, **_lin(W, name))
+
+    def norm(self, W, n, dtype=None):
+        """LayerNorm n of the stream in a 16-bit type (the operands' unless given: enc_norm / dec_norm name theirs)."""
+        (g0, b0), (g1, b1) = W(n, "g", "b")
+        if g1 is None:
+            return ops.layernorm(self.x, g0, b0, dtype=dtype or self.dt)
+        return ops.layernorm_grouped2(self.x, g0, b0, g1, b1, dtype=dtype or self.dt)
+
+    final_norm = norm
+
+    def norm_pair(self, W, own, cross):
+        """(LayerNorm `own` of each group's rows, LayerNorm `cross` of the OTHER group's rows) from one pass over x."""
+        return ops.layernorm_dual2(self.x, W(own, "g", "b"), W(cross, "g", "b"), dtype=self.dt)
+
+    def project(self, W, name, a, epi, swap=False, **kw):
+        """Projection `name` of a = norm(...) or one of norm_pair(...); `swap`: a holds the other group's rows (it already does)."""
+        return ops.gemm_ex(a, epi=epi, **_lin(W, name), **kw)
+
+    def accumulate(self, W, name, a):
+        """x += projection `name` of a."""
+        ops.gemm_ex(a, epi=ops.EPI_F32_ACCUM, out=self.x, resid=self.x, **_lin(W, name))
+
+    def round(self, dtype):
+        return ops.cast_f32(self.x, dtype)
+
+
+class _HiLoStream:
+    """The same stream with the LayerNorm fold (fp16 trunk): x = hi + lo in two fp16 planes (22 bits) that the residual GEMMs
+    update in place together with the rows' statistics; hi is the operand of every projection behind a LayerNorm, whose
+    epilogue normalises (.fw / .fb / .fcs weights) - no LayerNorm pass, no 16-bit copy of the stream."""
+
+    def __init__(self, rows, cols, groups, device):
+        self.hl = ops.ln_hl_buffers(rows, cols, device, groups=groups)
+        self.hi, _, self.st = self.hl
+
+    def init(self, W, name, a):
+        ops.gemm_ex(a, epi=ops.EPI_F32, hl=self.hl, **_lin(W, name))
+
+    def norm(self, W, n):
+        return self.hi
+
+    def norm_pair(self, W, own, cross):
+        return self.hi, self.hi
+
+    def project(self, W, name, a, epi, swap=False, **kw):
+        """`swap`: group g multiplies the OTHER group's plane, with that plane's statistics (a_swap)."""
+        (s0,), (s1,) = W(name, "fcs")
+        return ops.gemm_ex(a, epi=epi, fold_in=(self.st, s0, s1), a_swap=swap, **_lin(W, name, "fw", "fb"), **kw)
+
+    def accumulate(self, W, name, a):
+        ops.gemm_ex(a, epi=ops.EPI_F32_ACCUM, hl=self.hl, **_lin(W, name))
+
+    def final_norm(self, W, n, dtype):
+        p0, p1 = W(n, "g", "b")
+        return ops.layernorm_hl(self.hl, *p0, *p1, dtype=dtype)  # enc_norm / dec_norm stay a kernel (it reads the planes)
+
+    def round(self, dtype):
+        if dtype == self.hi.dtype:
+            return self.hi.clone()                               # the hi plane IS the stream rounded to fp16
+        return ops.cast_f32(ops.hl_to_f32(self.hl), dtype)
+
+
 class Mast3rFull:
     """Drop-in for the reference's `Mast3rFull` model object (mast3r_utils.py:72-76)."""
 
@@ -321,42 +400,42 @@ class Mast3rFull:
             P[p + ".w"] = t.to(dev, wdt).contiguous()
             P[p + ".b"] = w[p + ".bias"].repeat(s * s).to(dev, torch.float32).contiguous()
 
-        def fold(dst, wt, bs, npre):
+        def fold(dst, npre):
             """Consumer of LayerNorm `npre`: weights with gamma folded in (rounded to the operand type), the column sums of
             those ROUNDED weights (what mean * sum_k W[n][k] must cancel exactly), bias + W . beta."""
             if not self.ln_fold:
                 return
+            wt, bs = w[dst + ".weight"], w[dst + ".bias"]
             gam, bet = w[npre + ".weight"].double(), w[npre + ".bias"].double()
             wf = (wt.double() * gam[None, :]).to(torch.float32).to(wdt)
             P[dst + ".fw"] = wf.to(dev).contiguous()
             P[dst + ".fcs"] = wf.double().sum(1).to(torch.float32).to(dev).contiguous()
             P[dst + ".fb"] = (bs.double() + wt.double() @ bet).to(torch.float32).to(dev).contiguous()
 
+        # the projections that sit behind a LayerNorm, per block kind: (projection, LayerNorm) - what the fold folds
+        folded = dict(enc=(("attn.qkv", "norm1"), ("mlp.fc1", "norm2")),
+                      dec=(("attn.qkv", "norm1"), ("cross_attn.projq", "norm2"), ("cross_attn.kv", "norm_y"), ("mlp.fc1", "norm3")))
         c = self.cfg
+        w = dict(w)                                             # (the concatenated k|v projections are added under their own names)
         P["patch.w"] = w["patch_embed.proj.weight"].reshape(c["enc_dim"], -1).to(dev, wdt).contiguous()
         P["patch.b"] = w["patch_embed.proj.bias"].to(dev, torch.float32).contiguous()
         for i in range(c["enc_depth"]):
             p = f"enc_blocks.{i}"
             norm(p + ".norm1"); lin(p + ".attn.qkv"); lin(p + ".attn.proj")
             norm(p + ".norm2"); lin(p + ".mlp.fc1"); lin(p + ".mlp.fc2")
-            fold(p + ".attn.qkv", w[p + ".attn.qkv.weight"], w[p + ".attn.qkv.bias"], p + ".norm1")
-            fold(p + ".mlp.fc1", w[p + ".mlp.fc1.weight"], w[p + ".mlp.fc1.bias"], p + ".norm2")
+            for proj, npre in folded["enc"]:
+                fold(f"{p}.{proj}", f"{p}.{npre}")
         norm("enc_norm"); lin("decoder_embed")
         for name in ("dec_blocks", "dec_blocks2"):
             for i in range(c["dec_depth"]):
                 p = f"{name}.{i}"
+                for s in ("weight", "bias"):
+                    w[f"{p}.cross_attn.kv.{s}"] = torch.cat([w[f"{p}.cross_attn.projk.{s}"], w[f"{p}.cross_attn.projv.{s}"]], 0)
                 norm(p + ".norm1"); lin(p + ".attn.qkv"); lin(p + ".attn.proj")
-                norm(p + ".norm2"); norm(p + ".norm_y"); lin(p + ".cross_attn.projq"); lin(p + ".cross_attn.proj")
-                P[p + ".cross_attn.kv.w"] = torch.cat([w[p + ".cross_attn.projk.weight"],
-                                                       w[p + ".cross_attn.projv.weight"]], 0).to(dev, wdt).contiguous()
-                P[p + ".cross_attn.kv.b"] = torch.cat([w[p + ".cross_attn.projk.bias"],
-                                                       w[p + ".cross_attn.projv.bias"]], 0).to(dev, torch.float32).contiguous()
+                norm(p + ".norm2"); norm(p + ".norm_y"); lin(p + ".cross_attn.projq"); lin(p + ".cross_attn.kv"); lin(p + ".cross_attn.proj")
                 norm(p + ".norm3"); lin(p + ".mlp.fc1"); lin(p + ".mlp.fc2")
-                fold(p + ".attn.qkv", w[p + ".attn.qkv.weight"], w[p + ".attn.qkv.bias"], p + ".norm1")
-                fold(p + ".cross_attn.projq", w[p + ".cross_attn.projq.weight"], w[p + ".cross_attn.projq.bias"], p + ".norm2")
-                fold(p + ".cross_attn.kv", torch.cat([w[p + ".cross_attn.projk.weight"], w[p + ".cross_attn.projv.weight"]], 0),
-                     torch.cat([w[p + ".cross_attn.projk.bias"], w[p + ".cross_attn.projv.bias"]], 0), p + ".norm_y")
-                fold(p + ".mlp.fc1", w[p + ".mlp.fc1.weight"], w[p + ".mlp.fc1.bias"], p + ".norm3")
+                for proj, npre in folded["dec"]:
+                    fold(f"{p}.{proj}", f"{p}.{npre}")
         norm("dec_norm")
         ld = c["layer_dims"]
         wdt = self.hdt
@@ -423,13 +502,46 @@ class Mast3rFull:
                       pv_bf16=self.pv_bf16)
         return out
 
-    # ------------------------------------------------------------------ encoder
+    # ------------------------------------------------------------------ trunk
+    def _W(self, p0: str, p1: Optional[str] = None):
+        """Weight lookup of a one- or two-group launch: W(name, *fields) -> per group the P[prefix + name.field] of every
+        field; the second group's are None for one group (p1 None) - what every operator takes to mean "one group"."""
+        P = self.P
+        return lambda n, *f: (tuple(P[f"{p0}{n}.{k}"] for k in f), tuple(None if p1 is None else P[f"{p1}{n}.{k}"] for k in f))
+
+    def _stream(self, rows: int, cols: int, groups: int, device):
+        """The residual stream of a [rows, cols] (x groups) token matrix.  The fold works on row PAIRS: an odd row count
+        (one image with an odd token grid, e.g. 21 x 21) takes the LayerNorm kernels."""
+        if self.ln_fold and rows % 2 == 0:
+            return _HiLoStream(rows, cols, groups, device)
+        return _F32Stream(self.tdt)
+
+    def _block(self, s, W, nb: int, t: int, heads: int, rtok, cross: bool):
+        """One transformer block on the residual stream s (either form) of nb images of t tokens: self-attention, with
+        `cross` cross-attention on the other group's stream (the decoder), the MLP.  W: the block's weights, one group or two."""
+        C, pv, qk = heads * 64, self.pv_bf16, ops.QK_PRESCALE
+        if cross:
+            # cross-attention memory: norm_y of the OTHER view's previous-layer tokens, then the k|v projection
+            # (one pass over the stream also yields norm1 of the same tokens for the self-attention below)
+            xn, yn = s.norm_pair(W, "norm1", "norm_y")
+            kv = s.project(W, "cross_attn.kv", yn, ops.EPI_BF16_ROPE, swap=True, rope=(rtok, C), pv_bf16=pv)   # [2,M,2C], k rotated
+        else:
+            xn = s.norm(W, "norm1")
+        # [..., 3C], q|k rotated; q additionally carries softmax scale * log2(e) (folded in before the 16-bit rounding)
+        qkv = s.project(W, "attn.qkv", xn, ops.EPI_BF16_ROPE, rope=(rtok, 2 * C, C, qk), pv_bf16=pv)
+        s.accumulate(W, "attn.proj", self._attn_qkv(qkv, nb, t, heads))
+        if cross:
+            q = s.project(W, "cross_attn.projq", s.norm(W, "norm2"), ops.EPI_BF16_ROPE, rope=(rtok, C, C, qk))
+            s.accumulate(W, "cross_attn.proj", self._attn_q_kv(q, kv, nb, t, heads))
+        hdn = s.project(W, "mlp.fc1", s.norm(W, "norm3" if cross else "norm2"), ops.EPI_BF16_GELU)
+        s.accumulate(W, "mlp.fc2", hdn)
+
     def encode_tokens(self, imgs_u8: torch.Tensor, imgs2_u8: Optional[torch.Tensor] = None):
         """uint8 [B,H,W,3] -> (enc_norm tokens, trunk 16-bit type, [B*T,1024], (gh,gw)).  Any H, W that are
         multiples of 16 (resize_img emits e.g. 512x336 -> 672 tokens, 512x288 -> 576).  imgs2_u8 (same shape): a second
         image batch encoded behind the first in the same token matrix ([2B*T,1024]) - both are patchified straight into
         their halves, no concatenated image tensor."""
-        P, c = self.P, self.cfg
+        c = self.cfg
         b, h, w, _ = imgs_u8.shape
         gh, gw = h // 16, w // 16
         t = gh * gw
@@ -442,43 +554,11 @@ class Mast3rFull:
             ops.patchify16(imgs_u8, dt, out=patches[:b * t])
             ops.patchify16(imgs2_u8, dt, out=patches[b * t:])
             b = 2 * b
-        if self.ln_fold and patches.shape[0] % 2 == 0:           # (the fold works on row PAIRS: an odd row count - one image with an
-            return self._encode_fold(patches, b, t, rtok), (gh, gw)   #  odd token grid, e.g. 21 x 21 - takes the LayerNorm kernels)
-        E = c["enc_dim"]
-        x = ops.gemm(patches, P["patch.w"], P["patch.b"], ops.EPI_F32)                        # fp32 residual stream
+        s = self._stream(patches.shape[0], c["enc_dim"], 1, patches.device)
+        s.init(self._W(""), "patch", patches)
         for i in range(c["enc_depth"]):
-            p = f"enc_blocks.{i}"
-            xn = ops.layernorm(x, P[p + ".norm1.g"], P[p + ".norm1.b"], dtype=dt)
-            # [M,3E], q|k rotated; q additionally carries softmax scale * log2(e) (folded in before the 16-bit rounding)
-            qkv = ops.gemm_rope(xn, P[p + ".attn.qkv.w"], P[p + ".attn.qkv.b"], rtok, 2 * E, q_cols=E, q_scale=ops.QK_PRESCALE,
-                                pv_bf16=self.pv_bf16)
-            a = self._attn_qkv(qkv, b, t, c["enc_heads"])
-            ops.gemm(a, P[p + ".attn.proj.w"], P[p + ".attn.proj.b"], ops.EPI_F32_ACCUM, out=x, resid=x)
-            xn = ops.layernorm(x, P[p + ".norm2.g"], P[p + ".norm2.b"], dtype=dt)
-            hdn = ops.gemm(xn, P[p + ".mlp.fc1.w"], P[p + ".mlp.fc1.b"], ops.EPI_BF16_GELU)
-            ops.gemm(hdn, P[p + ".mlp.fc2.w"], P[p + ".mlp.fc2.b"], ops.EPI_F32_ACCUM, out=x, resid=x)
-        return ops.layernorm(x, P["enc_norm.g"], P["enc_norm.b"], dtype=dt), (gh, gw)
-
-    def _encode_fold(self, patches, b, t, rtok):
-        """The encoder blocks with the LayerNorm fold: the residual stream lives in two fp16 planes (x = hi + lo, 22 bits) that
-        the residual GEMMs update in place together with the rows' statistics; hi is the operand of the qkv / fc1
-        projections, whose epilogues apply norm1 / norm2 - no LayerNorm pass, no 16-bit copy of the stream."""
-        P, c, dt = self.P, self.cfg, self.tdt
-        E, heads = c["enc_dim"], c["enc_heads"]
-        m = patches.shape[0]
-        hl = ops.ln_hl_buffers(m, E, patches.device)              # the stream as hi + lo fp16 planes (+ row statistics)
-        x16, _, st = hl
-        ops.gemm_ex(patches, P["patch.w"], P["patch.b"], ops.EPI_F32, hl=hl)
-        n_blk = c["enc_depth"]
-        for i in range(n_blk):
-            p = f"enc_blocks.{i}"
-            qkv = ops.gemm_ex(x16, P[p + ".attn.qkv.fw"], P[p + ".attn.qkv.fb"], ops.EPI_BF16_ROPE,
-                              rope=(rtok, 2 * E, E, ops.QK_PRESCALE), pv_bf16=self.pv_bf16, fold_in=(st, P[p + ".attn.qkv.fcs"]))
-            a = self._attn_qkv(qkv, b, t, heads)
-            ops.gemm_ex(a, P[p + ".attn.proj.w"], P[p + ".attn.proj.b"], ops.EPI_F32_ACCUM, hl=hl)
-            hdn = ops.gemm_ex(x16, P[p + ".mlp.fc1.fw"], P[p + ".mlp.fc1.fb"], ops.EPI_BF16_GELU, fold_in=(st, P[p + ".mlp.fc1.fcs"]))
-            ops.gemm_ex(hdn, P[p + ".mlp.fc2.w"], P[p + ".mlp.fc2.b"], ops.EPI_F32_ACCUM, hl=hl)
-        return ops.layernorm_hl(hl, P["enc_norm.g"], P["enc_norm.b"], dtype=dt)                  # enc_norm stays a kernel (reads the planes)
+            self._block(s, self._W(f"enc_blocks.{i}."), b, t, c["enc_heads"], rtok, cross=False)
+        return s.final_norm(self._W(""), "enc_norm", dt), (gh, gw)
 
     def encode(self, img):
         """model.encode(img) (mast3r_utils.py:278): uint8 [H,W,3] -> tokens [T,1024] (16-bit tensor of the trunk type);
@@ -493,112 +573,28 @@ class Mast3rFull:
         """f1, f2 [P*T,1024] in the trunk 16-bit type (enc_norm outputs of view 1 / view 2) -> two lists of DPT
         taps ([P*T,C] in the HEAD 16-bit type) at the configured hooks.  The two decoder branches (different
         weights, same shapes) run as 2-group launches: one GEMM / LayerNorm / attention launch serves both views."""
-        P, c = self.P, self.cfg
+        c = self.cfg
         gh, gw = grid
         t = gh * gw
         rtok = self._rope(gh, gw)
-        D, heads = c["dec_dim"], c["dec_heads"]
         m = npairs * t
         dt, hdt = self.tdt, self.hdt
         if f1.dtype != dt or f2.dtype != dt:
             raise TypeError(f"encoder features must be {dt} (precision={self.precision!r}), got {f1.dtype}")
-        if (f1.is_contiguous() and f2.is_contiguous() and f1.untyped_storage().data_ptr() == f2.untyped_storage().data_ptr()
-                and f2.data_ptr() == f1.data_ptr() + f1.numel() * f1.element_size()):
-            fcat = torch.as_strided(f1, (2, m, f1.shape[1]), (m * f1.shape[1], f1.shape[1], 1))   # adjacent halves of the encoder batch
-        else:
-            fcat = torch.stack([f1, f2])                                                 # [2,M,1024]
-        if self.ln_fold and m % 2 == 0:
-            return self._decode_fold(fcat, f1, f2, npairs, t, rtok)
-        x = ops.gemm_grouped2(fcat, P["decoder_embed.w"], P["decoder_embed.w"], P["decoder_embed.b"],
-                              P["decoder_embed.b"], ops.EPI_F32)                         # fp32 residual streams [2,M,D]
+        fcat = _pair2(f1, f2)                                     # [2,M,1024]: a view on adjacent halves of the encoder batch
+        s = self._stream(m, c["dec_dim"], 2, fcat.device)
+        s.init(self._W("", ""), "decoder_embed", fcat)            # both residual streams [2,M,D]
         # tap 0 = the cached encoder features; the heads read them in their own 16-bit type (bf16 -> fp16 is exact
         # for these LayerNorm outputs: fp16 has more mantissa bits and |x| << 65504)
         if hdt == dt:
             taps = [[f1], [f2]]
         else:
-            c16 = ops.cast16(fcat.reshape(2 * m, -1), hdt)                              # one launch; halves stay adjacent for heads()
+            c16 = ops.cast16(fcat.reshape(2 * m, -1), hdt)        # one launch; halves stay adjacent for heads()
             taps = [[c16[:m]], [c16[m:]]]
-        hooks = set(c["hooks"])
-        W = lambda i, s: (P[f"dec_blocks.{i}.{s}"], P[f"dec_blocks2.{i}.{s}"])
         for i in range(c["dec_depth"]):
-            # cross-attention memory: norm_y of the OTHER view's previous-layer tokens, then k|v projection
-            # (one pass over x also yields norm1 of the same tokens for the self-attention below)
-            xn, yn = ops.layernorm_dual2(x, ((W(i, "norm1.g")[0], W(i, "norm1.b")[0]), (W(i, "norm1.g")[1], W(i, "norm1.b")[1])),
-                                         ((W(i, "norm_y.g")[0], W(i, "norm_y.b")[0]), (W(i, "norm_y.g")[1], W(i, "norm_y.b")[1])), dtype=dt)
-            pv = self.pv_bf16
-            kv = ops.gemm_grouped2(yn, *W(i, "cross_attn.kv.w"), *W(i, "cross_attn.kv.b"), ops.EPI_BF16_ROPE,
-                                   rope=(rtok, D), pv_bf16=pv)                      # [2,M,2D], k rotated
-            # self-attention
-            qkv = ops.gemm_grouped2(xn, *W(i, "attn.qkv.w"), *W(i, "attn.qkv.b"), ops.EPI_BF16_ROPE,
-                                    rope=(rtok, 2 * D, D, ops.QK_PRESCALE), pv_bf16=pv)
-            a = self._attn_qkv(qkv, 2 * npairs, t, heads)
-            ops.gemm_grouped2(a, *W(i, "attn.proj.w"), *W(i, "attn.proj.b"), ops.EPI_F32_ACCUM, out=x, resid=x)
-            # cross-attention
-            xn = ops.layernorm_grouped2(x, W(i, "norm2.g")[0], W(i, "norm2.b")[0], W(i, "norm2.g")[1], W(i, "norm2.b")[1], dtype=dt)
-            q = ops.gemm_grouped2(xn, *W(i, "cross_attn.projq.w"), *W(i, "cross_attn.projq.b"), ops.EPI_BF16_ROPE,
-                                  rope=(rtok, D, D, ops.QK_PRESCALE))
-            a = self._attn_q_kv(q, kv, 2 * npairs, t, heads)
-            ops.gemm_grouped2(a, *W(i, "cross_attn.proj.w"), *W(i, "cross_attn.proj.b"), ops.EPI_F32_ACCUM, out=x, resid=x)
-            # MLP
-            xn = ops.layernorm_grouped2(x, W(i, "norm3.g")[0], W(i, "norm3.b")[0], W(i, "norm3.g")[1], W(i, "norm3.b")[1], dtype=dt)
-            hdn = ops.gemm_grouped2(xn, *W(i, "mlp.fc1.w"), *W(i, "mlp.fc1.b"), ops.EPI_BF16_GELU)
-            ops.gemm_grouped2(hdn, *W(i, "mlp.fc2.w"), *W(i, "mlp.fc2.b"), ops.EPI_F32_ACCUM, out=x, resid=x)
-            layer = i + 1
-            if layer in hooks:
-                if layer == c["dec_depth"]:
-                    tap = ops.layernorm_grouped2(x, P["dec_norm.g"], P["dec_norm.b"], P["dec_norm.g"], P["dec_norm.b"], dtype=hdt)
-                else:
-                    tap = ops.cast_f32(x, hdt)
-                taps[0].append(tap[0])
-                taps[1].append(tap[1])
-        return taps
-
-    def _decode_fold(self, fcat, f1, f2, npairs, t, rtok):
-        """decode_tokens with the LayerNorm fold (fp16 trunk): every norm1 / norm2 / norm_y / norm3 lives in the epilogue of
-        the projection behind it; the residual GEMMs keep the 16-bit copy x16 of both streams and their row statistics st
-        up to date.  Group g of the k|v projection multiplies the OTHER branch's copy (a_swap)."""
-        P, c = self.P, self.cfg
-        D, heads = c["dec_dim"], c["dec_heads"]
-        m = npairs * t
-        dev = fcat.device
-        dt, hdt, pv = self.tdt, self.hdt, self.pv_bf16
-        hl = ops.ln_hl_buffers(m, D, dev, groups=2)               # both residual streams [2,M,D] as hi + lo planes
-        x16, _, st = hl
-        ops.gemm_ex(fcat, P["decoder_embed.w"], P["decoder_embed.b"], ops.EPI_F32, w1=P["decoder_embed.w"],
-                    bias1=P["decoder_embed.b"], hl=hl)
-        if hdt == dt:
-            taps = [[f1], [f2]]
-        else:
-            c16 = ops.cast16(fcat.reshape(2 * m, -1), hdt)
-            taps = [[c16[:m]], [c16[m:]]]
-        hooks = set(c["hooks"])
-        W = lambda i, s: (P[f"dec_blocks.{i}.{s}"], P[f"dec_blocks2.{i}.{s}"])
-
-        def consume(i, name, epi, **kw):
-            (w0, w1), (b0, b1), (s0, s1) = W(i, name + ".fw"), W(i, name + ".fb"), W(i, name + ".fcs")
-            return ops.gemm_ex(x16, w0, b0, epi, w1=w1, bias1=b1, fold_in=(st, s0, s1), **kw)
-
-        def produce(i, name, a):
-            (w0, w1), (b0, b1) = W(i, name + ".w"), W(i, name + ".b")
-            ops.gemm_ex(a, w0, b0, ops.EPI_F32_ACCUM, w1=w1, bias1=b1, hl=hl)
-
-        for i in range(c["dec_depth"]):
-            # cross-attention memory: norm_y of the OTHER view's previous-layer tokens, then the k|v projection
-            kv = consume(i, "cross_attn.kv", ops.EPI_BF16_ROPE, rope=(rtok, D), pv_bf16=pv, a_swap=True)   # [2,M,2D], k rotated
-            qkv = consume(i, "attn.qkv", ops.EPI_BF16_ROPE, rope=(rtok, 2 * D, D, ops.QK_PRESCALE), pv_bf16=pv)
-            produce(i, "attn.proj", self._attn_qkv(qkv, 2 * npairs, t, heads))
-            q = consume(i, "cross_attn.projq", ops.EPI_BF16_ROPE, rope=(rtok, D, D, ops.QK_PRESCALE))
-            produce(i, "cross_attn.proj", self._attn_q_kv(q, kv, 2 * npairs, t, heads))
-            hdn = consume(i, "mlp.fc1", ops.EPI_BF16_GELU)
-            produce(i, "mlp.fc2", hdn)
-            layer = i + 1
-            if layer in hooks:
-                if layer == c["dec_depth"]:
-                    tap = ops.layernorm_hl(hl, P["dec_norm.g"], P["dec_norm.b"], P["dec_norm.g"], P["dec_norm.b"], dtype=hdt)
-                elif hdt == dt:
-                    tap = x16.clone()                      # the hi plane IS the stream rounded to the heads' type
-                else:
-                    tap = ops.cast_f32(ops.hl_to_f32(hl), hdt)
+            self._block(s, self._W(f"dec_blocks.{i}.", f"dec_blocks2.{i}."), 2 * npairs, t, c["dec_heads"], rtok, cross=True)
+            if i + 1 in c["hooks"]:
+                tap = s.final_norm(self._W("", ""), "dec_norm", hdt) if i + 1 == c["dec_depth"] else s.round(hdt)
                 taps[0].append(tap[0])
                 taps[1].append(tap[1])
         return taps

@@ -427,6 +427,46 @@ def test_width_without_fold_statistics_keeps_the_layernorm_kernels(dev):
         assert _rel(o["desc_conf"], r["desc_conf"]) < 6e-3
 
 
+@pytest.mark.parametrize("precision,ln_fold", [("fp16", None), ("bf16", None), ("fp16", "0")])
+def test_trunk_launches_follow_the_stream_form(dev, monkeypatch, precision, ln_fold):
+    """Which entry points one encoder + decoder pass issues, counted from the structure (E encoder blocks of 4 GEMMs and one
+    attention, D two-group decoder blocks of 7 GEMMs and two attentions, the two embeddings, the hooks).  Every parity test
+    passes at its tolerance on either form of the residual stream, so only this pins that the fp16 trunk runs the LayerNorm
+    fold (no LayerNorm launch but enc_norm / dec_norm on the hi / lo planes, mid-depth taps are copies of the hi plane) and
+    that the bf16 trunk and M3_LN_FOLD=0 run the LayerNorm kernels: norm1 + norm_y of a decoder block from ONE dual2 launch."""
+    from mast3r_slam import _ffi
+    if ln_fold is not None:
+        monkeypatch.setenv("M3_LN_FOLD", ln_fold)
+    cfg = M.TINY_CFG
+    net = M.Mast3rFull(weights=M.init_random_weights(cfg, seed=1), cfg=cfg, device=dev, precision=precision)
+    h, wd = 128, 256                                                 # 128 tokens per image: an even row count
+    im1, im2 = (net._as_images(synthetic.textured_image(h, wd, s)) for s in (0, 1))
+    counts, real = {}, _ffi.call
+
+    def counting(name, *args):
+        counts[name] = counts.get(name, 0) + 1
+        return real(name, *args)
+
+    monkeypatch.setattr(_ffi, "call", counting)
+    tok, grid = net.encode_tokens(im1, im2)
+    m = grid[0] * grid[1]
+    taps = net.decode_tokens(tok[:m], tok[m:], 1, grid)
+    assert len(taps[0]) == len(taps[1]) == len(cfg["hooks"])
+    E, D, hooks = cfg["enc_depth"], cfg["dec_depth"], cfg["hooks"]
+    last, mid = int(D in hooks), sum(1 for k in hooks if 0 < k < D)
+    folded = precision == "fp16" and ln_fold is None
+    assert net.ln_fold is folded
+    want = {"m3_gemm_ex": (1 + 4 * E) + (1 + 7 * D), "m3_attention_prescaled_dt": E + 2 * D}
+    if folded:
+        want.update(m3_layernorm_hl_dt=1 + last, m3_layernorm_dt=0, m3_layernorm_dual2_dt=0, m3_layernorm_grouped2_dt=0)
+        taps_cast = 0 if net.hdt == net.tdt else mid                 # a mid-depth tap is a copy of the hi plane when the types agree
+    else:
+        want.update(m3_layernorm_hl_dt=0, m3_layernorm_dt=2 * E + 1, m3_layernorm_dual2_dt=D, m3_layernorm_grouped2_dt=2 * D + last)
+        taps_cast = mid                                              # the fp32 stream is rounded (cast_f32) to the heads' type, whichever it is
+    want.update(m3_cast_f32_dt=taps_cast, m3_cast16=0 if net.hdt == net.tdt else 1)     # tap 0: one cast of the encoder tokens
+    assert {k: counts.get(k, 0) for k in want} == want
+
+
 def test_graphed_reconstruct_equals_eager(tiny, dev):
     """The hipGraph-replayed network (fixed shape, static buffers) returns the same bits as eager launches,
     call after call with different images."""
