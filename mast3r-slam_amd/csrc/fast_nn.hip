@@ -14,6 +14,10 @@
 // reduction.  The database is split over blockIdx.y (so that a 4096-query search still fills the chip); the
 // per-split winners are merged with ONE 64-bit atomicMax per query on a key = (order-preserving score bits,
 // inverted index), which also implements the lowest-index tie-break deterministically.
+//
+// Host side (below the kernels): PackedMap / BlockStats / PruneWs define each buffer layout once - pointers and size -,
+// plan_search the database split, launch_nn_mfma / launch_pack the two template dispatches, and frnn_round is the one
+// round body behind m3_frnn_round, m3_frnn_round_active and m3_frnn_round_pruned.
 #include "common.h"
 #include "../../include/m3slam.h"
 
@@ -793,6 +797,138 @@ k_frnn_end(unsigned long long *__restrict__ keys, const int32_t *__restrict__ xy
     if (act && !conv) cur[i] = back;
 }
 
+// ---- host side: buffer views, the split plan and the launches every entry point shares ----------------------------------
+// Each scratch layout is written down once, in the view that hands out its pointers.  A view on a NULL base has null
+// pointers and still knows its size: that is what the m3_*_bytes entry points return.
+inline char *at(const void *base, int64_t off) { return base ? (char *)base + off : nullptr; }
+
+struct PackedMap {      // a descriptor map packed by k_nn_pack: hi fp16 [P][N][32] (K zero-padded), then lo for fp32 descriptors
+    unsigned short *hi, *lo;
+    int P, N;
+    int64_t bytes;
+    PackedMap(const void *p, int P, int N, int in_f16)
+        : hi((unsigned short *)at(p, 0)), lo(in_f16 ? nullptr : (unsigned short *)at(p, (int64_t)P * N * 64)), P(P), N(N),
+          bytes((int64_t)P * N * 64 * (in_f16 ? 1 : 2)) {}
+};
+
+struct BlockStats {     // k_frnn_blockstats of an H x W map: NB 8 x 8 pixel blocks per pair, stored with the pair stride NBp
+    int H, W, NB, NBp;  // (NB rounded up to 64): centroids fp16 [P][NBp][32], then rad fp32 [P][NBp], then bn fp32 [P][NBp]
+    unsigned short *cen;
+    float *rad, *bn;
+    int64_t bytes;
+    BlockStats(const void *p, int P, int H, int W)
+        : H(H), W(W), NB(m3_cdiv(H, 8) * m3_cdiv(W, 8)), NBp(m3_cdiv(NB, 64) * 64), cen((unsigned short *)at(p, 0)),
+          rad((float *)at(p, (int64_t)P * NBp * 64)), bn((float *)at(p, (int64_t)P * NBp * 68)), bytes((int64_t)P * NBp * 72) {}
+};
+
+struct PruneWs {        // scratch of one block-bound search for S seeds and a database of nbp (padded) blocks
+    int64_t head_bytes;                  // centroid-search keys [P][S] + survivor totals [P], padded to 16 bytes: zeroed per search
+    unsigned long long *keysC;
+    int32_t *total;
+    float *mlb, *qn;                     // [P][S] each
+    unsigned long long *surv;            // survivor bits [P][cdiv(S, 16)][nbp / 64]
+    int64_t bytes;
+    PruneWs(const void *p, int P, int S, int nbp)
+        : head_bytes(((int64_t)P * S * 8 + (int64_t)P * 4 + 15) / 16 * 16), keysC((unsigned long long *)at(p, 0)),
+          total((int32_t *)at(p, (int64_t)P * S * 8)), mlb((float *)at(p, head_bytes)), qn((float *)at(p, head_bytes + (int64_t)P * S * 4)),
+          surv((unsigned long long *)at(p, head_bytes + (int64_t)P * S * 8)),
+          bytes(head_bytes + (int64_t)P * S * 8 + (int64_t)P * m3_cdiv(S, 16) * (nbp / 64) * 8) {}
+};
+
+// The database is split over blockIdx.y so that about `target` workgroups run: at most max_splits, every split but the
+// last a whole number of `step` rows.
+struct SearchPlan { dim3 grid; int per_split; };
+SearchPlan plan_search(int qblocks, int N, int P, int target, int max_splits, int step) {
+    int splits = m3_cdiv(target, qblocks * P);
+    if (splits < 1) splits = 1;
+    if (splits > max_splits) splits = max_splits;
+    if (splits > m3_cdiv(N, step)) splits = m3_cdiv(N, step);
+    const int per_split = m3_cdiv(m3_cdiv(N, splits), step) * step;
+    return {dim3(qblocks, m3_cdiv(N, per_split), P), per_split};
+}
+// ~4 workgroups per CU over the whole call, whole LDS steps except in the last split
+SearchPlan plan_mfma_search(int S, int N, int P) { return plan_search(m3_cdiv(S, kQPB), N, P, 1024, 1024, kRows); }
+
+// The brute-force MFMA search of S queries (rows qidx of q; null: row s) in d: one pass for lo-less maps, three otherwise.
+// qlist / qcount: the active-set form; gate_total / gate_nb: the fallback form of the block-bound search.
+void launch_nn_mfma(const PackedMap &q, const int32_t *qidx, const PackedMap &d, unsigned long long *keys, int S,
+                    const SearchPlan &pl, hipStream_t st, const int32_t *qlist = nullptr, const int32_t *qcount = nullptr,
+                    const int32_t *gate_total = nullptr, int gate_nb = 0) {
+    hipLaunchKernelGGL(d.lo ? k_nn_mfma<3> : k_nn_mfma<1>, pl.grid, dim3(kThreads), 0, st, q.hi, q.lo, qidx, d.hi, d.lo, keys, S,
+                       q.N, d.N, pl.per_split, qlist, qcount, gate_total, gate_nb);
+}
+
+// X [m.P * m.N][D], IEEE fp16 for a lo-less map and fp32 otherwise, to the K-padded planes of m
+void launch_pack(const void *X, const PackedMap &m, int D, hipStream_t st) {
+    const long long rows = (long long)m.P * m.N;
+    const auto k = m.lo ? (D == 24 ? k_nn_pack<false, 24> : D == 16 ? k_nn_pack<false, 16> : k_nn_pack<false, 32>)
+                        : (D == 24 ? k_nn_pack<true, 24> : D == 16 ? k_nn_pack<true, 16> : k_nn_pack<true, 32>);
+    hipLaunchKernelGGL(k, dim3((unsigned)m3_cdiv(rows * 4, (long long)kThreads)), dim3(kThreads), 0, st, X, m.hi, m.lo, rows);
+}
+
+void launch_unpack(const unsigned long long *keys, int32_t *idx_out, float *score_out, long long total, hipStream_t st) {
+    hipLaunchKernelGGL(k_nn_unpack, dim3((unsigned)m3_cdiv(total, (long long)kThreads)), dim3(kThreads), 0, st, keys, idx_out,
+                       score_out, total);
+}
+
+// One search of a round: S queries (rows qidx of q) against d, merged into keys - the brute-force kernel.  With ds, the
+// statistics of d, the block bounds run first (prune_ws: PruneWs scratch) and gate it.
+int frnn_search(const PackedMap &q, const int32_t *qidx, const PackedMap &d, const BlockStats *ds, unsigned long long *keys,
+                int S, hipStream_t st, const int32_t *qlist, const int32_t *qcount, void *prune_ws) {
+    const int P = d.P, NQ = q.N;
+    const int32_t *gate_total = nullptr;
+    if (ds) {
+        const int H = ds->H, W = ds->W, NB = ds->NB, NBp = ds->NBp, NBW = NBp / 64, nqt = m3_cdiv(S, 16);
+        const PruneWs ws(prune_ws, P, S, NBp);
+        M3_CHECK_HIP(hipMemsetAsync(ws.keysC, 0, (size_t)ws.head_bytes, st), "m3_frnn_round_pruned/memset");
+        // 1. the most promising block per query: the brute-force kernel on the centroids (hi plane of the queries).  The
+        // centroid table is [P][NBp][32]: the search runs over NBp rows so that pair b's rows start at b * NBp as
+        // k_frnn_blockstats laid them out (with N = NB every pair b > 0 scored the wrong rows whenever NB % 64 != 0, e.g.
+        // 224 x 224: results stayed exact, the lower bound - and with it the pruning - did not); the padding rows are zero
+        // vectors and k_frnn_seed_lb clamps the chosen block to < NB
+        launch_nn_mfma(PackedMap(q.hi, P, NQ, 1), qidx, PackedMap(ds->cen, P, NBp, 1), ws.keysC, S, plan_mfma_search(S, NBp, P), st,
+                       qlist, qcount);
+        const dim3 blk(kThreads), gl(m3_cdiv(S, kThreads / 64), P);
+        const int ngrp = m3_cdiv(nqt, kQG);
+        int ysplit = m3_cdiv(8192, ngrp * P);
+        ysplit = ysplit < 1 ? 1 : (ysplit > NBW ? NBW : ysplit);
+        const int wpw = m3_cdiv(NBW, ysplit);
+        const dim3 gs(m3_cdiv(ngrp, kThreads / 64), m3_cdiv(NBW, wpw), P), ge(m3_cdiv(nqt, kQE), kEvalY, P);
+        // 2. - 3. lower bound per query, surviving blocks per query tile, exact scores of the survivors
+        hipLaunchKernelGGL(d.lo ? k_frnn_seed_lb<true> : k_frnn_seed_lb<false>, gl, blk, 0, st, q.hi, q.lo, qidx, d.hi, d.lo, ds->bn,
+                           ws.keysC, ws.mlb, ws.qn, S, NQ, H, W, NB, NBp, qlist, qcount);
+        hipLaunchKernelGGL(d.lo ? k_frnn_survivors<true> : k_frnn_survivors<false>, gs, blk, 0, st, q.hi, q.lo, qidx, ds->cen,
+                           ds->rad, ds->bn, ws.mlb, ws.qn, ws.surv, ws.total, S, NQ, NBp, nqt, wpw, qlist, qcount);
+        hipLaunchKernelGGL((d.lo ? k_frnn_eval<3, kQE> : k_frnn_eval<1, kQE>), ge, blk, 0, st, q.hi, q.lo, qidx, d.hi, d.lo, ws.surv,
+                           ws.total, keys, S, NQ, H, W, NB, NBp, nqt, qlist, qcount);
+        gate_total = ws.total;      // 4. gated on the survivor count, the workgroups below leave at once when the bounds worked
+    }
+    launch_nn_mfma(q, qidx, d, keys, S, plan_mfma_search(S, d.N, P), st, qlist, qcount, gate_total, ds ? ds->NB : 0);
+    return M3_OK;
+}
+
+// One round for P pairs: the optional compaction of the active seeds into act_ws (list [P][S], then count [P]), view 1 ->
+// view 2, k_frnn_mid, and back, k_frnn_end.  s1 / s2: statistics of m1 / m2, or null for the brute-force search;
+// where: the caller's name for the launch check.
+int frnn_round(const PackedMap &m1, const PackedMap &m2, const BlockStats *s1, const BlockStats *s2, int32_t *cur, uint8_t *active,
+               int32_t *got1, int32_t *got2, int32_t *xy2_ws, uint64_t *keys_ws, int32_t *act_ws, const int32_t *seed_order,
+               void *prune_ws, int S, hipStream_t st, const char *where) {
+    const int P = m1.P;
+    unsigned long long *keys = reinterpret_cast<unsigned long long *>(keys_ws);
+    int32_t *list = act_ws, *count = act_ws ? act_ws + (size_t)P * S : nullptr;
+    const long long total = (long long)P * S;
+    const dim3 eb(kThreads), eg((unsigned)m3_cdiv(total, (long long)kThreads));
+    if (act_ws) hipLaunchKernelGGL(k_frnn_compact, dim3(P), eb, 0, st, active, seed_order, list, count, S);
+    int rc = frnn_search(m1, cur, m2, s2, keys, S, st, list, count, prune_ws);                    // view 1 -> view 2
+    if (rc != M3_OK) return rc;
+    hipLaunchKernelGGL(k_frnn_mid, eg, eb, 0, st, keys, xy2_ws, total);
+    rc = frnn_search(m2, xy2_ws, m1, s1, keys, S, st, list, count, prune_ws);                     // and back
+    if (rc != M3_OK) return rc;
+    hipLaunchKernelGGL(k_frnn_end, eg, eb, 0, st, keys, xy2_ws, cur, active, got1, got2, total);
+    M3_CHECK_LAUNCH(where);
+    return M3_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -804,31 +940,21 @@ int m3_nn_search(const float *Q, const float *DB, int32_t *idx_out, float *score
     M3_REQUIRE(((reinterpret_cast<size_t>(Q) | reinterpret_cast<size_t>(DB)) & 15) == 0);
     hipStream_t st = (hipStream_t)stream;
     M3_CHECK_HIP(hipMemsetAsync(keys_ws, 0, (size_t)B * S * 8, st), "m3_nn_search/memset");
-    const int qblocks = m3_cdiv(S, kThreads * kQPL);
-    int splits = m3_cdiv(2048, qblocks * B);                 // ~8 workgroups per CU over the whole call
-    if (splits < 1) splits = 1;
-    if (splits > 1024) splits = 1024;
-    if (splits > N) splits = N;
-    const int per_split = m3_cdiv(N, splits);
-    splits = m3_cdiv(N, per_split);
-    dim3 grid(qblocks, splits, B);
+    const SearchPlan pl = plan_search(m3_cdiv(S, kThreads * kQPL), N, B, 2048, 1024, 1);   // ~8 workgroups per CU over the whole call
     unsigned long long *keys = reinterpret_cast<unsigned long long *>(keys_ws);
-    if (D == 24) hipLaunchKernelGGL(k_nn_search<24>, grid, dim3(kThreads), 0, st, Q, DB, keys, S, N, per_split);
-    else if (D == 16) hipLaunchKernelGGL(k_nn_search<16>, grid, dim3(kThreads), 0, st, Q, DB, keys, S, N, per_split);
-    else hipLaunchKernelGGL(k_nn_search<32>, grid, dim3(kThreads), 0, st, Q, DB, keys, S, N, per_split);
+    hipLaunchKernelGGL(D == 24 ? k_nn_search<24> : D == 16 ? k_nn_search<16> : k_nn_search<32>, pl.grid, dim3(kThreads), 0, st, Q, DB,
+                       keys, S, N, pl.per_split);
     M3_CHECK_LAUNCH("m3_nn_search");
-    const long long total = (long long)B * S;
-    hipLaunchKernelGGL(k_nn_unpack, dim3((unsigned)m3_cdiv(total, (long long)kThreads)), dim3(kThreads), 0, st,
-                       (const unsigned long long *)keys, idx_out, score_out, total);
+    launch_unpack(keys, idx_out, score_out, (long long)B * S, st);
     M3_CHECK_LAUNCH("m3_nn_search/unpack");
     return M3_OK;
 }
 
 // MFMA search.  Q [B,S,D], DB [B,N,D] in fp32 (in_f16 = 0) or IEEE fp16 (in_f16 = 1), D <= 32 and D % 4 == 0.
-// pack_ws: m3_nn_pack_bytes(B, S, N, in_f16) bytes of scratch for the K-padded fp16 operands.
+// pack_ws: m3_nn_pack_bytes(B, S, N, in_f16) bytes of scratch: the packed queries, then the packed database.
 int64_t m3_nn_pack_bytes(int B, int S, int N, int in_f16) {
     if (B <= 0 || S <= 0 || N <= 0) return 0;
-    return (int64_t)B * ((int64_t)S + N) * 64 * (in_f16 ? 1 : 2);
+    return PackedMap(nullptr, B, S, in_f16).bytes + PackedMap(nullptr, B, N, in_f16).bytes;
 }
 
 int m3_nn_search_mfma(const void *Q, const void *DB, int32_t *idx_out, float *score_out, uint64_t *keys_ws,
@@ -836,81 +962,30 @@ int m3_nn_search_mfma(const void *Q, const void *DB, int32_t *idx_out, float *sc
     M3_REQUIRE(Q && DB && idx_out && keys_ws && pack_ws && B > 0 && S > 0 && N > 0 && B <= 65535);
     M3_REQUIRE((D == 16 || D == 24 || D == 32) && (reinterpret_cast<size_t>(pack_ws) & 15) == 0);
     hipStream_t st = (hipStream_t)stream;
-    unsigned short *qhi = (unsigned short *)pack_ws, *dhi = qhi + (size_t)B * S * 32;
-    unsigned short *qlo = in_f16 ? nullptr : dhi + (size_t)B * N * 32, *dlo = in_f16 ? nullptr : qlo + (size_t)B * S * 32;
-    const long long qr = (long long)B * S, dr = (long long)B * N;
-    const dim3 blk(kThreads), gq((unsigned)m3_cdiv(qr * 4, (long long)kThreads)), gd((unsigned)m3_cdiv(dr * 4, (long long)kThreads));
-#define M3_PACK(DD)                                                                                     \
-    do {                                                                                                \
-        if (in_f16) { hipLaunchKernelGGL((k_nn_pack<true, DD>), gq, blk, 0, st, Q, qhi, qlo, qr);        \
-                      hipLaunchKernelGGL((k_nn_pack<true, DD>), gd, blk, 0, st, DB, dhi, dlo, dr); }     \
-        else { hipLaunchKernelGGL((k_nn_pack<false, DD>), gq, blk, 0, st, Q, qhi, qlo, qr);              \
-               hipLaunchKernelGGL((k_nn_pack<false, DD>), gd, blk, 0, st, DB, dhi, dlo, dr); }           \
-    } while (0)
-    if (D == 24) M3_PACK(24); else if (D == 16) M3_PACK(16); else M3_PACK(32);
-#undef M3_PACK
+    const PackedMap q(pack_ws, B, S, in_f16), d(at(pack_ws, q.bytes), B, N, in_f16);
+    launch_pack(Q, q, D, st);
+    launch_pack(DB, d, D, st);
     M3_CHECK_LAUNCH("m3_nn_search_mfma/pack");
     M3_CHECK_HIP(hipMemsetAsync(keys_ws, 0, (size_t)B * S * 8, st), "m3_nn_search_mfma/memset");
-    const int qblocks = m3_cdiv(S, kQPB);
-    int splits = m3_cdiv(1024, qblocks * B);                  // ~4 workgroups per CU over the whole call
-    if (splits < 1) splits = 1;
-    if (splits > m3_cdiv(N, kRows)) splits = m3_cdiv(N, kRows);
-    int per_split = m3_cdiv(N, splits);
-    per_split = m3_cdiv(per_split, kRows) * kRows;            // whole LDS steps except in the last split
-    splits = m3_cdiv(N, per_split);
-    const dim3 grid(qblocks, splits, B);
     unsigned long long *keys = reinterpret_cast<unsigned long long *>(keys_ws);
-    if (in_f16) hipLaunchKernelGGL(k_nn_mfma<1>, grid, blk, 0, st, qhi, qlo, (const int32_t *)nullptr, dhi, dlo, keys, S, S, N, per_split,
-                                   (const int32_t *)nullptr, (const int32_t *)nullptr, (const int32_t *)nullptr, 0);
-    else hipLaunchKernelGGL(k_nn_mfma<3>, grid, blk, 0, st, qhi, qlo, (const int32_t *)nullptr, dhi, dlo, keys, S, S, N, per_split,
-                            (const int32_t *)nullptr, (const int32_t *)nullptr, (const int32_t *)nullptr, 0);
+    launch_nn_mfma(q, nullptr, d, keys, S, plan_mfma_search(S, N, B), st);
     M3_CHECK_LAUNCH("m3_nn_search_mfma");
-    const long long total = (long long)B * S;
-    hipLaunchKernelGGL(k_nn_unpack, dim3((unsigned)m3_cdiv(total, (long long)kThreads)), dim3(kThreads), 0, st,
-                       (const unsigned long long *)keys, idx_out, score_out, total);
+    launch_unpack(keys, idx_out, score_out, (long long)B * S, st);
     M3_CHECK_LAUNCH("m3_nn_search_mfma/unpack");
     return M3_OK;
 }
 
 
 // ---- batched fast reciprocal NN: pack each descriptor map ONCE, then rounds of (forward search, backward search) ------
-// A packed map is [P][N][32] fp16 (K zero-padded), followed by the lo plane for fp32 descriptors.
 int64_t m3_frnn_pack_bytes(int P, int N, int in_f16) {
     if (P <= 0 || N <= 0) return 0;
-    return (int64_t)P * N * 64 * (in_f16 ? 1 : 2);
+    return PackedMap(nullptr, P, N, in_f16).bytes;
 }
 int m3_frnn_pack(const void *Dmap, void *packed, int P, int N, int D, int in_f16, void *stream) {
     M3_REQUIRE(Dmap && packed && P > 0 && N > 0 && (D == 16 || D == 24 || D == 32));
     M3_REQUIRE((reinterpret_cast<size_t>(packed) & 15) == 0);
-    hipStream_t st = (hipStream_t)stream;
-    unsigned short *hi = (unsigned short *)packed, *lo = in_f16 ? nullptr : hi + (size_t)P * N * 32;
-    const long long rows = (long long)P * N;
-    const dim3 blk(kThreads), grid((unsigned)m3_cdiv(rows * 4, (long long)kThreads));
-#define M3_PACK1(DD)                                                                                         \
-    do { if (in_f16) hipLaunchKernelGGL((k_nn_pack<true, DD>), grid, blk, 0, st, Dmap, hi, lo, rows);          \
-         else hipLaunchKernelGGL((k_nn_pack<false, DD>), grid, blk, 0, st, Dmap, hi, lo, rows); } while (0)
-    if (D == 24) M3_PACK1(24); else if (D == 16) M3_PACK1(16); else M3_PACK1(32);
-#undef M3_PACK1
+    launch_pack(Dmap, PackedMap(packed, P, N, in_f16), D, (hipStream_t)stream);
     M3_CHECK_LAUNCH("m3_frnn_pack");
-    return M3_OK;
-}
-
-static int frnn_search(const void *qpacked, int NQ, const int32_t *qidx, const void *dpacked, int N, unsigned long long *keys,
-                       int P, int S, int in_f16, hipStream_t st, const int32_t *qlist = nullptr, const int32_t *qcount = nullptr) {
-    const unsigned short *qhi = (const unsigned short *)qpacked, *qlo = in_f16 ? nullptr : qhi + (size_t)P * NQ * 32;
-    const unsigned short *dhi = (const unsigned short *)dpacked, *dlo = in_f16 ? nullptr : dhi + (size_t)P * N * 32;
-    const int qblocks = m3_cdiv(S, kQPB);
-    int splits = m3_cdiv(1024, qblocks * P);                  // ~4 workgroups per CU over the whole call
-    if (splits < 1) splits = 1;
-    if (splits > m3_cdiv(N, kRows)) splits = m3_cdiv(N, kRows);
-    int per_split = m3_cdiv(N, splits);
-    per_split = m3_cdiv(per_split, kRows) * kRows;
-    splits = m3_cdiv(N, per_split);
-    const dim3 grid(qblocks, splits, P), blk(kThreads);
-    if (in_f16) hipLaunchKernelGGL(k_nn_mfma<1>, grid, blk, 0, st, qhi, qlo, qidx, dhi, dlo, keys, S, NQ, N, per_split, qlist, qcount,
-                                   (const int32_t *)nullptr, 0);
-    else hipLaunchKernelGGL(k_nn_mfma<3>, grid, blk, 0, st, qhi, qlo, qidx, dhi, dlo, keys, S, NQ, N, per_split, qlist, qcount,
-                            (const int32_t *)nullptr, 0);
     return M3_OK;
 }
 
@@ -922,16 +997,8 @@ int m3_frnn_round(const void *packed1, const void *packed2, int32_t *cur, uint8_
                   int32_t *xy2_ws, uint64_t *keys_ws, int P, int S, int N1, int N2, int in_f16, void *stream) {
     M3_REQUIRE(packed1 && packed2 && cur && active && got1 && got2 && xy2_ws && keys_ws);
     M3_REQUIRE(P > 0 && P <= 65535 && S > 0 && N1 > 0 && N2 > 0);
-    hipStream_t st = (hipStream_t)stream;
-    unsigned long long *keys = reinterpret_cast<unsigned long long *>(keys_ws);
-    const long long total = (long long)P * S;
-    const dim3 eb(kThreads), eg((unsigned)m3_cdiv(total, (long long)kThreads));
-    frnn_search(packed1, N1, cur, packed2, N2, keys, P, S, in_f16, st);               // view 1 -> view 2
-    hipLaunchKernelGGL(k_frnn_mid, eg, eb, 0, st, keys, xy2_ws, total);
-    frnn_search(packed2, N2, xy2_ws, packed1, N1, keys, P, S, in_f16, st);            // and back
-    hipLaunchKernelGGL(k_frnn_end, eg, eb, 0, st, keys, (const int32_t *)xy2_ws, cur, active, got1, got2, total);
-    M3_CHECK_LAUNCH("m3_frnn_round");
-    return M3_OK;
+    return frnn_round(PackedMap(packed1, P, N1, in_f16), PackedMap(packed2, P, N2, in_f16), nullptr, nullptr, cur, active, got1,
+                      got2, xy2_ws, keys_ws, nullptr, nullptr, nullptr, S, (hipStream_t)stream, "m3_frnn_round");
 }
 
 // m3_frnn_round restricted to the seeds that are still active: act_ws int32 [P * (S + 1)] scratch receives the ascending
@@ -943,111 +1010,30 @@ int m3_frnn_round_active(const void *packed1, const void *packed2, int32_t *cur,
                          int in_f16, void *stream) {
     M3_REQUIRE(packed1 && packed2 && cur && active && got1 && got2 && xy2_ws && keys_ws && act_ws);
     M3_REQUIRE(P > 0 && P <= 65535 && S > 0 && N1 > 0 && N2 > 0);
-    hipStream_t st = (hipStream_t)stream;
-    unsigned long long *keys = reinterpret_cast<unsigned long long *>(keys_ws);
-    int32_t *list = act_ws, *count = act_ws + (size_t)P * S;
-    const long long total = (long long)P * S;
-    const dim3 eb(kThreads), eg((unsigned)m3_cdiv(total, (long long)kThreads));
-    hipLaunchKernelGGL(k_frnn_compact, dim3(P), eb, 0, st, (const uint8_t *)active, (const int32_t *)nullptr, list, count, S);
-    frnn_search(packed1, N1, cur, packed2, N2, keys, P, S, in_f16, st, list, count);
-    hipLaunchKernelGGL(k_frnn_mid, eg, eb, 0, st, keys, xy2_ws, total);
-    frnn_search(packed2, N2, xy2_ws, packed1, N1, keys, P, S, in_f16, st, list, count);
-    hipLaunchKernelGGL(k_frnn_end, eg, eb, 0, st, keys, (const int32_t *)xy2_ws, cur, active, got1, got2, total);
-    M3_CHECK_LAUNCH("m3_frnn_round_active");
-    return M3_OK;
+    return frnn_round(PackedMap(packed1, P, N1, in_f16), PackedMap(packed2, P, N2, in_f16), nullptr, nullptr, cur, active, got1,
+                      got2, xy2_ws, keys_ws, act_ws, nullptr, nullptr, S, (hipStream_t)stream, "m3_frnn_round_active");
 }
 
 // ---- block-bound search: statistics of a packed map, scratch, and the round built on it ---------------------------------
-static inline int prune_nb(int H, int W) { return m3_cdiv(H, 8) * m3_cdiv(W, 8); }
-static inline int prune_nbp(int H, int W) { return m3_cdiv(prune_nb(H, W), 64) * 64; }
-// stats of a packed map [P][H * W]: centroids fp16 [P][NBp][32], then rad fp32 [P][NBp], then bn fp32 [P][NBp]
 int64_t m3_frnn_stats_bytes(int P, int H, int W) {
     if (P <= 0 || H <= 0 || W <= 0) return 0;
-    return (int64_t)P * prune_nbp(H, W) * (64 + 4 + 4);
+    return BlockStats(nullptr, P, H, W).bytes;
 }
 int m3_frnn_blockstats(const void *packed, void *stats, int P, int H, int W, int in_f16, void *stream) {
     M3_REQUIRE(packed && stats && P > 0 && P <= 65535 && H > 0 && W > 0 && (int64_t)H * W < (1ll << 31));
     M3_REQUIRE((reinterpret_cast<size_t>(stats) & 15) == 0);
-    const unsigned short *hi = (const unsigned short *)packed, *lo = in_f16 ? nullptr : hi + (size_t)P * H * W * 32;
-    const int NB = prune_nb(H, W), NBp = prune_nbp(H, W);
-    unsigned short *cen = (unsigned short *)stats;
-    float *rad = reinterpret_cast<float *>(cen + (size_t)P * NBp * 32), *bn = rad + (size_t)P * NBp;
-    hipLaunchKernelGGL(k_frnn_blockstats, dim3(m3_cdiv(NBp, kThreads / 64), P), dim3(kThreads), 0, (hipStream_t)stream, hi, lo, cen, rad, bn,
-                       H, W, NB, NBp);
+    const PackedMap m(packed, P, H * W, in_f16);
+    const BlockStats s(stats, P, H, W);
+    hipLaunchKernelGGL(k_frnn_blockstats, dim3(m3_cdiv(s.NBp, kThreads / 64), P), dim3(kThreads), 0, (hipStream_t)stream, m.hi, m.lo,
+                       s.cen, s.rad, s.bn, H, W, s.NB, s.NBp);
     M3_CHECK_LAUNCH("m3_frnn_blockstats");
     return M3_OK;
 }
-// scratch of m3_frnn_round_pruned for S seeds
+// scratch of m3_frnn_round_pruned for S seeds: one PruneWs, sized for the map with more blocks
 int64_t m3_frnn_prune_ws_bytes(int P, int S, int H1, int W1, int H2, int W2) {
     if (P <= 0 || S <= 0 || H1 <= 0 || W1 <= 0 || H2 <= 0 || W2 <= 0) return 0;
-    const int64_t head = ((int64_t)P * S * 8 + (int64_t)P * 4 + 15) / 16 * 16;        // centroid-search keys + survivor totals (zeroed per search)
-    const int nbp = prune_nbp(H1, W1) > prune_nbp(H2, W2) ? prune_nbp(H1, W1) : prune_nbp(H2, W2);
-    return head + (int64_t)P * S * 8 + (int64_t)P * m3_cdiv(S, 16) * (nbp / 64) * 8;
-}
-
-static int frnn_search_pruned(const void *qpacked, int NQ, const int32_t *qidx, const void *dpacked, int H, int W, const void *dstats,
-                              unsigned long long *keys, int P, int S, int in_f16, hipStream_t st, const int32_t *qlist,
-                              const int32_t *qcount, void *ws) {
-    const int N = H * W;
-    const unsigned short *qhi = (const unsigned short *)qpacked, *qlo = in_f16 ? nullptr : qhi + (size_t)P * NQ * 32;
-    const unsigned short *dhi = (const unsigned short *)dpacked, *dlo = in_f16 ? nullptr : dhi + (size_t)P * N * 32;
-    const int NB = prune_nb(H, W), NBp = prune_nbp(H, W), NBW = NBp / 64, nqt = m3_cdiv(S, 16);
-    const unsigned short *cen = (const unsigned short *)dstats;
-    const float *rad = reinterpret_cast<const float *>(cen + (size_t)P * NBp * 32), *bn = rad + (size_t)P * NBp;
-    const int64_t head = ((int64_t)P * S * 8 + (int64_t)P * 4 + 15) / 16 * 16;
-    unsigned long long *keysC = (unsigned long long *)ws;
-    int32_t *total = reinterpret_cast<int32_t *>(keysC + (size_t)P * S);
-    float *mlb = reinterpret_cast<float *>((unsigned char *)ws + head), *qn = mlb + (size_t)P * S;
-    unsigned long long *surv = reinterpret_cast<unsigned long long *>(qn + (size_t)P * S);
-    M3_CHECK_HIP(hipMemsetAsync(ws, 0, (size_t)head, st), "m3_frnn_round_pruned/memset");
-    const dim3 blk(kThreads);
-    {   // 1. the most promising block per query: the brute-force kernel on the NB centroids (hi plane of the queries)
-        const int qblocks = m3_cdiv(S, kQPB);
-        int splits = m3_cdiv(1024, qblocks * P);
-        if (splits < 1) splits = 1;
-        // the centroid table is [P][NBp][32] (NBp = NB rounded up to 64): the search runs over NBp rows so that pair b's
-        // rows start at b * NBp as k_frnn_blockstats laid them out (with N = NB every pair b > 0 scored the wrong rows
-        // whenever NB % 64 != 0, e.g. 224 x 224: results stayed exact, the lower bound - and with it the pruning - did not);
-        // the padding rows are zero vectors and k_frnn_seed_lb clamps the chosen block to < NB
-        if (splits > m3_cdiv(NBp, kRows)) splits = m3_cdiv(NBp, kRows);
-        int per_split = m3_cdiv(m3_cdiv(NBp, splits), kRows) * kRows;
-        splits = m3_cdiv(NBp, per_split);
-        hipLaunchKernelGGL(k_nn_mfma<1>, dim3(qblocks, splits, P), blk, 0, st, qhi, (const unsigned short *)nullptr, qidx, cen,
-                           (const unsigned short *)nullptr, keysC, S, NQ, NBp, per_split, qlist, qcount, (const int32_t *)nullptr, 0);
-    }
-    const dim3 gl(m3_cdiv(S, kThreads / 64), P);
-    const int ngrp = m3_cdiv(nqt, kQG);
-    int ysplit = m3_cdiv(8192, ngrp * P);
-    ysplit = ysplit < 1 ? 1 : (ysplit > NBW ? NBW : ysplit);
-    const int wpw = m3_cdiv(NBW, ysplit);
-    const dim3 gs(m3_cdiv(ngrp, kThreads / 64), m3_cdiv(NBW, wpw), P), ge(m3_cdiv(nqt, kQE), kEvalY, P);
-    if (in_f16) {
-        hipLaunchKernelGGL(k_frnn_seed_lb<false>, gl, blk, 0, st, qhi, qlo, qidx, dhi, dlo, bn, keysC, mlb, qn, S, NQ, H, W, NB, NBp, qlist, qcount);
-        hipLaunchKernelGGL(k_frnn_survivors<false>, gs, blk, 0, st, qhi, qlo, qidx, cen, rad, bn, (const float *)mlb, (const float *)qn,
-                           surv, total, S, NQ, NBp, nqt, wpw, qlist, qcount);
-        hipLaunchKernelGGL((k_frnn_eval<1, kQE>), ge, blk, 0, st, qhi, qlo, qidx, dhi, dlo, (const unsigned long long *)surv,
-                           (const int32_t *)total, keys, S, NQ, H, W, NB, NBp, nqt, qlist, qcount);
-    } else {
-        hipLaunchKernelGGL(k_frnn_seed_lb<true>, gl, blk, 0, st, qhi, qlo, qidx, dhi, dlo, bn, keysC, mlb, qn, S, NQ, H, W, NB, NBp, qlist, qcount);
-        hipLaunchKernelGGL(k_frnn_survivors<true>, gs, blk, 0, st, qhi, qlo, qidx, cen, rad, bn, (const float *)mlb, (const float *)qn,
-                           surv, total, S, NQ, NBp, nqt, wpw, qlist, qcount);
-        hipLaunchKernelGGL((k_frnn_eval<3, kQE>), ge, blk, 0, st, qhi, qlo, qidx, dhi, dlo, (const unsigned long long *)surv,
-                           (const int32_t *)total, keys, S, NQ, H, W, NB, NBp, nqt, qlist, qcount);
-    }
-    {   // 4. the brute-force search, gated on the survivor count (its workgroups leave at once when the bounds worked)
-        const int qblocks = m3_cdiv(S, kQPB);
-        int splits = m3_cdiv(1024, qblocks * P);
-        if (splits < 1) splits = 1;
-        if (splits > m3_cdiv(N, kRows)) splits = m3_cdiv(N, kRows);
-        int per_split = m3_cdiv(m3_cdiv(N, splits), kRows) * kRows;
-        splits = m3_cdiv(N, per_split);
-        const dim3 grid(qblocks, splits, P);
-        if (in_f16) hipLaunchKernelGGL(k_nn_mfma<1>, grid, blk, 0, st, qhi, qlo, qidx, dhi, dlo, keys, S, NQ, N, per_split, qlist, qcount,
-                                       (const int32_t *)total, NB);
-        else hipLaunchKernelGGL(k_nn_mfma<3>, grid, blk, 0, st, qhi, qlo, qidx, dhi, dlo, keys, S, NQ, N, per_split, qlist, qcount,
-                                (const int32_t *)total, NB);
-    }
-    return M3_OK;
+    const int nbp1 = BlockStats(nullptr, P, H1, W1).NBp, nbp2 = BlockStats(nullptr, P, H2, W2).NBp;
+    return PruneWs(nullptr, P, S, nbp1 > nbp2 ? nbp1 : nbp2).bytes;
 }
 
 // m3_frnn_round / m3_frnn_round_active with the block-bound search: the maps are H1 x W1 / H2 x W2 pixels in raster order,
@@ -1065,21 +1051,9 @@ int m3_frnn_round_pruned(const void *packed1, const void *packed2, const void *s
     M3_REQUIRE(packed1 && packed2 && stats1 && stats2 && cur && active && got1 && got2 && xy2_ws && keys_ws && prune_ws);
     M3_REQUIRE(P > 0 && P <= 65535 && S > 0 && H1 > 0 && W1 > 0 && H2 > 0 && W2 > 0 && (reinterpret_cast<size_t>(prune_ws) & 15) == 0);
     M3_REQUIRE((int64_t)H1 * W1 < (1ll << 31) && (int64_t)H2 * W2 < (1ll << 31) && (!seed_order || act_ws));
-    hipStream_t st = (hipStream_t)stream;
-    unsigned long long *keys = reinterpret_cast<unsigned long long *>(keys_ws);
-    const int32_t *list = act_ws, *count = act_ws ? act_ws + (size_t)P * S : nullptr;
-    const long long total = (long long)P * S;
-    const int N1 = H1 * W1, N2 = H2 * W2;
-    const dim3 eb(kThreads), eg((unsigned)m3_cdiv(total, (long long)kThreads));
-    if (act_ws) hipLaunchKernelGGL(k_frnn_compact, dim3(P), eb, 0, st, (const uint8_t *)active, seed_order, act_ws, act_ws + (size_t)P * S, S);
-    int rc = frnn_search_pruned(packed1, N1, cur, packed2, H2, W2, stats2, keys, P, S, in_f16, st, list, count, prune_ws);
-    if (rc != M3_OK) return rc;
-    hipLaunchKernelGGL(k_frnn_mid, eg, eb, 0, st, keys, xy2_ws, total);
-    rc = frnn_search_pruned(packed2, N2, xy2_ws, packed1, H1, W1, stats1, keys, P, S, in_f16, st, list, count, prune_ws);
-    if (rc != M3_OK) return rc;
-    hipLaunchKernelGGL(k_frnn_end, eg, eb, 0, st, keys, (const int32_t *)xy2_ws, cur, active, got1, got2, total);
-    M3_CHECK_LAUNCH("m3_frnn_round_pruned");
-    return M3_OK;
+    const BlockStats s1(stats1, P, H1, W1), s2(stats2, P, H2, W2);
+    return frnn_round(PackedMap(packed1, P, H1 * W1, in_f16), PackedMap(packed2, P, H2 * W2, in_f16), &s1, &s2, cur, active, got1,
+                      got2, xy2_ws, keys_ws, act_ws, seed_order, prune_ws, S, (hipStream_t)stream, "m3_frnn_round_pruned");
 }
 
 // The reciprocal pairs of `rounds` rounds (got1 / got2 int32 [rounds,P,S]) as FIXED-SHAPE device outputs - no sort, no

@@ -56,6 +56,23 @@ def test_metadata_entry_points(built_lib):
     assert L.m3_gn_rays_max_dim() % 7 == 0
 
 
+def test_fast_nn_scratch_sizes(built_lib):
+    """The matcher's scratch sizes are pure host code (csrc/fast_nn.hip: each one is the size of the view that hands out the
+    pointers).  Pinned to the values the layouts documented there give."""
+    L = _ffi.lib()
+    assert L.m3_frnn_pack_bytes(2, 2240, 1) == 286720 and L.m3_frnn_pack_bytes(2, 2240, 0) == 573440      # P N 64 (x 2: lo plane)
+    assert L.m3_nn_pack_bytes(1, 300, 5000, 0) == 678400                     # queries + database, hi + lo
+    assert L.m3_frnn_stats_bytes(2, 40, 56) == 9216                          # NB = 35 -> NBp = 64; 2 x 64 x (64 + 4 + 4)
+    assert L.m3_frnn_prune_ws_bytes(2, 140, 40, 56, 48, 64) == 4640          # head 2256 + mlb, qn 2240 + survivor bits 144
+    assert L.m3_frnn_pack_bytes(0, 2240, 1) == 0 and L.m3_frnn_pack_bytes(2, -1, 0) == 0
+    assert L.m3_nn_pack_bytes(0, 300, 5000, 0) == 0 and L.m3_nn_pack_bytes(1, 0, 5000, 0) == 0 and L.m3_nn_pack_bytes(1, 300, -5, 1) == 0
+    assert L.m3_frnn_stats_bytes(0, 40, 56) == 0 and L.m3_frnn_stats_bytes(2, 0, 56) == 0 and L.m3_frnn_stats_bytes(2, 40, -1) == 0
+    for k in range(6):
+        args = [2, 140, 40, 56, 48, 64]
+        args[k] = 0 if k % 2 else -3
+        assert L.m3_frnn_prune_ws_bytes(*args) == 0
+
+
 def test_null_arguments_are_rejected_without_a_gpu(built_lib):
     # argument validation happens before any HIP call, so this is safe on a CPU-only box
     L = _ffi.lib()

@@ -207,6 +207,73 @@ def test_block_bound_search_equals_brute_force_bit_for_bit(dev, case):
             assert int(brute["count"].min()) > 20
 
 
+@pytest.mark.parametrize("half", [True, False], ids=["f16", "f32"])
+def test_pruned_round_without_an_active_list_equals_the_full_round(dev, half):
+    """m3_frnn_round_pruned with act_ws = NULL and seed_order = NULL (a block-bound round on every seed slot) against
+    m3_frnn_round, through the C ABI, three rounds.  40 x 56 maps, subsample 4, P = 2: S = 140 is no multiple of 16,
+    N = 2240 none of 128, NB = 35 none of 64 - pair 1 reads its centroids, radii and bounds at the padded stride NBp = 64.
+    Seed 3: the CPU oracle converges 115 - 120 of the 140 seeds of either pair in round 0 and leaves 20 - 25 active."""
+    from mast3r_slam import _ffi
+    sc = synthetic.geometric_pair(40, 56, seed=3, batch=2)
+    D1, D2 = torch.from_numpy(sc["D21"]).to(dev), torch.from_numpy(sc["D11"]).to(dev)
+    if half:
+        D1, D2 = D1.half(), D2.half()
+    P, h, w, d = D1.shape
+    n, sub, f16 = h * w, 4, int(half)
+    L, st = _ffi.lib(), _ffi.stream_ptr()
+    buf = lambda nbytes: torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
+    pk1, pk2 = buf(L.m3_frnn_pack_bytes(P, n, f16)), buf(L.m3_frnn_pack_bytes(P, n, f16))
+    st1, st2 = buf(L.m3_frnn_stats_bytes(P, h, w)), buf(L.m3_frnn_stats_bytes(P, h, w))
+    for D, pk, stats in ((D1, pk1, st1), (D2, pk2, st2)):
+        _ffi.call("m3_frnn_pack", _ffi.ptr(D), _ffi.ptr(pk), P, n, d, f16, st)
+        _ffi.call("m3_frnn_blockstats", _ffi.ptr(pk), _ffi.ptr(stats), P, h, w, f16, st)
+    ys, xs = torch.arange(sub // 2, h, sub, device=dev), torch.arange(sub // 2, w, sub, device=dev)
+    seeds = (ys[:, None] * w + xs[None, :]).reshape(-1).to(torch.int32)
+    s = seeds.numel()
+    assert (s, n) == (140, 2240)
+    pws = buf(L.m3_frnn_prune_ws_bytes(P, s, h, w, h, w))
+
+    def state():
+        return dict(cur=seeds[None].repeat(P, 1).contiguous(), active=torch.ones((P, s), dtype=torch.uint8, device=dev),
+                    got1=torch.empty((P, s), dtype=torch.int32, device=dev), got2=torch.empty((P, s), dtype=torch.int32, device=dev),
+                    xy2=torch.empty((P, s), dtype=torch.int32, device=dev), keys=torch.zeros((P, s), dtype=torch.int64, device=dev))
+    a, b = state(), state()
+    for r in range(3):
+        _ffi.call("m3_frnn_round", _ffi.ptr(pk1), _ffi.ptr(pk2), _ffi.ptr(a["cur"]), _ffi.ptr(a["active"]), _ffi.ptr(a["got1"]),
+                  _ffi.ptr(a["got2"]), _ffi.ptr(a["xy2"]), _ffi.ptr(a["keys"]), P, s, n, n, f16, st)
+        _ffi.call("m3_frnn_round_pruned", _ffi.ptr(pk1), _ffi.ptr(pk2), _ffi.ptr(st1), _ffi.ptr(st2), _ffi.ptr(b["cur"]),
+                  _ffi.ptr(b["active"]), _ffi.ptr(b["got1"]), _ffi.ptr(b["got2"]), _ffi.ptr(b["xy2"]), _ffi.ptr(b["keys"]),
+                  None, None, _ffi.ptr(pws), P, s, h, w, h, w, f16, st)
+        for k in ("cur", "active", "got1", "got2"):
+            assert torch.equal(a[k], b[k]), (r, k)
+        assert not bool(a["keys"].any()) and not bool(b["keys"].any())
+        if r == 0:                                                   # round 0 found pairs and left work for the later rounds
+            assert int((a["got1"] >= 0).sum(1).min()) > 100 and int(a["active"].sum(1).min()) >= 10
+
+
+@pytest.mark.parametrize("order", ["large_to_small", "small_to_large"])
+def test_fast_reciprocal_nn_between_maps_of_different_sizes(dev, order):
+    """N1 != N2 (48 x 64 against 40 x 56, both ways; P = 2): the query side and the database side of every search differ in
+    rows per pair, in map shape and in block count.  Block-bound and brute-force matchers agree on every output, and per
+    pair the device loop returns the set of the per-round host loop.  The CPU oracle finds 189 / 183 pairs from the 192
+    seeds of the larger map and 140 / 139 from the 140 seeds of the smaller one."""
+    sc = synthetic.geometric_pair(48, 64, seed=3, batch=2)
+    D1 = torch.from_numpy(sc["D21"]).to(dev)
+    D2 = torch.from_numpy(np.ascontiguousarray(sc["D11"][:, :40, :56])).to(dev)
+    floor = 170
+    if order == "small_to_large":
+        D1, D2, floor = D2, D1, 130
+    fast = matching.fast_reciprocal_nn_maps(D1, D2, subsample=4, max_iter=4, prune=True)
+    brute = matching.fast_reciprocal_nn_maps(D1, D2, subsample=4, max_iter=4, prune=False)
+    _same_maps(fast, brute)
+    assert int(brute["count"].min()) > floor
+    for p in range(2):
+        j1, j2 = matching.fast_reciprocal_nn_device(D1[p], D2[p], subsample=4, max_iter=4)
+        i1, i2 = matching.fast_reciprocal_nn(D1[p], D2[p], subsample=4, max_iter=4)
+        got = set(zip(j1.cpu().tolist(), j2.cpu().tolist()))
+        assert got == set(zip(i1.cpu().tolist(), i2.cpu().tolist())) and len(got) == int(brute["count"][p])
+
+
 def test_match_dispatches_to_the_fast_reciprocal_nn_matcher(dev):
     """matching.match with matching.use_fast_nn (the switch is this repo's; the contract is matching.py:12-38's): idx / valid
     in the dense matchers' format - valid exactly where a reciprocal pair ends AND the 3-D points agree within dist_thresh;
