@@ -451,6 +451,44 @@ int m3_render_map(const float *const *X, const float *const *C, const void *cons
                   int bg_g, int bg_b, void *ws, int64_t ws_bytes, uint8_t *rgb, float *depth, int64_t *index,
                   void *stream);
 
+/* ---------------------------------------------------------- camera intrinsics */
+
+/* Focal length of every keyframe from its own pointmap.  Host side: mast3r_slam/intrinsics.py.
+ *
+ * The map arrives as for m3_map_export_*: device tables X[k] -> float [N,3] (points in the keyframe's own camera frame)
+ * and C[k] -> float [N], Nk [K] int32, N = H * W pixels in row-major order.  The pinhole's principal point is (cx, cy)
+ * in pixel-centre coordinates; fx = fy = f is estimated per keyframe.
+ *
+ *   valid(k, n)   <=>  the export rule C[k][n] / (float)Nk[k] > thresh (IEEE fp32 divide, strict, NaN fails;
+ *                      use_thresh = 0 skips it), x, y, z of X[k][n] all finite, and z > z_min (strict).  No other
+ *                      pixel contributes to any sum.
+ *   per pixel          float64 from the fp32 inputs, every operation separately rounded:
+ *                      u = (n % W) - cx, v = (n / W) - cy, a = x / z, b = y / z, pq = a u + b v, qq = a a + b b
+ *   pass 0             f_0 = sum pq / sum qq                                   (the least-squares focal)
+ *   pass i = 1..iters  d = sqrt((u - f a)^2 + (v - f b)^2) at f = f_{i-1}, w = 1 / (d > 1e-8 ? d : 1e-8),
+ *                      f_i = sum w pq / sum w qq                               (Weiszfeld step of sum d -> min)
+ *   last pass          the mean of d at f = f_iters
+ *   out[k]             double [4]: f_iters, f_0, the number of valid pixels, the mean d in pixels.  No valid pixel:
+ *                      (NaN, NaN, 0, NaN); a zero denominator gives what IEEE division gives; nothing is clamped.
+ *
+ * m3_focal_launches(iters) = iters + 3 launches are queued (iters + 2 passes over the pixels and one that finishes the
+ * mean), whatever K and N are (0: iters out of range); there is no host synchronisation, no allocation and no copy, so
+ * the call can be captured into a graph.  There are no floating-point atomics: a workgroup reduces a fixed tile of one
+ * keyframe (4096 pixels; larger only where a keyframe would otherwise have more than 256 tiles) in a fixed order -
+ * per thread in pixel order, a shuffle tree per wave, the waves in order through LDS - and stores its sums to ws; the
+ * workgroups of the next pass each add their keyframe's tile sums in ascending tile order to get f.  The bytes of out
+ * are therefore the same on every call, and a keyframe's row does not depend on which keyframes share the call.
+ * 16-byte loads are used per keyframe when N % 4 == 0 and its arrays are 16-byte aligned; any other input takes
+ * scalar loads, with the same result.
+ * ws: m3_focal_ws_bytes(K, N) bytes (0 = unsupported shape: K * N must stay below 2^31 and K * tiles within 2^22),
+ * 16-byte aligned, contents ignored on entry.  M3_ERR_INVALID_ARG for H * W != N, iters outside 0 ... 64, a negative
+ * or NaN z_min, a non-finite cx / cy or a short ws.  K = 0 queues nothing and returns M3_OK. */
+int64_t m3_focal_ws_bytes(int K, int N);
+int m3_focal_launches(int iters);
+int m3_focal_estimate(const float *const *X, const float *const *C, const int32_t *Nk, int K, int N, int H, int W,
+                      int use_thresh, float thresh, double cx, double cy, float z_min, int iters, void *ws,
+                      int64_t ws_bytes, double *out, void *stream);
+
 /* -------------------------------------------------------------- preprocessing */
 
 /* Frame preprocessing in front of m3_patchify16_dt (mast3r_utils.py:132-207 resize_img).  Host side:

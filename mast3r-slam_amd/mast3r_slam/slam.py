@@ -19,7 +19,7 @@ from typing import Callable, Iterable, Optional
 
 import torch
 
-from . import export, render
+from . import export, intrinsics, render
 from .config import get_config
 from .dataloader import Dataset, load_dataset
 from .frame import Keyframes, create_frame
@@ -225,12 +225,18 @@ class SLAM:
             poses = torch.cat(self.poses) if self.poses else torch.empty((0, 8))
         return export.save_trajectory(path, ts, poses, format=format)
 
+    def estimate_intrinsics(self, **kw) -> intrinsics.IntrinsicsEstimate:
+        """intrinsics.estimate_intrinsics over the keyframes: one pinhole for the map from the pointmaps themselves.
+        Opt-in: nothing in the loop uses it."""
+        return intrinsics.estimate_intrinsics(self.keyframes, **kw)
+
     # ------------------------------------------------------------------ headless views (no counterpart: the reference
     # hands its callback to a desktop GUI)
     def render_view(self, T_WC: Optional[torch.Tensor] = None, K=None, size=None, **kw):
         """render.render_map over the keyframes: (rgb uint8 [H,W,3], depth float32 [H,W][, index]).  Defaults: the pose
         the last processed frame was given, the keyframes' own image size, and the keyframes' intrinsics moved to
-        `size` (render.default_intrinsics without calibration)."""
+        `size` (render.default_intrinsics without calibration).  K = "estimate": the pinhole of estimate_intrinsics()
+        moved to `size` (one host read of the per-keyframe focals)."""
         frames = [kf for kf in self.keyframes._frames if kf.X_canon is not None]
         if T_WC is None:
             if not self.poses:
@@ -243,6 +249,11 @@ class SLAM:
             size = own
         if K is None and own is not None and self.keyframes.get_intrinsics() is not None:
             K = render.scaled_intrinsics(self.keyframes.get_intrinsics(), own, size)
+        if isinstance(K, str):
+            if K != "estimate":
+                raise ValueError(f"render_view: K must be intrinsics, None or 'estimate', got {K!r}")
+            est = self.estimate_intrinsics()
+            K = render.scaled_intrinsics(est.K, est.size, size)
         return render.render_map(self.keyframes, T_WC, K, size, **kw)
 
     def save_view(self, path, T_WC: Optional[torch.Tensor] = None, K=None, size=None, **kw) -> None:
