@@ -299,6 +299,279 @@ def uniform_expected64(v: torch.Tensor, tq: int, kv_batch_shift: int = 0) -> tor
     return v.double().roll(-kv_batch_shift, 0).mean(1, keepdim=True).expand(-1, tq, -1)
 
 
+# ------------------------------------------------------------------------------------------ integer convolution
+def int_conv(b: int, h: int, w: int, cin: int, cout: int, seed: int, groups: int = 1):
+    """x [groups, b, h, w, cin] in [-3, 3] with a few -0.0, W [groups, cout, 3, 3, cin] in [-3, 3], bias [groups, cout] in
+    [-64, 64]: float32 holders of integers, exact in bf16 and fp16, its own weights and bias per group.  With cin <= 256 every
+    partial sum of conv + bias + residual (integers in [-64, 64]) stays below 9 * 256 * 9 + 128 < 2^24: fp32 accumulation is
+    exact in any order - per tap, per channel slice, per split-K plane."""
+    assert cin <= 256
+    g = _gen(seed)
+    x = torch.randint(-3, 4, (groups, b, h, w, cin), generator=g).float()
+    wt = torch.randint(-3, 4, (groups, cout, 3, 3, cin), generator=g).float()
+    bias = torch.randint(-64, 65, (groups, cout), generator=g).float()
+    flat = x.view(-1)
+    flat[torch.randint(0, flat.numel(), (max(4, flat.numel() // 97),), generator=g)] = -0.0
+    return x, wt, bias
+
+
+def tap_identity_weights(cout: int, cin: int, single_tap: bool = False) -> torch.Tensor:
+    """[cout, 3, 3, cin]: w[co, ky, kx, ci] = 1 where ci == (co + 7 * (3 ky + kx)) % cin, else 0 - output channel co is the sum
+    of nine known shifted input channels, one per tap.  single_tap: only tap co % 9 is kept, so output (y, x, co) is ONE input
+    element (or the zero padding)."""
+    co = torch.arange(cout)[:, None]
+    t = torch.arange(9)[None, :]
+    ci = (co + 7 * t) % cin                                               # [cout, 9]
+    w = torch.zeros(cout, 9, cin)
+    w.scatter_(2, ci[..., None], 1.0)
+    if single_tap:
+        w = w * (t == co % 9).float()[..., None]
+    return w.view(cout, 3, 3, cin)
+
+
+def conv_out_size(h: int, w: int, stride: int = 1):
+    return (h + 2 - 3) // stride + 1, (w + 2 - 3) // stride + 1
+
+
+def conv_cols(x: torch.Tensor, stride: int = 1) -> torch.Tensor:
+    """x [..., b, h, w, c] -> [..., b * oh * ow, 9 c]: nine shifted (strided) slices of the zero-padded map, concatenated in
+    (ky, kx, ci) order - the layout of W [cout, 3, 3, cin] flattened to [cout, 9 cin]."""
+    h, w, c = x.shape[-3:]
+    oh, ow = conv_out_size(h, w, stride)
+    xp = torch.nn.functional.pad(x, (0, 0, 1, 1, 1, 1))
+    sl = [xp[..., ky:ky + stride * (oh - 1) + 1:stride, kx:kx + stride * (ow - 1) + 1:stride, :] for ky in range(3) for kx in range(3)]
+    return torch.cat(sl, -1).reshape(x.shape[:-4] + (x.shape[-4] * oh * ow, 9 * c))
+
+
+def conv_ref64(x, w, bias=None, resid=None, stride: int = 1, relu_input: bool = False, dtype=torch.float64) -> torch.Tensor:
+    """3x3 convolution, padding 1, of x [..., b, h, w, cin] with w [..., cout, 3, 3, cin] (+ bias [..., cout]) (+ resid
+    [..., b, oh, ow, cout]) -> [..., b, oh, ow, cout] in float64, as shifted slices fed through gemm_ref64: no convolution
+    library, no code shared with the kernels.  relu_input: x is clamped at 0 first.  dtype=torch.float32 is for integer inputs
+    only, where a float32 matmul is exact as well."""
+    b, h, wd, cin = x.shape[-4:]
+    oh, ow = conv_out_size(h, wd, stride)
+    cout = w.shape[-4]
+    xx = x.to(dtype)
+    if relu_input:
+        xx = xx.clamp(min=0)
+    cols = conv_cols(xx, stride)
+    wf = w.to(dtype).reshape(w.shape[:-4] + (cout, 9 * cin))
+    if dtype == torch.float64:
+        ref = gemm_ref64(cols, wf, bias)
+    else:
+        ref = cols @ wf.transpose(-1, -2)
+        if bias is not None:
+            ref = ref + bias.to(dtype).unsqueeze(-2)
+    ref = ref.reshape(x.shape[:-4] + (b, oh, ow, cout))
+    if resid is not None:
+        ref = ref + resid.to(dtype)
+    return ref
+
+
+def conv_max_partial_sum(x, w, bias=None, resid_lim: int = 64, stride: int = 1) -> float:
+    """Upper bound of every partial sum any summation order can form: sum of |x| |w| over the window + |bias| + resid_lim."""
+    m = conv_ref64(x.abs(), w.abs(), None if bias is None else bias.abs(), stride=stride)
+    return float(m.max()) + resid_lim
+
+
+# ----------------------------------------------------------------------------------------------- fused head tail
+def head4_problem(b: int, h: int, w: int, cin: int, seed: int, groups: int = 1, zero_patches: int = 3):
+    """Inputs of the fused head tail relu(conv3x3(x) + bias) [128 channels, fp32 registers] -> W4 [4, 128], b4 -> (xyz, logit)
+    for which r = [xyz, logit] is EXACT in fp32:
+      x      integers in [-a, a], the amplitude a in {1, 2, 3} constant on 4 x 4 blocks (so |xyz| spreads over (0, 6]), and
+             `zero_patches` 5 x 5 patches of zeros per image (the first in the corner (0, 0)): the pixels whose whole window is
+             zero have h = relu(bias);
+      w      sparse: three taps of +-1 per output channel; bias integers in [-2, 1]: h is an integer in [0, 10];
+      W4     integers in [-8, 8] times 2^-7 (xyz rows) / 2^-6 (logit row); b4 multiples of 2^-7, chosen so that
+             xyz = relu(bias) . W4^T + b4 = 0 exactly on the all-zero windows (the 1e-8 clamp branch); logit bias in [-1, 1].
+    Every product h * W4 is a multiple of 2^-7 below 2^0, every sum of 128 of them below 2^7: 14 bits, exact in any order."""
+    g = _gen(seed)
+    amp = torch.randint(1, 4, (groups, b, (h + 3) // 4, (w + 3) // 4, 1), generator=g)
+    amp = amp.repeat_interleave(4, 2).repeat_interleave(4, 3)[:, :, :h, :w]
+    x = (torch.randint(-3, 4, (groups, b, h, w, cin), generator=g).clamp(-amp, amp)).float()
+    for gi in range(groups):
+        for bi in range(b):
+            for k in range(zero_patches):
+                y0 = 0 if k == 0 else int(torch.randint(0, max(1, h - 4), (1,), generator=g))
+                x0 = 0 if k == 0 else int(torch.randint(0, max(1, w - 4), (1,), generator=g))
+                x[gi, bi, y0:y0 + 5, x0:x0 + 5] = 0.0
+    wt = torch.zeros(groups, 128, 9 * cin)
+    idx = torch.rand(groups, 128, 9 * cin, generator=g).argsort(-1)[..., :3]
+    wt.scatter_(-1, idx, (torch.randint(0, 2, (groups, 128, 3), generator=g) * 2 - 1).float())
+    wt = wt.view(groups, 128, 3, 3, cin)
+    bias = torch.randint(-2, 2, (groups, 128), generator=g).float()
+    w4 = torch.randint(-8, 9, (groups, 4, 128), generator=g).float() * 2.0 ** -7
+    w4[:, 3] *= 2.0
+    b4 = torch.zeros(groups, 4)
+    b4[:, :3] = -(torch.relu(bias).double()[:, None, :] * w4[:, :3].double()).sum(-1).float()
+    b4[:, 3] = torch.randint(-128, 129, (groups,), generator=g).float() * 2.0 ** -7
+    return dict(x=x, w=wt, bias=bias, w4=w4, b4=b4)
+
+
+def head4_r64(p, x=None, use_bias: bool = True) -> torch.Tensor:
+    """float64 r = relu(conv(x) + bias) . W4^T + b4, [groups, b, h, w, 4]; x: another input map for the same weights."""
+    hmap = torch.relu(conv_ref64(p["x"] if x is None else x, p["w"], p["bias"] if use_bias else None))
+    return hmap @ p["w4"].double().transpose(-1, -2)[:, None, None] + p["b4"].double()[:, None, None, None, :]
+
+
+def head4_expected64(r64: torch.Tensor):
+    """pts = xyz / max(|xyz|, 1e-8) * expm1(|xyz|), conf = 1 + exp(logit), float64."""
+    xyz, c = r64[..., :3], r64[..., 3]
+    d = xyz.norm(dim=-1, keepdim=True)
+    return xyz / d.clamp(min=1e-8) * torch.expm1(d), 1.0 + torch.exp(c)
+
+
+def exp_f32_errors(r64: torch.Tensor):
+    """(E_expm1, E_exp): RELATIVE error of float32 numpy expm1 at d = float32(|xyz|) and exp at the logit against float64 at
+    the same float32 argument, maximum over the problem's own r values, times 4 - the margin for the device's expm1f / expf,
+    whose accuracy is not documented.  Measured on the reference side only, like rope_trig_error."""
+    xyz = r64[..., :3].double().numpy()
+    d32 = np.sqrt((xyz * xyz).sum(-1)).astype(np.float32)
+    d32 = d32[d32 > 0]
+    c32 = r64[..., 3].numpy().astype(np.float32)
+    e1 = np.abs(np.expm1(d32).astype(np.float64) - np.expm1(d32.astype(np.float64))) / np.expm1(d32.astype(np.float64))
+    e2 = np.abs(np.exp(c32).astype(np.float64) - np.exp(c32.astype(np.float64))) / np.exp(c32.astype(np.float64))
+    return 4.0 * float(e1.max()), 4.0 * float(e2.max())
+
+
+def head4_bounds(r64: torch.Tensor, e_expm1: float, e_exp: float):
+    """Per-element bounds of the tail at an exact r = (x, y, z, c), e = 2^-24, from the kernels' formula
+        d = sqrtf(x x + y y + z z);  sc = expm1f(d) / fmaxf(d, 1e-8f);  pts = (x, y, z) * sc;  conf = 1 + expf(c):
+      s = x x + y y + z z   three non-negative terms, each product and each of the two sums rounded (or fused): <= 3 e relative
+      d = sqrtf(s)          half of that + the root's own rounding (2 e allowed)                                -> 4 e on d
+      E = expm1f(d)         the argument's error amplified by kappa(d) = d e^d / (e^d - 1) (in [1, d + 1)): 4 e kappa,
+                            plus the function's own error e_expm1 (measured, exp_f32_errors)
+      sc = E / d            d's 4 e again + the division (2 e allowed);  pts = x * sc: one rounding
+    pts:  |ref| ((4 kappa + 7) e + e_expm1).   d = 0: expm1f(0) = 0, sc = 0, pts = 0 exactly - the bound is 0 there.
+    conf: e_exp exp(c) + 2 e (1 + exp(c)) - the function's error and the rounding of the sum (one rounding; two allowed)."""
+    e = 2.0 ** -24
+    xyz, c = r64[..., :3], r64[..., 3]
+    d = xyz.norm(dim=-1, keepdim=True)
+    kappa = torch.where(d > 0, d * torch.exp(d) / torch.expm1(d).clamp(min=1e-300), torch.ones_like(d))
+    pts, conf = head4_expected64(r64)
+    return pts.abs() * ((4 * kappa + 7) * e + e_expm1), e_exp * torch.exp(c) + 2 * e * (1 + torch.exp(c))
+
+
+def head4_f32(r64: torch.Tensor):
+    """The tail's formula in float32 on the CPU, operation by operation (numpy)."""
+    r = r64.numpy().astype(np.float32)
+    assert np.array_equal(r.astype(np.float64), r64.numpy())
+    x, y, z, c = r[..., 0], r[..., 1], r[..., 2], r[..., 3]
+    s = ((x * x).astype(np.float32) + (y * y).astype(np.float32)).astype(np.float32) + (z * z).astype(np.float32)
+    d = np.sqrt(s.astype(np.float32)).astype(np.float32)
+    sc = (np.expm1(d).astype(np.float32) / np.maximum(d, np.float32(1e-8))).astype(np.float32)
+    pts = np.stack([x * sc, y * sc, z * sc], -1).astype(np.float32)
+    conf = (np.float32(1.0) + np.exp(c).astype(np.float32)).astype(np.float32)
+    return torch.from_numpy(pts), torch.from_numpy(conf)
+
+
+# ------------------------------------------------------------------------------------ x2 align-corners upsample
+def const_map(b: int, h: int, w: int, c: int, seed: int, groups: int = 1):
+    """v [groups, b, c] integers in [-3, 3] (its own per group, batch item and channel) and the map x[g, b, :, :, c] = v."""
+    v = torch.randint(-3, 4, (groups, b, c), generator=_gen(seed)).float()
+    return v, v[:, :, None, None, :].expand(groups, b, h, w, c).contiguous()
+
+
+def quarter_values(shape, seed: int) -> torch.Tensor:
+    """Multiples of 1/4 within [-4, 4]: 6 bits, exact in bf16 and fp16."""
+    return torch.randint(-16, 17, tuple(shape), generator=_gen(seed)).float() / 4.0
+
+
+def upsample_coords_f32(n_in: int, n_out: int, n_full: int = 0):
+    """The kernels' coordinate arithmetic in float32 for output indices 0 .. n_out - 1 of the FULL x2 map (n_full = 2 n_in):
+    s = (float)(n_in - 1) / (float)(n_full - 1), f = i * s, i0 = min((int) f, n_in - 1), i1 = min(i0 + 1, n_in - 1), w = f - i0.
+    Returns (i0, i1, w) as numpy arrays (w float32)."""
+    n_full = n_full or 2 * n_in
+    s = np.float32(n_in - 1) / np.float32(n_full - 1) if n_full > 1 else np.float32(0)
+    f = (np.arange(n_out).astype(np.float32) * s).astype(np.float32)
+    i0 = np.minimum(f.astype(np.int64), n_in - 1)
+    i1 = np.minimum(i0 + 1, n_in - 1)
+    return i0, i1, (f - i0.astype(np.float32)).astype(np.float32)
+
+
+def blend_f32(a, b, w):
+    """a * (1 - w) + b * w in float32, operation by operation (numpy float32 arrays)."""
+    one_m = (np.float32(1) - w).astype(np.float32)
+    return ((a * one_m).astype(np.float32) + (b * w).astype(np.float32)).astype(np.float32)
+
+
+def upsample2x_f32(x: torch.Tensor, oh: int = 0, ow: int = 0) -> torch.Tensor:
+    """The kernels' x2 upsample of x [..., h, w, c] in float32 on the CPU: float32 coordinates, horizontal blends, then the
+    vertical blend; cropped to (oh, ow).  Not rounded to 16 bits."""
+    h, w = x.shape[-3:-1]
+    oh, ow = oh or 2 * h, ow or 2 * w
+    y0, y1, wy = upsample_coords_f32(h, oh)
+    x0, x1, wx = upsample_coords_f32(w, ow)
+    xn = x.numpy().astype(np.float32)
+    wxb, wyb = wx[:, None], wy[:, None, None]
+    top = blend_f32(xn[..., y0, :, :][..., :, x0, :], xn[..., y0, :, :][..., :, x1, :], wxb)
+    bot = blend_f32(xn[..., y1, :, :][..., :, x0, :], xn[..., y1, :, :][..., :, x1, :], wxb)
+    return torch.from_numpy(blend_f32(top, bot, wyb))
+
+
+def _nbr_max(d: torch.Tensor, dim: int) -> torch.Tensor:
+    """max over positions i - 1, i, i + 1 along dim."""
+    n = d.shape[dim]
+    lo = torch.cat([d.narrow(dim, 0, 1), d.narrow(dim, 0, n - 1)], dim)
+    hi = torch.cat([d.narrow(dim, 1, n - 1), d.narrow(dim, n - 1, 1)], dim)
+    return torch.maximum(d, torch.maximum(lo, hi))
+
+
+def upsample2x_ref64(x: torch.Tensor, oh: int = 0, ow: int = 0):
+    """float64 bilinear x2 upsample (align_corners) of x [..., h, w, c] with the EXACT weights: output index i reads source
+    coordinate i (n - 1) / (2 n - 1).  Returns (ref, t): t is the allowance for the kernels' fp32 arithmetic,
+        t = 2^-23 h Sy + 2^-23 w Sx + 16 * 2^-24 A:
+    the coordinate f = i * s carries two roundings (s, then the product), at most 2^-23 n absolute; the blend is continuous and
+    piecewise linear, so a coordinate error moves the value by at most the error times the local slope - Sy / Sx = the
+    largest |difference of vertically / horizontally adjacent source pixels| over the cell and its neighbours (a floor that
+    lands on the other side of an integer evaluates the neighbouring cell, at a weight within 2^-23 n of 0 or 1); the three
+    blends are <= 8 roundings relative to A = the largest |corner| (16 allowed, FMA contraction included)."""
+    h, w = x.shape[-3:-1]
+    oh, ow = oh or 2 * h, ow or 2 * w
+    xd = x.double()
+
+    def coords(n, n_out):
+        f = torch.arange(n_out, dtype=torch.float64) * (n - 1) / (2 * n - 1)
+        i0 = f.floor().long().clamp(max=n - 1)
+        return i0, (i0 + 1).clamp(max=n - 1), f - i0
+    y0, y1, wy = coords(h, oh)
+    x0, x1, wx = coords(w, ow)
+    rows = lambda t, i: t.index_select(-3, i)
+    cols = lambda t, i: t.index_select(-2, i)
+    wxb, wyb = wx[:, None], wy[:, None, None]
+    top = cols(rows(xd, y0), x0) * (1 - wxb) + cols(rows(xd, y0), x1) * wxb
+    bot = cols(rows(xd, y1), x0) * (1 - wxb) + cols(rows(xd, y1), x1) * wxb
+    ref = top * (1 - wyb) + bot * wyb
+    zy, zx = torch.zeros_like(xd[..., :1, :, :]), torch.zeros_like(xd[..., :, :1, :])
+    dy = torch.cat([(xd[..., 1:, :, :] - xd[..., :-1, :, :]).abs(), zy], -3)      # dy[y] = |x[y + 1] - x[y]| (0 in the last row)
+    dx = torch.cat([(xd[..., :, 1:, :] - xd[..., :, :-1, :]).abs(), zx], -2)
+    sy = _nbr_max(_nbr_max(dy, -3), -2)                                              # over the cell's two columns and row neighbours
+    sx = _nbr_max(_nbr_max(dx, -2), -3)
+    amax = _nbr_max(_nbr_max(xd.abs(), -3), -2)
+    g = lambda t: cols(rows(t, y0), x0)
+    t = 2.0 ** -23 * (h * g(sy) + w * g(sx)) + 16 * 2.0 ** -24 * g(amax)
+    return ref, t
+
+
+def upsample_bound(ref64: torch.Tensor, t: torch.Tensor, dt) -> torch.Tensor:
+    """One rounding to the 16-bit type of a value within t of ref64: u (|ref| + t) + t, or half the spacing of the type's
+    subnormals where that is larger (2^-25 in fp16: a blend may cancel to below 2^-14)."""
+    fi = torch.finfo(dt)
+    return (fi.eps / 2 * (ref64.abs() + t)).clamp(min=fi.smallest_normal * fi.eps / 2) + t
+
+
+def single_tap_gather(m: torch.Tensor, cout: int) -> torch.Tensor:
+    """What a convolution with tap_identity_weights(cout, cin, single_tap=True) makes of the map m [..., h, w, cin]: output
+    (y, x, co) = m[y + ky - 1, x + kx - 1, (co + 7 t) % cin] with t = co % 9 = 3 ky + kx, zero outside the map."""
+    h, w, cin = m.shape[-3:]
+    mp = torch.nn.functional.pad(m, (0, 0, 1, 1, 1, 1))
+    out = []
+    for co in range(cout):
+        t = co % 9
+        out.append(mp[..., t // 3:t // 3 + h, t % 3:t % 3 + w, (co + 7 * t) % cin])
+    return torch.stack(out, -1)
+
+
 # ---------------------------------------------------------------------------------------------------- checker
 def ulp_step(x: torch.Tensor) -> torch.Tensor:
     """x moved by one unit in the last place of its own type, away from zero (x finite, of a 16-bit type or float32)."""
@@ -306,10 +579,22 @@ def ulp_step(x: torch.Tensor) -> torch.Tensor:
     return (x.contiguous().view(it) + 1).view(x.dtype)
 
 
-def assert_equal_elementwise(out: torch.Tensor, ref: torch.Tensor, what: str, max_report: int = 8):
+def _where(r: int, c: int, hw) -> str:
+    """Position of element (row r, column c) in a report; hw = (h, w) of an NHWC map adds (b, y, x, channel) and the position
+    inside a 16 x 32 output tile of the direct convolution kernels."""
+    s = f"row {r} (%256 = {r % 256}) col {c} (%256 = {c % 256})"
+    if hw is not None:
+        h, w = hw
+        y, x = (r // w) % h, r % w
+        s += f" = (b {r // (h * w)}, y {y}, x {x}, ch {c}) y%16 = {y % 16} x%32 = {x % 32}"
+    return s
+
+
+def assert_equal_elementwise(out: torch.Tensor, ref: torch.Tensor, what: str, max_report: int = 8, hw=None):
     """`out` must equal `ref` element for element (ref is cast to out's dtype first: one round to nearest even when it is the
     float64 result).  On failure: how many elements differ and the first few as (row, column, got, expected) with
-    row % 256 / column % 256, so the tile position is readable.  Leading dimensions are folded into the row."""
+    row % 256 / column % 256, so the tile position is readable.  Leading dimensions are folded into the row.  hw = (h, w):
+    out is an NHWC map [..., h, w, channels]; the report adds (b, y, x, channel) and y % 16, x % 32."""
     assert tuple(out.shape) == tuple(ref.shape), f"{what}: shape {tuple(out.shape)} vs {tuple(ref.shape)}"
     exp = ref.to(device=out.device).to(out.dtype)
     if torch.equal(out, exp):
@@ -323,12 +608,12 @@ def assert_equal_elementwise(out: torch.Tensor, ref: torch.Tensor, what: str, ma
     cols_bad = int(bad.any(0).sum())
     lines = []
     for r, c in idx[:max_report].tolist():
-        lines.append(f"  row {r} (%256 = {r % 256}) col {c} (%256 = {c % 256}): got {float(o2[r, c])!r} expected {float(e2[r, c])!r}")
+        lines.append(f"  {_where(r, c, hw)}: got {float(o2[r, c])!r} expected {float(e2[r, c])!r}")
     raise AssertionError(f"{what}: {nbad} of {o2.numel()} elements differ ({rows_bad} rows, {cols_bad} columns touched); first "
                          f"{len(lines)}:\n" + "\n".join(lines))
 
 
-def assert_within(out: torch.Tensor, ref64: torch.Tensor, bound: torch.Tensor, what: str, max_report: int = 8):
+def assert_within(out: torch.Tensor, ref64: torch.Tensor, bound: torch.Tensor, what: str, max_report: int = 8, hw=None):
     """|out - ref64| <= bound per element (float64 on out's device); same report as assert_equal_elementwise."""
     d = (out.double() - ref64.to(out.device)).abs()
     bnd = bound.to(out.device)
@@ -338,7 +623,7 @@ def assert_within(out: torch.Tensor, ref64: torch.Tensor, bound: torch.Tensor, w
     cols = out.shape[-1]
     idx = bad.reshape(-1, cols).nonzero()
     o2, r2, d2, b2 = out.reshape(-1, cols), ref64.to(out.device).reshape(-1, cols), d.reshape(-1, cols), bnd.reshape(-1, cols)
-    lines = [f"  row {r} (%256 = {r % 256}) col {c} (%256 = {c % 256}): got {float(o2[r, c])!r} expected {float(r2[r, c])!r} "
+    lines = [f"  {_where(r, c, hw)}: got {float(o2[r, c])!r} expected {float(r2[r, c])!r} "
              f"|diff| {float(d2[r, c]):.3e} > bound {float(b2[r, c]):.3e}" for r, c in idx[:max_report].tolist()]
     raise AssertionError(f"{what}: {int(idx.shape[0])} of {out.numel()} elements outside their bound; worst diff / bound = "
-                         f"{float((d / bnd).max()):.3f}; first {len(lines)}:\n" + "\n".join(lines))
+                         f"{float((d / bnd.clamp(min=1e-300)).max()):.3f}; first {len(lines)}:\n" + "\n".join(lines))

@@ -230,6 +230,229 @@ def test_within_checker_reports_position():
         X.assert_within(out, ref, torch.full_like(ref, 1.0), "nan")
 
 
+# ------------------------------------------------------------------------------------------ integer convolution
+def _conv2d64(x, w, bias, stride, relu_input=False):
+    """torch's own float64 convolution of NHWC x [b,h,w,c] with w [cout,3,3,cin]."""
+    import torch.nn.functional as F
+    xx = x.double().clamp(min=0) if relu_input else x.double()
+    y = F.conv2d(xx.permute(0, 3, 1, 2), w.double().permute(0, 3, 1, 2), None if bias is None else bias.double(), stride=stride, padding=1)
+    return y.permute(0, 2, 3, 1)
+
+
+@pytest.mark.parametrize("shape_stride", [((2, 15, 17, 64, 68), 1), ((1, 15, 17, 64, 68), 2), ((1, 20, 28, 64, 36), 2), ((1, 1, 1, 64, 4), 1)], ids=str)
+def test_shifted_slice_reference_equals_conv2d_in_float64(shape_stride):
+    (b, h, w, cin, cout), s = shape_stride
+    x, wt, bias = X.int_conv(b, h, w, cin, cout, seed=5, groups=2)
+    for dt in DT16:
+        for t in (x, wt, bias):
+            assert torch.equal(t.to(dt).float(), t)
+    assert bool((x == 0).any()) and bool(torch.signbit(x[x == 0]).any())        # a few -0.0 are there
+    assert not torch.equal(wt[0], wt[1]) and not torch.equal(bias[0], bias[1])
+    res = X.randint((2, b) + X.conv_out_size(h, w, s) + (cout,), -64, 64, seed=6)
+    for relu_in in (False, True):
+        ref = X.conv_ref64(x, wt, bias, res, s, relu_in)
+        for g in range(2):
+            assert torch.equal(ref[g], _conv2d64(x[g], wt[g], bias[g], s, relu_in) + res[g].double())
+    # float32 slices + float32 matmul give the same numbers (the reference of the largest GPU case is built that way)
+    assert torch.equal(X.conv_ref64(x, wt, bias, res, s, dtype=torch.float32).double(), X.conv_ref64(x, wt, bias, res, s))
+
+
+def test_integer_convolution_partial_sums_stay_below_2_24():
+    """Largest Cin of the GPU tests (256): the sum of |x| |w| over the window + |bias| + 64 bounds every partial sum any
+    order can form - per tap, per 64-channel slice, per split-K plane; worst case of the ranges and this draw in float64."""
+    assert 9 * 256 * 9 + 128 < 2 ** 24 and 9 * 256 * 9 + 128 < 65504            # ... and the result is inside the fp16 range
+    x, wt, bias = X.int_conv(2, 16, 16, 256, 256, seed=8)
+    m = X.conv_max_partial_sum(x, wt, bias)
+    assert m <= 9 * 256 * 9 + 128 and m < 2 ** 24
+    ref = X.conv_ref64(x, wt, bias)
+    cols, wf = X.conv_cols(x), wt.reshape(1, 256, 9 * 256)
+    acc = torch.zeros(1, 512, 256)
+    for k0 in torch.randperm(36, generator=torch.Generator().manual_seed(1)).tolist():      # K tiles of 64 in a shuffled order, fp32
+        acc = acc + cols[..., k0 * 64:(k0 + 1) * 64] @ wf[..., k0 * 64:(k0 + 1) * 64].transpose(-1, -2)
+    assert torch.equal((acc + bias[:, None]).double().view(ref.shape), ref)
+    with pytest.raises(AssertionError):
+        X.int_conv(1, 4, 4, 512, 8, seed=1)
+
+
+def test_tap_identity_output_is_a_sum_of_nine_known_channels():
+    cin, cout = 64, 36
+    w = X.tap_identity_weights(cout, cin)
+    assert float(w.sum()) == cout * 9 and bool((w.sum(-1) == 1).all())
+    x, _, _ = X.int_conv(1, 6, 7, cin, cout, seed=2)
+    ref = X.conv_ref64(x[0], w)
+    xp = torch.nn.functional.pad(x[0].double(), (0, 0, 1, 1, 1, 1))
+    for co in (0, 5, 35):
+        want = sum(xp[:, ky:ky + 6, kx:kx + 7, (co + 7 * (3 * ky + kx)) % cin] for ky in range(3) for kx in range(3))
+        assert torch.equal(ref[..., co], want)
+    w1 = X.tap_identity_weights(128, 128, single_tap=True)
+    assert float(w1.sum()) == 128 and bool((w1.flatten(1).sum(1) == 1).all())
+    m = torch.randn(2, 6, 8, 128, dtype=torch.float64, generator=torch.Generator().manual_seed(3))
+    assert torch.equal(X.single_tap_gather(m, 128), X.conv_ref64(m, w1))
+
+
+@pytest.mark.parametrize("dt", DT16)
+def test_conv_checker_names_a_moved_element_and_swapped_taps(dt):
+    """One output element moved by one ulp, and two taps of the weights swapped: the checker fails and names the position as
+    (b, y, x, channel) with y % 16 and x % 32.  Swapped taps (0, 0) <-> (0, 1) change every row but y = 0 (where both read
+    padding), the border column x = 0 included (where one of them does)."""
+    b, h, w, cin, cout = 2, 18, 40, 64, 36
+    x, wt, bias = X.int_conv(b, h, w, cin, cout, seed=12)
+    ref = X.conv_ref64(x[0], wt[0], bias[0])
+    out = ref.to(dt)
+    X.assert_equal_elementwise(out, ref, "correct answer", hw=(h, w))
+    bad = out.clone()
+    bad[1, 17, 33, 35] = X.ulp_step(bad[1, 17, 33, 35].reshape(1))[0]
+    rel = float((bad.double() - ref).norm() / ref.norm()) - float((out.double() - ref).norm() / ref.norm())
+    assert rel < 1e-4                                                       # invisible to the whole-tensor norm
+    with pytest.raises(AssertionError) as e:
+        X.assert_equal_elementwise(bad, ref, "one ulp", hw=(h, w))
+    msg = str(e.value)
+    assert f"1 of {b * h * w * cout} elements differ" in msg and "(b 1, y 17, x 33, ch 35) y%16 = 1 x%32 = 1" in msg, msg
+    ws = wt[0].clone()
+    ws[:, 0, 0], ws[:, 0, 1] = wt[0][:, 0, 1], wt[0][:, 0, 0]
+    got = X.conv_ref64(x[0], ws, bias[0]).to(dt)
+    with pytest.raises(AssertionError, match=r"\(b 0, y 1, x 0, ch 0\) y%16 = 1 x%32 = 0") as e:
+        X.assert_equal_elementwise(got, ref, "swapped taps", hw=(h, w), max_report=4)
+    assert f"({b * (h - 1) * w} rows," in str(e.value)
+    # a border row that clamps where it should read zero padding: only rows y = 0 differ, and the report says so
+    xc = torch.cat([x[0][:, :1], x[0]], 1)                                  # row -1 := row 0
+    clamp = X.conv_ref64(xc, wt[0], bias[0])[:, 1:]
+    clamp[:, -1] = ref[:, -1]                                               # (the appended row changed the last row's padding too)
+    with pytest.raises(AssertionError) as e:
+        X.assert_equal_elementwise(clamp.to(dt), ref, "clamped top border", hw=(h, w), max_report=10 ** 6)
+    assert " y 0," in str(e.value) and not any(f" y {k}," in str(e.value) for k in range(1, h))
+
+
+# ----------------------------------------------------------------------------------------------- fused head tail
+HEAD4_CASES = [(1, 50, 120, 64, 170, 1), (2, 32, 48, 128, 80, 2), (1, 16, 16, 128, 32, 2), (1, 48, 80, 128, 128, 2)]     # as the GPU tests build them
+
+
+@pytest.mark.parametrize("case", HEAD4_CASES, ids=str)
+def test_head4_problem_is_exact_and_its_bound_holds_for_float32(case):
+    """r = (xyz, logit) is exact in fp32 in any order, |xyz| spreads over (0, 6] with exact zeros, the logit over [-8, 8]; the
+    float32 evaluation of the kernels' formula, operation by operation, stays inside head4_bounds on its own."""
+    b, h, w, cin, seed, groups = case
+    p = X.head4_problem(b, h, w, cin, seed, groups)
+    for dt in DT16:
+        for k in ("x", "w", "w4"):
+            assert torch.equal(p[k].to(dt).float(), p[k])
+    hmap = torch.relu(X.conv_ref64(p["x"], p["w"], p["bias"]))
+    assert float(hmap.max()) <= 10 and torch.equal(hmap, hmap.round())
+    r64 = X.head4_r64(p)
+    assert torch.equal(r64.float().double(), r64) and torch.equal(r64 * 128, (r64 * 128).round())
+    # the projection in float32, in two other orders (channel halves first; reversed)
+    hf, w4f = hmap.float(), p["w4"][:, None, None]
+    r_a = (hf[..., :64] @ w4f[..., :64].transpose(-1, -2) + hf[..., 64:] @ w4f[..., 64:].transpose(-1, -2)) + p["b4"][:, None, None, None]
+    r_b = hf.flip(-1) @ w4f.flip(-1).transpose(-1, -2) + p["b4"][:, None, None, None]
+    assert torch.equal(r_a.double(), r64) and torch.equal(r_b.double(), r64)
+    assert 128 * 10 * 8 * 2 < 2 ** 24                                       # in units of 2^-7: 14 bits
+    d = r64[..., :3].norm(dim=-1)
+    zeros = int((d == 0).sum())
+    print(f"|xyz|: max {float(d.max()):.3f} zeros {zeros} median {float(d.median()):.3f}; logit in [{float(r64[..., 3].min())}, {float(r64[..., 3].max())}]")
+    assert zeros >= 9 * groups * b and float(d.max()) <= 6.0 and float(d.max()) > 3.0 and float(d[d > 0].min()) < 0.25
+    assert float(r64[..., 3].abs().max()) <= 8.0 and float(r64[..., 3].max()) > 2.0 and float(r64[..., 3].min()) < -2.0
+    e1, e2 = X.exp_f32_errors(r64)
+    print(f"E_expm1 = {e1:.3e} E_exp = {e2:.3e} (4 x float32 numpy against float64)")
+    assert 2.0 ** -24 < e1 < 2e-6 and 2.0 ** -24 < e2 < 2e-6
+    bp, bc = X.head4_bounds(r64, e1, e2)
+    assert float(bp[d == 0].abs().max()) == 0.0                             # the clamp branch: pts must be exactly 0
+    rp, rc = X.head4_expected64(r64)
+    pts, conf = X.head4_f32(r64)
+    worst = float(((pts.double() - rp).abs() / bp.clamp(min=1e-300)).max()), float(((conf.double() - rc).abs() / bc).max())
+    print(f"float32 formula: worst |diff| / bound = {worst[0]:.3f} (pts) {worst[1]:.3f} (conf)")
+    X.assert_within(pts, rp, bp, "float32 tail, pts", hw=(h, w))
+    X.assert_within(conf.unsqueeze(-1), rc.unsqueeze(-1), bc.unsqueeze(-1), "float32 tail, conf", hw=(h, w))
+    # the bound notices xyz scaled by the neighbouring pixel's norm, and a logit one grid step (2^-7) off
+    pb = pts.clone()
+    pb[:, :, :, 1:] = pts[:, :, :, 1:] / rp[:, :, :, 1:].norm(dim=-1, keepdim=True).clamp(min=1e-3) * rp[:, :, :, :-1].norm(dim=-1, keepdim=True)
+    with pytest.raises(AssertionError):
+        X.assert_within(pb, rp, bp, "neighbour's norm", hw=(h, w))
+    with pytest.raises(AssertionError):
+        X.assert_within((1 + torch.exp(r64[..., 3] + 2.0 ** -7)).float().unsqueeze(-1), rc.unsqueeze(-1), bc.unsqueeze(-1), "logit off", hw=(h, w))
+
+
+# ------------------------------------------------------------------------------------ x2 align-corners upsample
+UP_IN_SIZES = sorted({n // 2 for n in (32, 48, 16, 80, 64)} | {11, 1, 5, 8})      # every input extent the GPU tests upsample
+
+
+def _fma32(a, b, c):
+    """float32 fma(a, b, c) through float64 (a b is exact there; the sum is rounded to float64 first: 2^-53, irrelevant here)."""
+    import numpy as np
+    return (a.astype(np.float64) * b.astype(np.float64) + c.astype(np.float64)).astype(np.float32)
+
+
+def test_constant_map_survives_every_blend_weight_that_occurs():
+    """(a): for every float32 weight the kernels compute at the sizes the GPU tests use and every v in [-3, 3], the formula
+    a (1 - w) + b w with a = b = v - both blends, with and without FMA contraction - stays within 4 fp32 ulps of v, 2^7
+    times closer than the nearest 16-bit rounding midpoint, so the upsampled map is v bit for bit in bf16 and fp16."""
+    import numpy as np
+    v = np.arange(-3, 4, dtype=np.float32)[:, None, None]
+    worst = 0.0
+    for n in UP_IN_SIZES:
+        _, _, w = X.upsample_coords_f32(n, 2 * n)
+        assert w.dtype == np.float32 and float(w.min()) >= 0.0 and float(w.max()) < 1.0
+        wx, wy = w[None, :, None], w[None, None, :]
+        one = np.float32(1)
+        for contract in (False, True):
+            if contract:
+                blend = lambda a, b, ww: _fma32(b, ww, (a * (one - ww)).astype(np.float32))
+            else:
+                blend = X.blend_f32
+            row = blend(v, v, wx)
+            out = blend(row, row, wy)
+            worst = max(worst, float(np.abs(out.astype(np.float64) - v).max() / 3.0))
+            for dt in DT16:
+                assert torch.equal(torch.from_numpy(out).to(dt).float(), torch.from_numpy(np.broadcast_to(v, out.shape).copy()))
+    print(f"constant map through both blends: worst relative error {worst:.3e} = {worst / 2.0 ** -23:.2f} ulp")
+    assert worst <= 4 * 2.0 ** -23 and worst * 2 ** 7 < 2.0 ** -12 / 2
+
+
+@pytest.mark.parametrize("dt", DT16)
+@pytest.mark.parametrize("bhw", [(2, 16, 24), (1, 8, 8), (1, 24, 40), (1, 32, 32), (1, 16, 8), (1, 8, 16), (3, 11, 16), (1, 1, 5)], ids=str)
+def test_upsample_bound_holds_for_the_float32_formula_and_sees_a_neighbour(bhw, dt):
+    """(b): the kernels' formula in float32 on the CPU (float32 coordinates, three blends), rounded to 16 bits, stays inside
+    u (|ref| + t) + t of the float64 interpolation with the exact weights - and the same map shifted by ONE source pixel (a
+    patch origin off by one) or with the far edge clamped one pixel early leaves it on most elements; the bound is far below
+    the difference a neighbouring source pixel makes (ratio printed and asserted)."""
+    b, h, w = bhw
+    x = X.quarter_values((b, h, w, 16), seed=h * w)
+    assert torch.equal(x.to(dt).float(), x) and float(x.abs().max()) <= 4.0
+    ref, t = X.upsample2x_ref64(x)
+    bound = X.upsample_bound(ref, t, dt)
+    y32 = X.upsample2x_f32(x)
+    worst = float(((y32.double() - ref).abs() / t.clamp(min=1e-300)).max())
+    print(f"float32 formula against float64: worst |diff| / t = {worst:.3f}")
+    assert bool(((y32.double() - ref).abs() <= t).all())
+    X.assert_within(y32.to(dt), ref, bound, "float32 upsample, rounded", hw=(2 * h, 2 * w))
+    if w > 1:
+        shifted, _ = X.upsample2x_ref64(x.roll(1, 2))                       # every read one source column to the left
+        diff = (shifted - ref).abs()
+        seen = float((diff > bound).double().mean())
+        ratio = float((diff / bound).median())
+        print(f"one source pixel off: {seen:.3f} of the elements leave the bound; median difference / bound = {ratio:.1f}")
+        assert seen > 0.9 and ratio > (50 if dt == torch.bfloat16 else 400)
+        with pytest.raises(AssertionError):
+            X.assert_within(shifted.to(dt), ref, bound, "patch origin off by one", hw=(2 * h, 2 * w))
+        if w > 2:
+            early = x.clone()
+            early[:, :, -1] = x[:, :, -2]                                   # min(.., IW - 2) where min(.., IW - 1) belongs
+            with pytest.raises(AssertionError, match=rf"x {2 * w - 1}, ch"):
+                X.assert_within(X.upsample2x_ref64(early)[0].to(dt), ref, bound, "far-edge clamp", hw=(2 * h, 2 * w), max_report=10 ** 6)
+
+
+def test_upsample_reference_equals_interpolate_in_float64():
+    import torch.nn.functional as F
+    x = X.quarter_values((2, 11, 16, 8), seed=3)
+    ref, _ = X.upsample2x_ref64(x)
+    want = F.interpolate(x.double().permute(0, 3, 1, 2), scale_factor=2, mode="bilinear", align_corners=True).permute(0, 2, 3, 1)
+    assert float((ref - want).abs().max()) < 1e-13
+    crop, _ = X.upsample2x_ref64(x, 21, 31)
+    assert torch.equal(crop, ref[:, :21, :31])
+    v, c = X.const_map(2, 4, 6, 8, seed=1, groups=2)
+    assert not torch.equal(v[0], v[1]) and not torch.equal(v[0, 0], v[0, 1]) and torch.equal(c[1, 1, 3, 5], v[1, 1])
+    assert torch.equal(X.upsample2x_ref64(c)[0], v[:, :, None, None, :].expand(2, 2, 8, 12, 8).double())
+
+
 # ----------------------------------------------------------------------------------------- host-level contracts
 def test_rope_bound_checks_its_promise():
     """ops.rope_bound verifies 0 <= pos and pos < bound once, on the host, before any launch relies on the promise."""
