@@ -417,6 +417,51 @@ int m3_map_voxel_scatter(const float *points, const uint8_t *colors, const int64
                          int64_t ws_bytes, int64_t M2, float *points_out, uint8_t *colors_out, int64_t *index_out,
                          void *stream);
 
+/* ------------------------------------------------------------------ map mesh */
+
+/* Triangle mesh of the keyframe map.  Host side: mast3r_slam/export.py collect_mesh.
+ *
+ * The map arrives as for m3_map_export_*: device tables X[k] -> float [N,3] (points in the keyframe's own camera frame),
+ * C[k] -> float [N], img[k]; poses [K,8], Nk [K], layout M3_MAP_IMG_*; N = H * W in row-major order.  stride s >= 1,
+ * edge_ratio > 0 (fp32), the export's use_thresh / thresh.
+ *
+ *   grid        vertices at pixels (gy * s, gx * s), gy < Hg = ceil(H / s), gx < Wg = ceil(W / s); source index
+ *               k * N + (gy * s) * W + gx * s.  Cells (gy, gx), gy < Hg - 1, gx < Wg - 1, corners a = (gy, gx),
+ *               b = (gy, gx + 1), c = (gy + 1, gx), d = (gy + 1, gx + 1)
+ *   triangles   t = 0 is (a, c, b), t = 1 is (b, c, d), in this order: counter-clockwise seen from the keyframe's
+ *               camera (x right, y down, z forward); the diagonal is always b - c
+ *   valid       the export rule: C[k][n] / (float)Nk[k] > thresh (strict, NaN fails; use_thresh = 0 skips it) and the
+ *               world point s R X + t finite, as the exporter computes it
+ *   edge (p,q)  on the camera-frame points, fp32, every operation separately rounded: dx = p.x - q.x, ...,
+ *               l2 = (dx*dx + dy*dy) + dz*dz, r2 = (x*x + y*y) + z*z per vertex, t2 = edge_ratio * edge_ratio; passes
+ *               iff l2 <= t2 * fminf(r2_p, r2_q) (a NaN on either side fails; no square root)
+ *   kept        a triangle: its three vertices valid and its three edges pass; a vertex: referenced by a kept triangle
+ *   outputs     vertices float [V,3] (world points, the exporter's bytes), colors uint8 [V,3] (the export's colour
+ *               rule), index int64 [V] (source index; may be NULL) in ascending source index; faces int32 [F,3], rows of
+ *               the vertex arrays, in ascending (k, gy, gx, t)
+ *
+ * m3_mesh_count: three launches (two bits per cell from LDS-staged vertex rows and kept triangles per row segment of
+ * 256 cells; used vertices per 1024-point tile; an exclusive scan of both).  Afterwards ws int32 [0] = V and [1] = F: the
+ * host reads both in one copy.  m3_mesh_scatter: two launches (vertices, which also write the vertex -> row remap into
+ * ws; faces, which read it) with the SAME inputs and ws, V and F as read back (both >= 1: the host launches nothing
+ * when F = 0) and outputs of exactly V and F rows.  m3_mesh_launches() = 5 whatever K, H, W and the content are.  No
+ * allocation, no host synchronisation and no atomics: positions are tile / segment offset + rank inside it, so two
+ * calls give identical bytes, and a keyframe's faces depend on the other keyframes only through the row offset.
+ * 16-byte loads are used per keyframe when stride = 1, N % 4 == 0 and its arrays are 16-byte aligned; any other input
+ * takes scalar loads, with the same result.
+ * ws: m3_mesh_ws_bytes(K, H, W, stride) bytes (0 = unsupported: K * H * W and 2 * K * (Hg-1) * (Wg-1) must stay below
+ * 2^31), 16-byte aligned, contents ignored on entry: int32 [4] header, the vertex tile and face segment offsets, int32 remap
+ * per grid vertex, one byte per cell.  K = 0, Hg < 2 or Wg < 2: m3_mesh_count only writes V = F = 0 (the tables may then
+ * be NULL).  M3_ERR_INVALID_ARG for NULL pointers, stride < 1, edge_ratio not > 0 (NaN included) or a short ws. */
+int64_t m3_mesh_ws_bytes(int K, int H, int W, int stride);
+int m3_mesh_launches(void);
+int m3_mesh_count(const float *const *X, const float *const *C, const float *poses, const int32_t *Nk, int K, int H, int W,
+                  int stride, int use_thresh, float thresh, float edge_ratio, void *ws, int64_t ws_bytes, void *stream);
+int m3_mesh_scatter(const float *const *X, const float *const *C, const void *const *img, const float *poses,
+                    const int32_t *Nk, int K, int H, int W, int stride, int use_thresh, float thresh, float edge_ratio,
+                    int layout, void *ws, int64_t ws_bytes, int64_t V, int64_t F, float *vertices, uint8_t *colors,
+                    int32_t *faces, int64_t *index, void *stream);
+
 /* ------------------------------------------------------------- map rendering */
 
 /* Headless renderer of the keyframe map.  Host side: mast3r_slam/render.py.

@@ -38,6 +38,8 @@ PER_FILE = {
     "render.hip": ["-ffp-contract=off"],
     # the per-pixel terms of the focal estimate are separately rounded float64 operations (tests/focal_twin.py)
     "intrinsics.hip": ["-ffp-contract=off"],
+    # the edge test is separately rounded fp32 operations (tests/mesh_twin.py restates them)
+    "mesh.hip": ["-ffp-contract=off"],
 }
 
 

@@ -15,6 +15,11 @@ integer (the kept count M) before it allocates exact-size outputs, and two calls
 choice and a function argument, not a config key: the reference exports every point and has no such constant.  The
 reference also writes ASCII PLY in a Python loop; here the body is one structured numpy array written in binary
 (`binary=False` keeps the ASCII form for small clouds).  CPU tensors raise RuntimeError: there is no CPU path.
+
+collect_mesh triangulates the same keyframes (csrc/mesh.hip): every pointmap is an organised
+H x W grid, so each cell of neighbouring pixels gives two triangles, and a triangle is refused when an edge is long
+against the range of its end points (a depth discontinuity).  Vertices are the exporter's world points and colours;
+save_ply_mesh writes them with a face element.
 """
 from __future__ import annotations
 
@@ -26,10 +31,11 @@ import torch
 
 from . import _ffi
 
-__all__ = ["collect_map", "save_ply", "save_trajectory"]
+__all__ = ["collect_map", "collect_mesh", "save_ply", "save_ply_mesh", "save_trajectory"]
 
 IMG_F32_CHW, IMG_U8_HWC = 0, 1                                         # include/m3slam.h
 _PLY_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")])
+_PLY_FACE_DTYPE = np.dtype([("n", "u1"), ("v", "<i4", (3,))])            # property list uchar int vertex_indices
 
 last_voxel_stats: dict = {}           # table slots / occupied voxels of the most recent voxel pass (tools/bench_map_export.py)
 
@@ -62,11 +68,15 @@ class _MapTables:
     __slots__ = ("k", "n", "layout", "device", "table", "nk", "poses", "hold", "frames")
 
 
+def _with_pointmap(keyframes) -> list:
+    return [f for f in (keyframes._frames if hasattr(keyframes, "_frames") else list(keyframes)) if f.X_canon is not None]
+
+
 def _map_tables(keyframes) -> Optional[_MapTables]:
     """Tables of `keyframes` (a Keyframes or a sequence of Frame; frames without a pointmap are skipped), None when no
     frame has a pointmap.  ValueError for mixed layouts / mismatched sizes or a map beyond 2^31 - 1 points, RuntimeError
     for CPU tensors."""
-    frames = [f for f in (keyframes._frames if hasattr(keyframes, "_frames") else list(keyframes)) if f.X_canon is not None]
+    frames = _with_pointmap(keyframes)
     if not frames:
         return None
     n = frames[0].X_canon.reshape(-1, 3).shape[0]
@@ -155,6 +165,77 @@ def _voxel_thin(points, colors, index, conf, voxel_size: float):
     return p2, c2, i2
 
 
+def _empty_mesh(device, return_index: bool):
+    vertices, colors = _empty(device, False)
+    out = (vertices, colors, torch.empty((0, 3), dtype=torch.int32, device=device))
+    return out + (torch.empty((0,), dtype=torch.int64, device=device),) if return_index else out
+
+
+def _grid_size(frames):
+    """(H, W) of the frames' images; ValueError if they differ between keyframes."""
+    first = None
+    for f in frames:
+        layout, img = _image(f, f.X_canon.reshape(-1, 3).shape[0])
+        hw = tuple(img.shape[1:]) if layout == IMG_F32_CHW else tuple(img.shape[:2])
+        first = first or hw
+        if hw != first:
+            raise ValueError(f"frame {f.frame_id}: image is {hw[0]}x{hw[1]}, the first keyframe's is {first[0]}x{first[1]}")
+    return first
+
+
+def collect_mesh(keyframes, c_conf_threshold: Optional[float] = 1.5, stride: int = 1, edge_ratio: Optional[float] = None,
+                 return_index: bool = False):
+    """Triangle mesh of `keyframes` (as collect_map takes them): vertices float32 [V,3], colours uint8 [V,3], faces
+    int32 [F,3] and (return_index) source indices int64 [V], as device tensors.
+
+    Every keyframe's pointmap is triangulated on its own pixel grid, every `stride`-th row and column: a cell of four
+    neighbouring grid vertices a b / c d gives the triangles (a, c, b) and (b, c, d), counter-clockwise seen from the
+    keyframe's camera.  A vertex is valid by collect_map's rule (c_conf_threshold None keeps every finite point).  An
+    edge (p, q) passes when |p - q|^2 <= edge_ratio^2 * min(|p|^2, |q|^2) on the camera-frame points, a triangle is
+    kept when its vertices are valid and its edges pass, and a vertex is emitted when a kept triangle references it.
+    Vertices come in ascending source index k * H * W + y * W + x with the bytes collect_map gives that point; faces
+    are rows of the vertex arrays in ascending (keyframe, grid row, grid column, triangle).  Meshes of overlapping
+    keyframes are not merged.
+
+    edge_ratio None means 0.02 * stride.  This is the project's choice, an argument like c_conf_threshold: at 512
+    columns and roughly 60 degrees of view a fronto-parallel pixel step is about 0.0023 of the range, so 0.02 admits
+    surfaces stretched about 6x the cell diagonal.  Nobody has tuned it on real data.
+
+    ValueError for stride < 1, edge_ratio <= 0 or keyframes of different image sizes; RuntimeError for CPU tensors."""
+    if int(stride) != stride or stride < 1:
+        raise ValueError(f"stride must be a positive integer, got {stride}")
+    stride = int(stride)
+    ratio = 0.02 * stride if edge_ratio is None else float(edge_ratio)
+    if not ratio > 0.0:
+        raise ValueError(f"edge_ratio must be positive, got {edge_ratio}")
+    frames = _with_pointmap(keyframes)
+    if not frames:
+        return _empty_mesh("cuda" if torch.cuda.is_available() else "cpu", return_index)
+    h, w = _grid_size(frames)
+    m_ = _map_tables(frames)
+    k, dev, table = m_.k, m_.device, m_.table
+    L = _ffi.lib()
+    ws_bytes = int(L.m3_mesh_ws_bytes(k, h, w, stride))
+    if ws_bytes <= 0:
+        raise ValueError(f"{k} keyframes of {h}x{w} at stride {stride} are too many cells for one mesh (limit 2^30 - 1)")
+    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+    use, thr = (0, 0.0) if c_conf_threshold is None else (1, float(c_conf_threshold))
+    st = _ffi.stream_ptr()
+    _ffi.call("m3_mesh_count", _ffi.ptr(table[0]), _ffi.ptr(table[1]), _ffi.ptr(m_.poses), _ffi.ptr(m_.nk), k, h, w, stride,
+              use, thr, ratio, _ffi.ptr(ws), ws_bytes, st)
+    v, f = ws[:8].view(torch.int32).tolist()                            # the one synchronisation: V and F in one copy
+    if f == 0:
+        return _empty_mesh(dev, return_index)
+    vertices = torch.empty((v, 3), dtype=torch.float32, device=dev)
+    colors = torch.empty((v, 3), dtype=torch.uint8, device=dev)
+    faces = torch.empty((f, 3), dtype=torch.int32, device=dev)
+    index = torch.empty((v,), dtype=torch.int64, device=dev) if return_index else None
+    _ffi.call("m3_mesh_scatter", _ffi.ptr(table[0]), _ffi.ptr(table[1]), _ffi.ptr(table[2]), _ffi.ptr(m_.poses),
+              _ffi.ptr(m_.nk), k, h, w, stride, use, thr, ratio, m_.layout, _ffi.ptr(ws), ws_bytes, v, f, _ffi.ptr(vertices),
+              _ffi.ptr(colors), _ffi.ptr(faces), _ffi.ptr(index), st)
+    return (vertices, colors, faces, index) if return_index else (vertices, colors, faces)
+
+
 def _host(a, dtype) -> np.ndarray:
     if isinstance(a, torch.Tensor):
         a = a.detach().cpu().numpy()
@@ -183,6 +264,41 @@ def save_ply(path, points, colors, binary: bool = True) -> int:
             rows = np.concatenate([p.astype(np.float64), c.astype(np.float64)], axis=1)
             np.savetxt(f, rows, fmt="%.6f %.6f %.6f %d %d %d")
     return m
+
+
+def save_ply_mesh(path, vertices, colors, faces, binary: bool = True):
+    """PLY with save_ply's vertex properties plus `element face F` / `property list uchar int vertex_indices`.  binary:
+    two structured arrays (vertices, then faces) in `binary_little_endian 1.0`; else ASCII lines, for small meshes.
+    ValueError when a face index is outside [0, V).  Returns (V, F)."""
+    p = _host(vertices, np.float32).reshape(-1, 3)
+    c = _host(colors, np.uint8).reshape(-1, 3)
+    t = _host(faces, np.int32).reshape(-1, 3)
+    if p.shape[0] != c.shape[0]:
+        raise ValueError(f"{p.shape[0]} vertices but {c.shape[0]} colours")
+    v, f = p.shape[0], t.shape[0]
+    if f and (int(t.min()) < 0 or int(t.max()) >= v):
+        raise ValueError(f"face indices span [{int(t.min())}, {int(t.max())}], the mesh has {v} vertices")
+    header = ("ply\nformat {} 1.0\nelement vertex {}\nproperty float x\nproperty float y\nproperty float z\n"
+              "property uchar red\nproperty uchar green\nproperty uchar blue\nelement face {}\n"
+              "property list uchar int vertex_indices\nend_header\n"
+              ).format("binary_little_endian" if binary else "ascii", v, f)
+    with open(os.fspath(path), "wb") as fh:
+        fh.write(header.encode("ascii"))
+        if binary:
+            body = np.empty(v, dtype=_PLY_DTYPE)
+            body["x"], body["y"], body["z"] = p[:, 0], p[:, 1], p[:, 2]
+            body["red"], body["green"], body["blue"] = c[:, 0], c[:, 1], c[:, 2]
+            body.tofile(fh)
+            tri = np.empty(f, dtype=_PLY_FACE_DTYPE)
+            tri["n"], tri["v"] = 3, t
+            tri.tofile(fh)
+        else:
+            if v:
+                np.savetxt(fh, np.concatenate([p.astype(np.float64), c.astype(np.float64)], axis=1),
+                           fmt="%.6f %.6f %.6f %d %d %d")
+            if f:
+                np.savetxt(fh, t, fmt="3 %d %d %d")
+    return v, f
 
 
 def _sim3_rows(poses: np.ndarray) -> np.ndarray:

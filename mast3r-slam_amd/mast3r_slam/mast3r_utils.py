@@ -15,7 +15,8 @@ Differences, on purpose:
 resize_img (:132-207) is the same host-side PIL preprocessing; resize_img_device (mast3r_slam/preprocess.py) computes
 the same bytes on the device.  The retrieval database (load_retriever :83-114,
 RetrievalDatabase :640-795, simple retrieval only) lives in mast3r_slam/retrieval.py and is re-exported here, as are
-the map and trajectory writers of mast3r_slam/export.py (collect_map, save_ply, save_trajectory; slam.py:320-415) and
+the map, mesh and trajectory writers of mast3r_slam/export.py (collect_map, collect_mesh, save_ply, save_ply_mesh,
+save_trajectory; slam.py:320-415) and
 the headless map renderer of mast3r_slam/render.py (render_map, ViewRecorder and its camera helpers) and the focal
 estimate of mast3r_slam/intrinsics.py (estimate_focal, estimate_intrinsics).
 """
@@ -30,7 +31,7 @@ from .config import get_config
 from .model import Mast3rFull
 from . import matching
 from .retrieval import RetrievalDatabase, load_retriever
-from .export import collect_map, save_ply, save_trajectory
+from .export import collect_map, collect_mesh, save_ply, save_ply_mesh, save_trajectory
 from .camera import CameraModel, load_calibration, undistort_device
 from .preprocess import adjust_intrinsics, resample_tables, resize_geometry, resize_img_device
 from .render import ViewRecorder, behind, default_intrinsics, depth_to_rgb, look_at, render_map, save_image
@@ -40,7 +41,7 @@ __all__ = [
     "load_mast3r", "resize_img", "frame_to_numpy", "downsample", "mast3r_inference_mono", "mast3r_asymmetric_inference",
     "mast3r_symmetric_inference", "mast3r_match_asymmetric", "mast3r_match_symmetric",
     "mast3r_decode_symmetric_batch", "mast3r_match_asymmetric_batch", "load_retriever", "RetrievalDatabase",
-    "collect_map", "save_ply", "save_trajectory",
+    "collect_map", "collect_mesh", "save_ply", "save_ply_mesh", "save_trajectory",
     "resize_img_device", "resize_geometry", "resample_tables", "adjust_intrinsics",
     "render_map", "default_intrinsics", "look_at", "behind", "depth_to_rgb", "save_image", "ViewRecorder",
     "estimate_focal", "estimate_intrinsics", "intrinsics_from_rows", "IntrinsicsEstimate",

@@ -213,6 +213,19 @@ class SLAM:
         points, colors = self.reconstruction(c_conf_threshold, voxel_size)
         return export.save_ply(path, points, colors, binary=binary)
 
+    def mesh(self, c_conf_threshold: Optional[float] = 1.5, stride: int = 1, edge_ratio: Optional[float] = None,
+             return_index: bool = False):
+        """export.collect_mesh over the keyframes: (vertices [V,3] float32, colours [V,3] uint8, faces [F,3] int32
+        [, index [V] int64]).  Opt-in: nothing in the loop uses it."""
+        return export.collect_mesh(self.keyframes, c_conf_threshold=c_conf_threshold, stride=stride, edge_ratio=edge_ratio,
+                                   return_index=return_index)
+
+    def save_mesh(self, path, c_conf_threshold: Optional[float] = 1.5, stride: int = 1,
+                  edge_ratio: Optional[float] = None, binary: bool = True):
+        """The keyframes' triangle mesh as a PLY with a face element; returns (vertices, faces) written."""
+        vertices, colors, faces = self.mesh(c_conf_threshold, stride, edge_ratio)
+        return export.save_ply_mesh(path, vertices, colors, faces, binary=binary)
+
     def save_trajectory(self, path, format: str = "tum", keyframes_only: bool = False) -> int:
         """:354-381.  Default: every processed frame at the pose it was given (results()["poses"]).  keyframes_only:
         the keyframes' current, backend-optimised poses at their own timestamps."""
