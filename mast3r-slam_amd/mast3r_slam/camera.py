@@ -1,7 +1,7 @@
 """Camera calibration: lens models, the undistortion table and the remap on the device in front of
 preprocess.resize_img_device.
 
-The calibrated operators (k_track_accum_calib, m3_constrain_points_to_ray, solve_GN_calib, render_map) assume an ideal
+The calibrated operators (k_track_accum<Calib>, m3_constrain_points_to_ray, solve_GN_calib, render_map) assume an ideal
 pinhole K; a real lens does not obey one.  The split is the one of preprocess.py: the host derives, in float64 and from
 the calibration alone, a table of source coordinates in 1/256 pixel (`CameraModel.undistort_table`, cached), and
 m3_remap_bilinear_u8 (csrc/undistort.hip) applies it with integer arithmetic: identical bytes every time.  The reference

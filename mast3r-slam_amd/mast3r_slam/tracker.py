@@ -61,17 +61,13 @@ def _ws(dev, P=1):
     return torch.empty(P * int(_ffi.lib().m3_track_ws_doubles()), dtype=torch.float64, device=dev)
 
 
-def opt_pose_ray_dist_sim3(Xf, Xk, T_WCf, T_WCk, Qk, valid, cfg=None, fixed_iters: bool = False):
-    """tracker.py:258-324.  Xf [N,3] (gathered at idx_f2k), Xk [N,3], Qk [N(,1)], valid [N(,1)].
-    Returns (T_WCf [8], T_CkCf [8], info float64[4] = iterations, cost, |tau|, status: 0 budget used up /
-    1 converged / 2 solve failed - singular or divergent, pose = the last good one).
-    Batched: Xf [P,N,3] with poses [P,8] solves P independent problems in one launch sequence
-    (outputs [P,8], [P,8], [P,4])."""
-    c = dict(get_config()["tracking"])
-    c.update(cfg or {})
+def _solve_batch(entry, Xf, Xk, T_WCf, T_WCk, Qk, valid, n, tail):
+    """What the two opt_pose_* solves share: [N,..] / [P,N,..] inputs as checked [P,..] tensors (n = points per problem,
+    -1 = taken from Xf), outputs and workspace, the call of `entry` (`tail` = its arguments after P and N), and the
+    unbatched return for unbatched inputs."""
     batched = Xf.dim() == 3
     P = Xf.shape[0] if batched else 1
-    Xf = _ffi.check(Xf.reshape(P, -1, 3), torch.float32, "Xf")
+    Xf = _ffi.check(Xf.reshape(P, n, 3), torch.float32, "Xf")
     n = Xf.shape[1]
     Xk = _ffi.check(Xk.reshape(P, n, 3), torch.float32, "Xk", (P, n, 3))
     Qk = _ffi.check(Qk.reshape(P, n), torch.float32, "Qk", (P, n))
@@ -83,13 +79,24 @@ def opt_pose_ray_dist_sim3(Xf, Xk, T_WCf, T_WCk, Qk, valid, cfg=None, fixed_iter
     out_rel = torch.empty((P, 8), dtype=torch.float32, device=dev)
     info = torch.empty((P, 4), dtype=torch.float64, device=dev)
     ws = _ws(dev, P)
-    _ffi.call("m3_track_gn_ray_dist_batch", _ffi.ptr(Xf), _ffi.ptr(Xk), _ffi.ptr(Qk), _ffi.ptr(v), _ffi.ptr(Tf),
-              _ffi.ptr(Tk), _ffi.ptr(out_f), _ffi.ptr(out_rel), _ffi.ptr(info), _ffi.ptr(ws), P, n,
-              int(c["max_iters"]), float(c["huber"]), float(c["sigma_ray"]), float(c["sigma_dist"]),
-              float(c["rel_error"]), float(c["delta_norm"]), 1 if fixed_iters else 0, _ffi.stream_ptr())
+    _ffi.call(entry, _ffi.ptr(Xf), _ffi.ptr(Xk), _ffi.ptr(Qk), _ffi.ptr(v), _ffi.ptr(Tf), _ffi.ptr(Tk), _ffi.ptr(out_f),
+              _ffi.ptr(out_rel), _ffi.ptr(info), _ffi.ptr(ws), P, n, *tail, _ffi.stream_ptr())
     if batched:
         return out_f, out_rel, info
     return out_f[0], out_rel[0], info[0]
+
+
+def opt_pose_ray_dist_sim3(Xf, Xk, T_WCf, T_WCk, Qk, valid, cfg=None, fixed_iters: bool = False):
+    """tracker.py:258-324.  Xf [N,3] (gathered at idx_f2k), Xk [N,3], Qk [N(,1)], valid [N(,1)].
+    Returns (T_WCf [8], T_CkCf [8], info float64[4] = iterations, cost, |tau|, status: 0 budget used up /
+    1 converged / 2 solve failed - singular or divergent, pose = the last good one).
+    Batched: Xf [P,N,3] with poses [P,8] solves P independent problems in one launch sequence
+    (outputs [P,8], [P,8], [P,4])."""
+    c = dict(get_config()["tracking"])
+    c.update(cfg or {})
+    return _solve_batch("m3_track_gn_ray_dist_batch", Xf, Xk, T_WCf, T_WCk, Qk, valid, -1, (
+        int(c["max_iters"]), float(c["huber"]), float(c["sigma_ray"]), float(c["sigma_dist"]),
+        float(c["rel_error"]), float(c["delta_norm"]), 1 if fixed_iters else 0))
 
 
 _K4_CACHE: dict = {}
@@ -143,29 +150,11 @@ def opt_pose_calib_sim3(Xf, Xk, T_WCf, T_WCk, Qk, valid, K, img_size, cfg=None, 
     c.setdefault("pixel_border", 0); c.setdefault("depth_eps", 0.0)
     c.update(cfg or {})
     h, w = img_size
-    batched = Xf.dim() == 3
-    P = Xf.shape[0] if batched else 1
-    n = h * w
-    Xf = _ffi.check(Xf.reshape(P, n, 3), torch.float32, "Xf", (P, n, 3))
-    Xk = _ffi.check(Xk.reshape(P, n, 3), torch.float32, "Xk", (P, n, 3))
-    Qk = _ffi.check(Qk.reshape(P, n), torch.float32, "Qk", (P, n))
-    v = _ffi.check(valid.reshape(P, n).to(torch.uint8), torch.uint8, "valid", (P, n))
-    Tf = _ffi.check(T_WCf.reshape(-1, 8).expand(P, 8).contiguous(), torch.float32, "T_WCf", (P, 8))
-    Tk = _ffi.check(T_WCk.reshape(-1, 8).expand(P, 8).contiguous(), torch.float32, "T_WCk", (P, 8))
-    dev = Xf.device
-    out_f = torch.empty((P, 8), dtype=torch.float32, device=dev)
-    out_rel = torch.empty((P, 8), dtype=torch.float32, device=dev)
-    info = torch.empty((P, 4), dtype=torch.float64, device=dev)
-    ws = _ws(dev, P)
     k4 = _k4(K)
-    _ffi.call("m3_track_gn_calib_batch", _ffi.ptr(Xf), _ffi.ptr(Xk), _ffi.ptr(Qk), _ffi.ptr(v), _ffi.ptr(Tf), _ffi.ptr(Tk),
-              _ffi.ptr(out_f), _ffi.ptr(out_rel), _ffi.ptr(info), _ffi.ptr(ws), P, n, h, w,
-              ctypes.cast(k4, ctypes.c_void_p), int(c["max_iters"]), float(c["huber"]), float(c["sigma_pixel"]),
-              float(c["sigma_depth"]), float(c["pixel_border"]), float(c["depth_eps"]), float(c["rel_error"]),
-              float(c["delta_norm"]), 1 if fixed_iters else 0, _ffi.stream_ptr())
-    if batched:
-        return out_f, out_rel, info
-    return out_f[0], out_rel[0], info[0]
+    return _solve_batch("m3_track_gn_calib_batch", Xf, Xk, T_WCf, T_WCk, Qk, valid, h * w, (
+        h, w, ctypes.cast(k4, ctypes.c_void_p), int(c["max_iters"]), float(c["huber"]), float(c["sigma_pixel"]),
+        float(c["sigma_depth"]), float(c["pixel_border"]), float(c["depth_eps"]), float(c["rel_error"]),
+        float(c["delta_norm"]), 1 if fixed_iters else 0))
 
 
 def normal_equations(Xf, Xk, T_CkCf, Qk, valid, cfg=None):

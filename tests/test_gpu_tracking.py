@@ -22,12 +22,23 @@ def _problem(h, w, seed, **kw):
     return pr
 
 
-def test_normal_equations_match_oracle(dev):
-    pr = _problem(48, 64, 1)
+def _off4(a, dev):
+    """The array on the device as a contiguous view that starts 4 bytes into a larger buffer: the same values behind a
+    pointer that is not 16-byte aligned."""
+    t = _t(a, dev)
+    buf = torch.empty(t.numel() + 8, dtype=t.dtype, device=dev)
+    v = buf[1:1 + t.numel()].view(t.shape)
+    v.copy_(t)
+    assert v.is_contiguous() and v.data_ptr() % 16 == 4
+    return v
+
+
+def _check_normal_equations(pr, dev, put=_t):
+    """`put` places Xf, Xk and Qk on the device (_t: aligned, _off4: 4 bytes off)."""
     rng = np.random.default_rng(0)
     q = np.array([0.01, -0.02, 0.015, 1.0]); q /= np.linalg.norm(q)
     T = np.concatenate([rng.normal(size=3) * 0.02, q, [1.01]]).astype(np.float32)
-    H, g, cost = tracker.normal_equations(_t(pr["Xf"], dev), _t(pr["Xk"], dev), _t(T, dev), _t(pr["Qk"], dev),
+    H, g, cost = tracker.normal_equations(put(pr["Xf"], dev), put(pr["Xk"], dev), _t(T, dev), put(pr["Qk"], dev),
                                           _t(pr["valid"], dev))
     # oracle: one _solve at the same pose
     Xf = pr["Xf"].astype(np.float64); Xk = pr["Xk"].astype(np.float64)
@@ -43,11 +54,9 @@ def test_normal_equations_match_oracle(dev):
     assert np.allclose(H.cpu().numpy(), H.cpu().numpy().T)
 
 
-@pytest.mark.parametrize("fixed", [False, True])
-def test_gn_loop_matches_oracle(dev, fixed):
-    pr = _problem(48, 64, 2)
-    Tf, Trel, info = tracker.opt_pose_ray_dist_sim3(_t(pr["Xf"], dev), _t(pr["Xk"], dev), _t(pr["T_WCf"], dev),
-                                                    _t(pr["T_WCk"], dev), _t(pr["Qk"], dev), _t(pr["valid"], dev),
+def _check_gn_loop(pr, dev, fixed, put=_t):
+    Tf, Trel, info = tracker.opt_pose_ray_dist_sim3(put(pr["Xf"], dev), put(pr["Xk"], dev), _t(pr["T_WCf"], dev),
+                                                    _t(pr["T_WCk"], dev), put(pr["Qk"], dev), _t(pr["valid"], dev),
                                                     fixed_iters=fixed)
     To, Trel_o, io = ot.opt_pose_ray_dist_sim3(pr["Xf"], pr["Xk"], pr["T_WCf"], pr["T_WCk"], pr["Qk"], pr["valid"],
                                                fixed_iters=10 if fixed else None)
@@ -57,6 +66,33 @@ def test_gn_loop_matches_oracle(dev, fixed):
     assert np.abs(Tf.cpu().numpy() - To).max() < 5e-5
     assert abs(info[1] - io["costs"][-1]) <= 1e-3 * io["costs"][-1]
     assert bool(info[3]) == (not fixed)
+
+
+def test_normal_equations_match_oracle(dev):
+    _check_normal_equations(_problem(48, 64, 1), dev)
+
+
+@pytest.mark.parametrize("fixed", [False, True])
+def test_gn_loop_matches_oracle(dev, fixed):
+    _check_gn_loop(_problem(48, 64, 2), dev, fixed)
+
+
+# The one-point path of k_track_accum (every other ray-distance problem of this file has N % 4 == 0 and aligned tensors):
+# an odd point count, and a four-points-per-lane size whose Xf, Xk and Qk are not 16-byte aligned.
+_ONE_POINT = {"odd_n": (33, 47, _t), "unaligned": (48, 64, _off4)}
+
+
+@pytest.mark.parametrize("case", sorted(_ONE_POINT))
+def test_normal_equations_on_the_one_point_path(dev, case):
+    h, w, put = _ONE_POINT[case]
+    _check_normal_equations(_problem(h, w, 1), dev, put)
+
+
+@pytest.mark.parametrize("fixed", [False, True])
+@pytest.mark.parametrize("case", sorted(_ONE_POINT))
+def test_gn_loop_on_the_one_point_path(dev, case, fixed):
+    h, w, put = _ONE_POINT[case]
+    _check_gn_loop(_problem(h, w, 2), dev, fixed, put)
 
 
 def test_nonidentity_world_poses(dev):
@@ -185,6 +221,31 @@ def test_track_gather_tiled_path_on_coherent_matches(dev):
         assert cnt[b].cpu().tolist() == [int(vo_o.sum()), int(vk_o.sum())]
 
 
+def test_track_gather_four_point_global_path(dev):
+    """k_track_gather<true>: the per-point streams are 16-byte aligned and N % 4 == 0, but the three gathered arrays
+    (Xf_canon, Cf_avg, Qff) are not, so the LDS-staged kernel cannot be used - four points per lane, rows fetched from
+    global memory.  Two problems, negative indices included; every output exact against numpy, counts included."""
+    rng = np.random.default_rng(33)
+    n = 5000
+    Xc = rng.normal(size=(2, n, 3)).astype(np.float32)
+    Cf = rng.uniform(-0.5, 3, (2, n)).astype(np.float32); Ck = rng.uniform(-0.5, 3, (2, n)).astype(np.float32)
+    Qff = rng.uniform(0.5, 4, (2, n)).astype(np.float32); Qkf = rng.uniform(0.5, 4, (2, n)).astype(np.float32)
+    idx = rng.integers(0, n, (2, n)).astype(np.int64)
+    idx[0, 100:140] = -rng.integers(1, n + 1, 40)                         # negative indices wrap by + n
+    idx[1, n - 7:] = -np.arange(1, 8)
+    vm = rng.uniform(size=(2, n)) < 0.8
+    Xf, Qk, vo, vk, cnt = tracker.track_gather(_off4(Xc, dev), _off4(Cf, dev), _t(Ck, dev), _off4(Qff, dev), _t(Qkf, dev),
+                                               _t(idx, dev), _t(vm, dev), 0.0, 1.5)
+    for b in range(2):
+        ii = np.where(idx[b] < 0, idx[b] + n, idx[b])
+        Qk_o = np.sqrt(Qff[b][ii] * Qkf[b])
+        vo_o, vk_o = ot.validity(vm[b], Cf[b][ii], Ck[b], Qk_o, 0.0, 1.5)
+        assert np.array_equal(Xf[b].cpu().numpy(), Xc[b][ii])
+        assert np.array_equal(Qk[b].cpu().numpy(), Qk_o)
+        assert np.array_equal(vo[b].cpu().numpy().astype(bool), vo_o) and np.array_equal(vk[b].cpu().numpy().astype(bool), vk_o)
+        assert cnt[b].cpu().tolist() == [int(vo_o.sum()), int(vk_o.sum())]
+
+
 def test_batched_solve_equals_loop_of_single_solves(dev):
     """P problems in one launch sequence == P separate calls, bit for bit (pairs are independent units)."""
     prs = [_problem(32, 48, 20 + i) for i in range(3)]
@@ -209,7 +270,7 @@ def test_batched_solve_equals_loop_of_single_solves(dev):
 @pytest.mark.parametrize("h,w", [(48, 64), (48, 62), (33, 47)])
 def test_calibrated_tracking_matches_oracle(dev, h, w):
     """opt_pose_calib_sim3 (tracker.py:326-406) vs the float64 oracle; also constrain_points_to_ray.  64-wide rows take the
-    four-points-per-lane path of k_track_accum_calib, widths that are not multiples of 4 (and odd point counts) the
+    four-points-per-lane path of k_track_accum<Calib>, widths that are not multiples of 4 (and odd point counts) the
     one-point path."""
     K = np.array([[float(w), 0, w / 2], [0, float(w), h / 2], [0, 0, 1]], dtype=np.float32)
     pr = synthetic.tracking_problem(h, w, seed=8)
