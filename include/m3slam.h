@@ -496,6 +496,47 @@ int m3_render_map(const float *const *X, const float *const *C, const void *cons
                   int bg_g, int bg_b, void *ws, int64_t ws_bytes, uint8_t *rgb, float *depth, int64_t *index,
                   void *stream);
 
+/* ------------------------------------------------------- multi-view consistency */
+
+/* Geometric consistency of the keyframe map across keyframes.  Host side:
+ * mast3r_slam/consistency.py.
+ *
+ * The map arrives as for m3_map_export_*: device tables X[k] -> float [N,3] (points in the keyframe's own camera frame)
+ * and C[k] -> float [N], poses [K,8] and Nk [K] in DEVICE memory, N = H * W pixels in row-major order.  (fx, fy, cx, cy)
+ * is the pinhole of that grid, integer coordinates are pixel centres.  nbr int32 [K,V] names the keyframes each
+ * keyframe is checked against, -1 = none; 0 <= V <= 255 (V = 0: nbr may be NULL).
+ *
+ *   observation plane  D[j][m] = X[j][m].z when point (j, m) passes the export's confidence test (C[j][m] / (float)Nk[j]
+ *                      > thresh, fp32 divide, strict, NaN fails; use_thresh = 0 skips it), that z is finite and
+ *                      z > z_min; otherwise NaN.  X is in j's camera frame: this is j's observed depth at pixel m
+ *   candidate(k, n)    the export rule: the confidence test and a finite world point p = s R X + t (fp32, as the
+ *                      exporter computes it).  A non-candidate has support = conflict = 0 and is not kept
+ *   per slot v         j = nbr[k][v]; skipped when j < 0, j >= K or j == k.  c = (R_j^T (p - t_j)) * (1 / s_j) by the
+ *                      renderer's formula (the nine entries of R_j^T and 1 / s_j formed in float64 from poses[j] and
+ *                      rounded to fp32; then separately rounded fp32 operations).  Skipped unless c.z > z_min (strict,
+ *                      NaN fails).  px = floorf((fx * (c.x / c.z) + cx) + 0.5f), py likewise; skipped unless
+ *                      0 <= px < W and 0 <= py < H (compared as floats).  d = D[j][py * W + px]; NaN: skipped.
+ *                      fabsf(c.z - d) <= depth_rtol * d: support += 1; else c.z < d: conflict += 1 (j saw through the
+ *                      point); else nothing (the point is occluded in j)
+ *   kept               candidate and support >= min_views and (max_conflicts < 0 or conflict <= max_conflicts)
+ *   outputs            support uint8 [K,N], conflict uint8 [K,N], conf float [K,N] = C[k][n] when kept, else -inf
+ *
+ * m3_consistency_launches() = 3 launches are queued on `stream` (inverse poses, observation planes, count) whatever K,
+ * N and V are; K = 0 queues nothing.  No allocation, no host synchronisation, no atomics and no floating-point
+ * reduction: the call can be captured into a graph and the bytes of every output are the same on every call; a
+ * keyframe's rows depend on itself and the keyframes its row of nbr names, nothing else.  16-byte loads are used per
+ * keyframe when N % 4 == 0 and its arrays are 16-byte aligned; any other input takes scalar loads, with the same result.
+ * ws: m3_consistency_ws_bytes(K, N) bytes (64 per keyframe for the inverse poses, then the planes; 0 = unsupported: K * N
+ * must stay below 2^31), 16-byte aligned, contents ignored on entry.  support and conflict 4-byte aligned, conf 16-byte
+ * aligned.  M3_ERR_INVALID_ARG for NULL pointers, V outside 0 ... 255, depth_rtol outside (0, 1), a negative or NaN
+ * z_min, min_views < 0, max_conflicts < -1, a side beyond 2^24, fx / fy not positive and finite or a short ws. */
+int64_t m3_consistency_ws_bytes(int K, int N);
+int m3_consistency_launches(void);
+int m3_consistency(const float *const *X, const float *const *C, const float *poses, const int32_t *Nk, int K, int H, int W,
+                   int use_thresh, float thresh, float fx, float fy, float cx, float cy, const int32_t *nbr, int V,
+                   float z_min, float depth_rtol, int min_views, int max_conflicts, void *ws, int64_t ws_bytes,
+                   uint8_t *support, uint8_t *conflict, float *conf, void *stream);
+
 /* ---------------------------------------------------------- camera intrinsics */
 
 /* Focal length of every keyframe from its own pointmap.  Host side: mast3r_slam/intrinsics.py.

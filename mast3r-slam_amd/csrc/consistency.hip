@@ -1,0 +1,183 @@
+// Multi-view consistency filter of the keyframe map (mast3r_slam/consistency.py): every exporter
+// candidate (k, n) is projected into the keyframes of its neighbour row and counted as supported (the neighbour saw the
+// same depth there), in conflict (the neighbour saw through it) or neither.  inverse poses -> observation planes ->
+// count; no atomics and no floating-point reductions, so two calls give identical bytes.  Nothing here waits for the
+// host or allocates: poses are read from device memory and the call can be captured into a graph.
+//
+// Compiled with -ffp-contract=off: the camera transform, the projection and the depth test are separately rounded fp32
+// operations (tests/consistency_twin.py restates them).  The world point is the exporter's: map_points.h is included
+// with contraction on, as map_export.hip compiles it.
+#include "common.h"
+#pragma clang fp contract(fast)
+#include "sim3_dev.h"
+#include "map_points.h"
+#pragma clang fp contract(off)
+#include "view_dev.h"
+
+namespace {
+
+constexpr int kInvStride = 16;                // floats per keyframe in the inverse-pose table: kViewWords, padded to 64 bytes
+
+inline int64_t inv_bytes(int K) { return (int64_t)K * kInvStride * 4; }
+
+inline bool shape_ok(int K, int N) {
+    return K >= 0 && N >= 1 && (int64_t)K * N <= 0x7fffffff && (int64_t)K * m3_cdiv(N, kTile) <= (1 << 30);
+}
+
+// One thread per keyframe: the view_inverse of its pose.
+__global__ void __launch_bounds__(kThreads) k_cons_inverse(const float *__restrict__ poses, int K, float *__restrict__ inv) {
+    const int k = blockIdx.x * kThreads + threadIdx.x;
+    if (k >= K) return;
+    float o[kInvStride];
+    view_inverse(poses + 8 * k, o);
+#pragma unroll
+    for (int i = kViewWords; i < kInvStride; ++i) o[i] = 0.f;
+#pragma unroll
+    for (int i = 0; i < kInvStride; i += 4) *(float4 *)(inv + (size_t)kInvStride * k + i) = float4{o[i], o[i + 1], o[i + 2], o[i + 3]};
+}
+
+// Grid as k_export_count.  D[k][n] = X[k][n].z where the point passes the confidence test and z is finite and > z_min,
+// else NaN.
+__global__ void __launch_bounds__(kThreads) k_cons_plane(const float *const *__restrict__ X, const float *const *__restrict__ C,
+                                                          const int32_t *__restrict__ Nk, int N, int tiles, int use_thresh,
+                                                          float thresh, float z_min, float *__restrict__ D) {
+    Tile t = tile_of(N, tiles);
+    if (t.n0 >= N) return;
+    const float *Xk = X[t.k], *Ck = C[t.k];
+    t.vec = t.n0 + kPts <= N && N % 4 == 0 && aligned16(Xk) && aligned16(Ck);
+    float avg[kPts];
+    const unsigned pass = conf_pass(Ck, t, N, (float)Nk[t.k], use_thresh, thresh, avg);
+    float z[kPts];
+    if (t.vec) {
+        const float4 *src = (const float4 *)(Xk + (size_t)3 * t.n0);
+        const float4 a = src[0], b = src[1], c = src[2];
+        z[0] = a.z; z[1] = b.y; z[2] = c.x; z[3] = c.w;
+    } else {
+#pragma unroll
+        for (int j = 0; j < kPts; ++j) z[j] = t.n0 + j < N ? Xk[(size_t)3 * (t.n0 + j) + 2] : 0.f;
+    }
+    float d[kPts];
+#pragma unroll
+    for (int j = 0; j < kPts; ++j) d[j] = (((pass >> j) & 1u) && isfinite(z[j]) && z[j] > z_min) ? z[j] : __builtin_nanf("");
+    float *Dk = D + (size_t)t.k * N + t.n0;
+    if (t.vec) {
+        *(float4 *)Dk = float4{d[0], d[1], d[2], d[3]};                          // D is 16-byte aligned and N % 4 == 0
+    } else {
+#pragma unroll
+        for (int j = 0; j < kPts; ++j)
+            if (t.n0 + j < N) Dk[j] = d[j];
+    }
+}
+
+// Grid as k_export_count: a workgroup belongs to one keyframe, a thread owns 4 consecutive points.  The neighbour loop is
+// outermost; the neighbour index and its inverse pose depend on the workgroup and the slot alone, so they are read
+// through scalar loads (readfirstlane keeps the addresses in SGPRs).  Per pair: the transform, one divide pair, one
+// 4-byte gather from D.
+__global__ void __launch_bounds__(kThreads) k_cons_count(const float *const *__restrict__ X, const float *const *__restrict__ C,
+                                                          const float *__restrict__ poses, const int32_t *__restrict__ Nk,
+                                                          int K, int N, int H, int W, int tiles, int use_thresh, float thresh,
+                                                          float fx, float fy, float cx, float cy,
+                                                          const int32_t *__restrict__ nbr, int V, float z_min, float rtol,
+                                                          int min_views, int max_conflicts, const float *__restrict__ inv,
+                                                          const float *__restrict__ D, uint8_t *__restrict__ support,
+                                                          uint8_t *__restrict__ conflict, float *__restrict__ conf) {
+    Tile t = tile_of(N, tiles);
+    if (t.n0 >= N) return;
+    const float *Xk = X[t.k], *Ck = C[t.k];
+    t.vec = t.n0 + kPts <= N && N % 4 == 0 && aligned16(Xk) && aligned16(Ck);
+    float avg[kPts];
+    unsigned keep = conf_pass(Ck, t, N, (float)Nk[t.k], use_thresh, thresh, avg);
+    V3<float> p[kPts];
+    if (keep) keep = world_points(Xk, t, load_pose<float>(poses + 8 * t.k), keep, p);
+    unsigned sup[kPts] = {0u, 0u, 0u, 0u}, con[kPts] = {0u, 0u, 0u, 0u};
+    if (keep) {
+        const float fW = (float)W, fH = (float)H;
+        const int32_t *row = nbr + (size_t)t.k * V;
+        for (int v = 0; v < V; ++v) {
+            const int j = __builtin_amdgcn_readfirstlane(row[v]);
+            if (j < 0 || j >= K || j == t.k) continue;
+            const float *sv = inv + (size_t)kInvStride * j;
+            const float *Dj = D + (size_t)j * N;
+#pragma unroll
+            for (int i = 0; i < kPts; ++i) {
+                if (!((keep >> i) & 1u)) continue;
+                const V3<float> c = view_point(sv, p[i]);
+                if (!(c.z > z_min)) continue;                                    // NaN fails
+                const float fu = floorf((fx * (c.x / c.z) + cx) + 0.5f), fv = floorf((fy * (c.y / c.z) + cy) + 0.5f);
+                if (!(fu >= 0.f && fu < fW && fv >= 0.f && fv < fH)) continue;   // as floats: u may be huge or NaN
+                const float d = Dj[(int)fv * W + (int)fu];
+                if (!(d == d)) continue;                                         // j has no observation there
+                if (fabsf(c.z - d) <= rtol * d) ++sup[i];
+                else if (c.z < d) ++con[i];
+            }
+        }
+    }
+    float c[kPts];
+    if (t.vec) {
+        const float4 q = *(const float4 *)(Ck + t.n0);
+        c[0] = q.x; c[1] = q.y; c[2] = q.z; c[3] = q.w;
+    } else {
+#pragma unroll
+        for (int i = 0; i < kPts; ++i) c[i] = t.n0 + i < N ? Ck[t.n0 + i] : 0.f;
+    }
+    unsigned ws = 0u, wc = 0u;
+#pragma unroll
+    for (int i = 0; i < kPts; ++i) {
+        const bool kept = ((keep >> i) & 1u) && (int)sup[i] >= min_views && (max_conflicts < 0 || (int)con[i] <= max_conflicts);
+        if (!kept) c[i] = -INFINITY;
+        ws |= sup[i] << (8 * i);
+        wc |= con[i] << (8 * i);
+    }
+    const size_t o = (size_t)t.k * N + t.n0;
+    if (t.vec) {                                                                 // N % 4 == 0: o is a multiple of 4
+        *(unsigned *)(support + o) = ws;
+        *(unsigned *)(conflict + o) = wc;
+        *(float4 *)(conf + o) = float4{c[0], c[1], c[2], c[3]};
+    } else {
+#pragma unroll
+        for (int i = 0; i < kPts; ++i) {
+            if (t.n0 + i >= N) continue;
+            support[o + i] = (uint8_t)sup[i];
+            conflict[o + i] = (uint8_t)con[i];
+            conf[o + i] = c[i];
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t m3_consistency_ws_bytes(int K, int N) {
+    return shape_ok(K, N) ? inv_bytes(K) + (int64_t)K * N * 4 : 0;
+}
+
+int m3_consistency_launches(void) { return 3; }
+
+int m3_consistency(const float *const *X, const float *const *C, const float *poses, const int32_t *Nk, int K, int H, int W,
+                   int use_thresh, float thresh, float fx, float fy, float cx, float cy, const int32_t *nbr, int V,
+                   float z_min, float depth_rtol, int min_views, int max_conflicts, void *ws, int64_t ws_bytes,
+                   uint8_t *support, uint8_t *conflict, float *conf, void *stream) {
+    M3_REQUIRE(H >= 1 && W >= 1 && H <= (1 << 24) && W <= (1 << 24) && (int64_t)H * W <= 0x7fffffff && shape_ok(K, H * W));
+    M3_REQUIRE((use_thresh == 0 || use_thresh == 1) && V >= 0 && V <= 255 && (V == 0 || nbr || K == 0));
+    M3_REQUIRE(fx > 0.f && fy > 0.f && fx < INFINITY && fy < INFINITY && cx - cx == 0.f && cy - cy == 0.f);
+    M3_REQUIRE(z_min >= 0.f && z_min < INFINITY && depth_rtol > 0.f && depth_rtol < 1.f && min_views >= 0 && max_conflicts >= -1);
+    if (K == 0) return M3_OK;
+    const int N = H * W;
+    M3_REQUIRE(X && C && poses && Nk && ws && support && conflict && conf);
+    M3_REQUIRE(((uintptr_t)ws & 15) == 0 && ws_bytes >= m3_consistency_ws_bytes(K, N));
+    M3_REQUIRE(((uintptr_t)support & 3) == 0 && ((uintptr_t)conflict & 3) == 0 && ((uintptr_t)conf & 15) == 0);
+    hipStream_t st = (hipStream_t)stream;
+    float *inv = (float *)ws;
+    float *D = (float *)((char *)ws + inv_bytes(K));
+    const int tiles = m3_cdiv(N, kTile);
+    const dim3 grid(K * tiles), block(kThreads);
+    hipLaunchKernelGGL(k_cons_inverse, dim3(m3_cdiv(K, kThreads)), block, 0, st, poses, K, inv);
+    hipLaunchKernelGGL(k_cons_plane, grid, block, 0, st, X, C, Nk, N, tiles, use_thresh, thresh, z_min, D);
+    hipLaunchKernelGGL(k_cons_count, grid, block, 0, st, X, C, poses, Nk, K, N, H, W, tiles, use_thresh, thresh, fx, fy, cx, cy,
+                       nbr, V, z_min, depth_rtol, min_views, max_conflicts, inv, D, support, conflict, conf);
+    M3_CHECK_LAUNCH("m3_consistency");
+    return M3_OK;
+}
+
+}  // extern "C"

@@ -11,23 +11,11 @@
 #include "sim3_dev.h"
 #include "map_points.h"
 #pragma clang fp contract(off)
+#include "view_dev.h"
 
 namespace {
 
 constexpr unsigned long long kNoKey = ~0ull;  // no source: a depth with these bits is a NaN and never a candidate
-constexpr int kViewWords = 13;                // rows of R_v^T (9), t_v (3), 1 / s_v
-
-// Inverse of the view pose (t, q xyzw, s), formed in float64 and rounded to fp32.  The rotation is the quaternion
-// formula of liegroups/so3.py without normalisation, as export.save_trajectory writes it.
-__device__ __forceinline__ void view_inverse(const float *__restrict__ T, float *__restrict__ o) {
-    const double x = T[3], y = T[4], z = T[5], w = T[6];
-    o[0] = (float)(1.0 - 2.0 * (y * y + z * z)); o[1] = (float)(2.0 * (x * y + w * z)); o[2] = (float)(2.0 * (x * z - w * y));
-    o[3] = (float)(2.0 * (x * y - w * z)); o[4] = (float)(1.0 - 2.0 * (x * x + z * z)); o[5] = (float)(2.0 * (y * z + w * x));
-    o[6] = (float)(2.0 * (x * z + w * y)); o[7] = (float)(2.0 * (y * z - w * x)); o[8] = (float)(1.0 - 2.0 * (x * x + y * y));
-    o[9] = T[0]; o[10] = T[1]; o[11] = T[2];
-    o[12] = (float)(1.0 / (double)T[7]);
-}
-
 // Key buffer to all ones, 16-byte stores.
 __global__ void __launch_bounds__(kThreads) k_render_clear(unsigned long long *__restrict__ keys, int64_t P) {
     const int64_t i = ((int64_t)blockIdx.x * kThreads + threadIdx.x) * 2;
@@ -58,14 +46,11 @@ __global__ void __launch_bounds__(kThreads) k_render_splat(const float *const *_
     V3<float> p[kPts];
     keep = world_points(Xk, t, load_pose<float>(poses + 8 * t.k), keep, p);
     constexpr int R = PS / 2;
-    const float inv_s = sv[12];
 #pragma unroll
     for (int j = 0; j < kPts; ++j) {
         if (!((keep >> j) & 1u)) continue;
-        const float dx = p[j].x - sv[9], dy = p[j].y - sv[10], dz = p[j].z - sv[11];
-        const float x = ((sv[0] * dx + sv[1] * dy) + sv[2] * dz) * inv_s;
-        const float y = ((sv[3] * dx + sv[4] * dy) + sv[5] * dz) * inv_s;
-        const float z = ((sv[6] * dx + sv[7] * dy) + sv[8] * dz) * inv_s;
+        const V3<float> c = view_point(sv, p[j]);
+        const float x = c.x, y = c.y, z = c.z;
         if (!(z > near && z < far)) continue;                                   // NaN fails; near >= 0: z is positive
         const float fu = floorf((fx * (x / z) + cx) + 0.5f), fv = floorf((fy * (y / z) + cy) + 0.5f);
         if (!(fu >= (float)-R && fu < (float)(Wv + R) && fv >= (float)-R && fv < (float)(Hv + R))) continue;

@@ -18,7 +18,8 @@ RetrievalDatabase :640-795, simple retrieval only) lives in mast3r_slam/retrieva
 the map, mesh and trajectory writers of mast3r_slam/export.py (collect_map, collect_mesh, save_ply, save_ply_mesh,
 save_trajectory; slam.py:320-415) and
 the headless map renderer of mast3r_slam/render.py (render_map, ViewRecorder and its camera helpers) and the focal
-estimate of mast3r_slam/intrinsics.py (estimate_focal, estimate_intrinsics).
+estimate of mast3r_slam/intrinsics.py (estimate_focal, estimate_intrinsics) and the multi-view consistency filter of
+mast3r_slam/consistency.py (multiview_support, consistent_keyframes).
 """
 from __future__ import annotations
 
@@ -35,6 +36,7 @@ from .export import collect_map, collect_mesh, save_ply, save_ply_mesh, save_tra
 from .camera import CameraModel, load_calibration, undistort_device
 from .preprocess import adjust_intrinsics, resample_tables, resize_geometry, resize_img_device
 from .render import ViewRecorder, behind, default_intrinsics, depth_to_rgb, look_at, render_map, save_image
+from .consistency import ConsistentFrame, consistent_keyframes, multiview_support, nearest_neighbours
 from .intrinsics import IntrinsicsEstimate, estimate_focal, estimate_intrinsics, intrinsics_from_rows
 
 __all__ = [
@@ -45,6 +47,7 @@ __all__ = [
     "resize_img_device", "resize_geometry", "resample_tables", "adjust_intrinsics",
     "render_map", "default_intrinsics", "look_at", "behind", "depth_to_rgb", "save_image", "ViewRecorder",
     "estimate_focal", "estimate_intrinsics", "intrinsics_from_rows", "IntrinsicsEstimate",
+    "multiview_support", "consistent_keyframes", "nearest_neighbours", "ConsistentFrame",
 ]
 
 

@@ -14,6 +14,7 @@ three-keyframe window to its backend edges; the reference computes these candida
 """
 from __future__ import annotations
 
+import math
 from collections import deque
 from typing import Callable, Iterable, Optional
 
@@ -21,6 +22,7 @@ import torch
 
 from . import export, intrinsics, render
 from .config import get_config
+from .consistency import consistent_keyframes
 from .dataloader import Dataset, load_dataset
 from .frame import Keyframes, create_frame
 from .global_opt import FactorGraph
@@ -201,28 +203,50 @@ class SLAM:
         }
 
     # ------------------------------------------------------------------ slam.py:320-415
+    def _consistent(self, consistency, c_conf_threshold):
+        """(keyframes, threshold) for the map writers under `consistency` (True: consistency.multiview_support's defaults;
+        a dict: its keyword arguments).  The pinhole is the keyframes' intrinsics (the K the driver was given, moved to the
+        preprocessed frames) when there are any, else "estimate".  The
+        filter's own confidence test is c_conf_threshold unless the dict sets one; a threshold of None is passed on as
+        -inf, so that "every point" still means every KEPT point (a rejected point's confidence is -inf)."""
+        kw = {} if consistency is True else dict(consistency)
+        kw.setdefault("c_conf_threshold", c_conf_threshold)
+        K = self.keyframes.get_intrinsics()
+        frames = consistent_keyframes(self.keyframes, "estimate" if K is None else K, **kw)
+        return frames, (-math.inf if c_conf_threshold is None else c_conf_threshold)
+
     def reconstruction(self, c_conf_threshold: Optional[float] = 1.5, voxel_size: Optional[float] = None,
-                       return_index: bool = False):
-        """export.collect_map over the keyframes: (points [M,3] float32, colours [M,3] uint8[, index [M] int64])."""
-        return export.collect_map(self.keyframes, c_conf_threshold=c_conf_threshold, voxel_size=voxel_size,
-                                  return_index=return_index)
+                       return_index: bool = False, consistency=None):
+        """export.collect_map over the keyframes: (points [M,3] float32, colours [M,3] uint8[, index [M] int64]).
+        consistency: None - no cross-check between keyframes; True or a dict of consistency.multiview_support's keyword
+        arguments - only points that pass the multi-view consistency filter (see _consistent)."""
+        if consistency is None or consistency is False:
+            return export.collect_map(self.keyframes, c_conf_threshold=c_conf_threshold, voxel_size=voxel_size,
+                                      return_index=return_index)
+        frames, thr = self._consistent(consistency, c_conf_threshold)
+        return export.collect_map(frames, c_conf_threshold=thr, voxel_size=voxel_size, return_index=return_index)
 
     def save_pointcloud(self, path, c_conf_threshold: Optional[float] = 1.5, voxel_size: Optional[float] = None,
-                        binary: bool = True) -> int:
-        """:383-415 as a filtered (and optionally voxel-thinned) PLY; returns the number of vertices written."""
-        points, colors = self.reconstruction(c_conf_threshold, voxel_size)
+                        binary: bool = True, consistency=None) -> int:
+        """:383-415 as a filtered (and optionally voxel-thinned) PLY; returns the number of vertices written.
+        consistency as for reconstruction."""
+        points, colors = self.reconstruction(c_conf_threshold, voxel_size, consistency=consistency)
         return export.save_ply(path, points, colors, binary=binary)
 
     def mesh(self, c_conf_threshold: Optional[float] = 1.5, stride: int = 1, edge_ratio: Optional[float] = None,
-             return_index: bool = False):
+             return_index: bool = False, consistency=None):
         """export.collect_mesh over the keyframes: (vertices [V,3] float32, colours [V,3] uint8, faces [F,3] int32
-        [, index [V] int64]).  Opt-in: nothing in the loop uses it."""
-        return export.collect_mesh(self.keyframes, c_conf_threshold=c_conf_threshold, stride=stride, edge_ratio=edge_ratio,
-                                   return_index=return_index)
+        [, index [V] int64]).  Opt-in: nothing in the loop uses it.  consistency as for reconstruction."""
+        if consistency is None or consistency is False:
+            return export.collect_mesh(self.keyframes, c_conf_threshold=c_conf_threshold, stride=stride, edge_ratio=edge_ratio,
+                                       return_index=return_index)
+        frames, thr = self._consistent(consistency, c_conf_threshold)
+        return export.collect_mesh(frames, c_conf_threshold=thr, stride=stride, edge_ratio=edge_ratio, return_index=return_index)
 
     def save_mesh(self, path, c_conf_threshold: Optional[float] = 1.5, stride: int = 1,
                   edge_ratio: Optional[float] = None, binary: bool = True):
-        """The keyframes' triangle mesh as a PLY with a face element; returns (vertices, faces) written."""
+        """The keyframes' triangle mesh as a PLY with a face element; returns (vertices, faces) written.  For a mesh of
+        the consistency-filtered map write export.save_ply_mesh(path, *self.mesh(..., consistency=True))."""
         vertices, colors, faces = self.mesh(c_conf_threshold, stride, edge_ratio)
         return export.save_ply_mesh(path, vertices, colors, faces, binary=binary)
 
