@@ -20,9 +20,8 @@ constexpr int kInvStride = 16;                // floats per keyframe in the inve
 
 inline int64_t inv_bytes(int K) { return (int64_t)K * kInvStride * 4; }
 
-inline bool shape_ok(int K, int N) {
-    return K >= 0 && N >= 1 && (int64_t)K * N <= 0x7fffffff && (int64_t)K * m3_cdiv(N, kTile) <= (1 << 30);
-}
+// An empty map is accepted (and nothing is launched for it).
+inline bool shape_ok(int K, int N) { return (K == 0 && N >= 1) || map_shape_ok(K, N); }
 
 // One thread per keyframe: the view_inverse of its pose.
 __global__ void __launch_bounds__(kThreads) k_cons_inverse(const float *__restrict__ poses, int K, float *__restrict__ inv) {
@@ -41,24 +40,18 @@ __global__ void __launch_bounds__(kThreads) k_cons_inverse(const float *__restri
 __global__ void __launch_bounds__(kThreads) k_cons_plane(const float *const *__restrict__ X, const float *const *__restrict__ C,
                                                           const int32_t *__restrict__ Nk, int N, int tiles, int use_thresh,
                                                           float thresh, float z_min, float *__restrict__ D) {
-    Tile t = tile_of(N, tiles);
+    const Tile t = tile_of(N, tiles, X, C);
     if (t.n0 >= N) return;
-    const float *Xk = X[t.k], *Ck = C[t.k];
-    t.vec = t.n0 + kPts <= N && N % 4 == 0 && aligned16(Xk) && aligned16(Ck);
     float avg[kPts];
-    const unsigned pass = conf_pass(Ck, t, N, (float)Nk[t.k], use_thresh, thresh, avg);
-    float z[kPts];
-    if (t.vec) {
-        const float4 *src = (const float4 *)(Xk + (size_t)3 * t.n0);
-        const float4 a = src[0], b = src[1], c = src[2];
-        z[0] = a.z; z[1] = b.y; z[2] = c.x; z[3] = c.w;
-    } else {
-#pragma unroll
-        for (int j = 0; j < kPts; ++j) z[j] = t.n0 + j < N ? Xk[(size_t)3 * (t.n0 + j) + 2] : 0.f;
-    }
+    const unsigned pass = conf_pass(t, N, (float)Nk[t.k], use_thresh, thresh, avg);
+    float x[3 * kPts];
+    load_points(t.X, t, pass, x);                                                // only z is used
     float d[kPts];
 #pragma unroll
-    for (int j = 0; j < kPts; ++j) d[j] = (((pass >> j) & 1u) && isfinite(z[j]) && z[j] > z_min) ? z[j] : __builtin_nanf("");
+    for (int j = 0; j < kPts; ++j) {
+        const float z = x[3 * j + 2];
+        d[j] = (((pass >> j) & 1u) && isfinite(z) && z > z_min) ? z : __builtin_nanf("");
+    }
     float *Dk = D + (size_t)t.k * N + t.n0;
     if (t.vec) {
         *(float4 *)Dk = float4{d[0], d[1], d[2], d[3]};                          // D is 16-byte aligned and N % 4 == 0
@@ -81,14 +74,12 @@ __global__ void __launch_bounds__(kThreads) k_cons_count(const float *const *__r
                                                           int min_views, int max_conflicts, const float *__restrict__ inv,
                                                           const float *__restrict__ D, uint8_t *__restrict__ support,
                                                           uint8_t *__restrict__ conflict, float *__restrict__ conf) {
-    Tile t = tile_of(N, tiles);
+    const Tile t = tile_of(N, tiles, X, C);
     if (t.n0 >= N) return;
-    const float *Xk = X[t.k], *Ck = C[t.k];
-    t.vec = t.n0 + kPts <= N && N % 4 == 0 && aligned16(Xk) && aligned16(Ck);
     float avg[kPts];
-    unsigned keep = conf_pass(Ck, t, N, (float)Nk[t.k], use_thresh, thresh, avg);
+    unsigned keep = conf_pass(t, N, (float)Nk[t.k], use_thresh, thresh, avg);
     V3<float> p[kPts];
-    if (keep) keep = world_points(Xk, t, load_pose<float>(poses + 8 * t.k), keep, p);
+    if (keep) keep = world_points(t, load_pose<float>(poses + 8 * t.k), keep, p);
     unsigned sup[kPts] = {0u, 0u, 0u, 0u}, con[kPts] = {0u, 0u, 0u, 0u};
     if (keep) {
         const float fW = (float)W, fH = (float)H;
@@ -113,13 +104,7 @@ __global__ void __launch_bounds__(kThreads) k_cons_count(const float *const *__r
         }
     }
     float c[kPts];
-    if (t.vec) {
-        const float4 q = *(const float4 *)(Ck + t.n0);
-        c[0] = q.x; c[1] = q.y; c[2] = q.z; c[3] = q.w;
-    } else {
-#pragma unroll
-        for (int i = 0; i < kPts; ++i) c[i] = t.n0 + i < N ? Ck[t.n0 + i] : 0.f;
-    }
+    load_conf(t.C, t, N, c);                                                     // raw: the masked confidence is not averaged
     unsigned ws = 0u, wc = 0u;
 #pragma unroll
     for (int i = 0; i < kPts; ++i) {

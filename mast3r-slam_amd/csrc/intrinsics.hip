@@ -9,12 +9,11 @@
 // Compiled with -ffp-contract=off: the per-pixel terms are separately rounded float64 operations
 // (tests/focal_twin.py restates them).
 #include "common.h"
+#include "map_points.h"     // kThreads, kPts, kTile, aligned16; no world point is formed here
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kPts = 4;                       // consecutive pixels per thread: one 16-byte load of C, three of X
-constexpr int kChunk = kThreads * kPts;       // pixels a workgroup reads per round
+constexpr int kChunk = kTile;                 // pixels a workgroup reads per round
 constexpr int kMinRounds = 4;                 // 4096-pixel tiles ...
 constexpr int kMaxTiles = 256;                // ... until a keyframe would have more tiles than this: then the tile grows
 constexpr int kPart = 3;                      // partial sums per tile: numerator, denominator (0 in the residual pass), count
@@ -36,8 +35,6 @@ inline Plan plan_of(int N) {
 inline bool focal_shape_ok(int K, int N) {
     return K >= 1 && N >= 1 && (int64_t)K * N <= 0x7fffffff && (int64_t)K * plan_of(N).tiles <= (1 << 22);
 }
-
-__device__ __forceinline__ bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 
 // The kPart sums of one keyframe's tile partials, each added in ascending tile order; every thread gets them.
 __device__ __forceinline__ void keyframe_sums(const double *__restrict__ part, int tiles, double (&s)[kPart]) {
@@ -77,6 +74,8 @@ __global__ void __launch_bounds__(kThreads) k_focal_pass(const float *const *__r
         }
     }
     const float *Xk = X[k], *Ck = C[k];
+    // The loads stay written out here, with the predicate hoisted out of the round loop: with load_conf / load_points
+    // of map_points.h inside the loop the pass measured 2.7 % slower at one keyframe (profiles/map_family_refactor.md).
     const bool vec = N % 4 == 0 && aligned16(Xk) && aligned16(Ck);
     const float nk = (float)Nk[k];
     double acc[kPart] = {0.0, 0.0, 0.0};

@@ -6,36 +6,11 @@
 #include "common.h"
 #include "sim3_dev.h"
 #include "map_points.h"
+#include "compact_dev.h"
 
 namespace {
 
-constexpr int kScanThreads = 1024;
-constexpr int kHdrWords = 4;                  // ws words: [0] kept count, [1] points dropped by the voxel key (stage B), [2..3] unused
 constexpr unsigned long long kEmpty = ~0ull;  // a packed voxel key uses 63 bits
-
-// Position of this thread's first kept point among the workgroup's kept points (source order: thread, then bit), and the
-// workgroup's total.  keep: bit j = point j of this thread is kept.
-__device__ __forceinline__ int block_prefix(unsigned keep, int &total) {
-    __shared__ int wsum[kThreads / M3_WAVE];
-    int before = 0, wtot = 0;
-#pragma unroll
-    for (int j = 0; j < kPts; ++j) {
-        const unsigned long long b = __ballot((keep >> j) & 1u);
-        before += __builtin_amdgcn_mbcnt_hi((unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, 0u));
-        wtot += __popcll(b);
-    }
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) wsum[w] = wtot;
-    __syncthreads();
-    int base = 0;
-    total = 0;
-#pragma unroll
-    for (int i = 0; i < kThreads / M3_WAVE; ++i) {
-        base += i < w ? wsum[i] : 0;
-        total += wsum[i];
-    }
-    return base + before;
-}
 
 // Kept points per workgroup.  X is only read by threads with a point that passed the confidence test.
 __global__ void __launch_bounds__(kThreads) k_export_count(const float *const *__restrict__ X,
@@ -43,58 +18,19 @@ __global__ void __launch_bounds__(kThreads) k_export_count(const float *const *_
                                                             const float *__restrict__ poses, const int32_t *__restrict__ Nk,
                                                             int N, int tiles, int use_thresh, float thresh,
                                                             int32_t *__restrict__ cnt) {
-    Tile t = tile_of(N, tiles);
-    const float *Xk = X[t.k], *Ck = C[t.k];
-    t.vec = t.n0 + kPts <= N && N % 4 == 0 && aligned16(Xk) && aligned16(Ck);
+    const Tile t = tile_of(N, tiles, X, C);
     float avg[kPts];
-    unsigned keep = conf_pass(Ck, t, N, (float)Nk[t.k], use_thresh, thresh, avg);
+    unsigned keep = conf_pass(t, N, (float)Nk[t.k], use_thresh, thresh, avg);
     if (keep) {
         V3<float> p[kPts];
-        keep = world_points(Xk, t, load_pose<float>(poses + 8 * t.k), keep, p);
+        keep = world_points(t, load_pose<float>(poses + 8 * t.k), keep, p);
     }
     int total;
     block_prefix(keep, total);
     if (threadIdx.x == 0) cnt[blockIdx.x] = total;
 }
 
-// Exclusive scan of cnt[0..B) in place, one workgroup; hdr[0] = the total.
-__global__ void __launch_bounds__(kScanThreads) k_export_scan(int32_t *__restrict__ cnt, int B, int32_t *__restrict__ hdr) {
-    __shared__ int wsum[kScanThreads / M3_WAVE];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int carry = 0;
-    for (int i0 = 0; i0 < B; i0 += kScanThreads * 4) {
-        const int i = i0 + threadIdx.x * 4;
-        int v[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = i + j < B ? cnt[i + j] : 0;
-        const int mine = (v[0] + v[1]) + (v[2] + v[3]);
-        int incl = mine;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const int o = __shfl_up(incl, off, 64);
-            if (lane >= off) incl += o;
-        }
-        if (lane == 63) wsum[w] = incl;
-        __syncthreads();
-        int base = carry, all = 0;
-#pragma unroll
-        for (int ww = 0; ww < kScanThreads / M3_WAVE; ++ww) {
-            base += ww < w ? wsum[ww] : 0;
-            all += wsum[ww];
-        }
-        int run = base + incl - mine;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            if (i + j < B) cnt[i + j] = run;
-            run += v[j];
-        }
-        carry += all;
-        __syncthreads();                               // wsum is rewritten by the next round
-    }
-    if (threadIdx.x == 0) hdr[0] = carry;
-}
-
-// LAYOUT 0: float32 [3,H,W] planes in [0,1]; 1: uint8 [H,W,3].
+// LAYOUT as fetch_rgb takes it.
 template <int LAYOUT>
 __global__ void __launch_bounds__(kThreads) k_export_scatter(const float *const *__restrict__ X,
                                                               const float *const *__restrict__ C,
@@ -104,52 +40,21 @@ __global__ void __launch_bounds__(kThreads) k_export_scatter(const float *const 
                                                               const int32_t *__restrict__ offs, int64_t M,
                                                               float *__restrict__ points, unsigned char *__restrict__ colors,
                                                               int64_t *__restrict__ index, float *__restrict__ conf) {
-    Tile t = tile_of(N, tiles);
-    const float *Xk = X[t.k], *Ck = C[t.k];
+    const Tile t = tile_of(N, tiles, X, C);
     const void *Ik = img[t.k];
-    t.vec = t.n0 + kPts <= N && N % 4 == 0 && aligned16(Xk) && aligned16(Ck);
     float avg[kPts];
-    unsigned keep = conf_pass(Ck, t, N, (float)Nk[t.k], use_thresh, thresh, avg);
+    unsigned keep = conf_pass(t, N, (float)Nk[t.k], use_thresh, thresh, avg);
     V3<float> p[kPts];
-    if (keep) keep = world_points(Xk, t, load_pose<float>(poses + 8 * t.k), keep, p);
+    if (keep) keep = world_points(t, load_pose<float>(poses + 8 * t.k), keep, p);
     int total;
     int64_t o = (int64_t)offs[blockIdx.x] + block_prefix(keep, total);
     if (!keep) return;
     unsigned char rgb[kPts][3];
-    if constexpr (LAYOUT == 0) {
-        const float *I = (const float *)Ik;
-        if (t.vec && aligned16(I)) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const float4 v = *(const float4 *)(I + (size_t)c * N + t.n0);
-                rgb[0][c] = to_u8(v.x); rgb[1][c] = to_u8(v.y); rgb[2][c] = to_u8(v.z); rgb[3][c] = to_u8(v.w);
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < kPts; ++j)
-#pragma unroll
-                for (int c = 0; c < 3; ++c) rgb[j][c] = (keep >> j) & 1u ? to_u8(I[(size_t)c * N + t.n0 + j]) : 0;
-        }
-    } else {
-        const unsigned char *I = (const unsigned char *)Ik;
-        if (t.vec && ((uintptr_t)I & 3) == 0) {                                 // 12 bytes from a 4-byte aligned address
-            const unsigned *src = (const unsigned *)(I + (size_t)3 * t.n0);
-            const unsigned w[3] = {src[0], src[1], src[2]};
-#pragma unroll
-            for (int b = 0; b < 12; ++b) rgb[b / 3][b % 3] = (unsigned char)(w[b / 4] >> (8 * (b % 4)));
-        } else {
-#pragma unroll
-            for (int j = 0; j < kPts; ++j)
-#pragma unroll
-                for (int c = 0; c < 3; ++c) rgb[j][c] = (keep >> j) & 1u ? I[(size_t)3 * (t.n0 + j) + c] : 0;
-        }
-    }
+    fetch_rgb<LAYOUT>(Ik, t, N, keep, rgb);
 #pragma unroll
     for (int j = 0; j < kPts; ++j) {
         if (!((keep >> j) & 1u) || o >= M) continue;                            // o < M always holds for a ws from the same inputs
-        points[3 * o] = p[j].x; points[3 * o + 1] = p[j].y; points[3 * o + 2] = p[j].z;
-        colors[3 * o] = rgb[j][0]; colors[3 * o + 1] = rgb[j][1]; colors[3 * o + 2] = rgb[j][2];
-        if (index) index[o] = (int64_t)t.k * N + t.n0 + j;
+        store_row(o, p[j], rgb[j], (int64_t)t.k * N + t.n0 + j, points, colors, index);
         if (conf) conf[o] = avg[j];
         ++o;
     }
@@ -285,30 +190,26 @@ __global__ void __launch_bounds__(kThreads) k_voxel_scatter(const float *__restr
     }
 }
 
-inline bool export_shape_ok(int K, int N) {
-    return K >= 1 && N >= 1 && (int64_t)K * N <= 0x7fffffff && (int64_t)K * m3_cdiv(N, kTile) <= (1 << 30);
-}
-
 }  // namespace
 
 extern "C" {
 
 int64_t m3_map_export_ws_bytes(int K, int N) {
-    if (!export_shape_ok(K, N)) return 0;
+    if (!map_shape_ok(K, N)) return 0;
     const int64_t blocks = (int64_t)K * m3_cdiv(N, kTile);
     return (kHdrWords + (blocks + 3) / 4 * 4) * 4;
 }
 
 int m3_map_export_count(const float *const *X, const float *const *C, const float *poses, const int32_t *Nk, int K, int N,
                         int use_thresh, float thresh, void *ws, int64_t ws_bytes, void *stream) {
-    M3_REQUIRE(X && C && poses && Nk && ws && export_shape_ok(K, N));
+    M3_REQUIRE(X && C && poses && Nk && ws && map_shape_ok(K, N));
     M3_REQUIRE((use_thresh == 0 || use_thresh == 1) && ((uintptr_t)ws & 15) == 0 && ws_bytes >= m3_map_export_ws_bytes(K, N));
     hipStream_t st = (hipStream_t)stream;
     const int tiles = m3_cdiv(N, kTile), blocks = K * tiles;
     int32_t *hdr = (int32_t *)ws;
     hipLaunchKernelGGL(k_export_count, dim3(blocks), dim3(kThreads), 0, st, X, C, poses, Nk, N, tiles, use_thresh, thresh,
                        hdr + kHdrWords);
-    hipLaunchKernelGGL(k_export_scan, dim3(1), dim3(kScanThreads), 0, st, hdr + kHdrWords, blocks, hdr);
+    launch_scan(st, hdr, ScanJob{hdr + kHdrWords, blocks});
     M3_CHECK_LAUNCH("m3_map_export_count");
     return M3_OK;
 }
@@ -317,7 +218,7 @@ int m3_map_export_scatter(const float *const *X, const float *const *C, const vo
                           const int32_t *Nk, int K, int N, int use_thresh, float thresh, int layout, const void *ws,
                           int64_t ws_bytes, int64_t M, float *points, uint8_t *colors, int64_t *index, float *conf,
                           void *stream) {
-    M3_REQUIRE(X && C && img && poses && Nk && ws && points && colors && export_shape_ok(K, N));
+    M3_REQUIRE(X && C && img && poses && Nk && ws && points && colors && map_shape_ok(K, N));
     M3_REQUIRE((use_thresh == 0 || use_thresh == 1) && ((uintptr_t)ws & 15) == 0 && ws_bytes >= m3_map_export_ws_bytes(K, N));
     M3_REQUIRE(M >= 1 && M <= (int64_t)K * N);
     M3_REQUIRE(layout == M3_MAP_IMG_F32_CHW || layout == M3_MAP_IMG_U8_HWC);
@@ -354,7 +255,7 @@ int m3_map_voxel_count(const float *points, const float *conf, int64_t M, float 
     hipLaunchKernelGGL(k_voxel_insert, dim3(m3_cdiv(M, kThreads)), dim3(kThreads), 0, st, points, conf, M, voxel_size,
                        v.keys, v.vals, v.slots, v.slot, v.hdr);
     hipLaunchKernelGGL(k_voxel_count, dim3((int)v.blocks), dim3(kThreads), 0, st, v.slot, v.vals, M, v.offs);
-    hipLaunchKernelGGL(k_export_scan, dim3(1), dim3(kScanThreads), 0, st, v.offs, (int)v.blocks, v.hdr);
+    launch_scan(st, v.hdr, ScanJob{v.offs, v.blocks});
     M3_CHECK_LAUNCH("m3_map_voxel_count");
     return M3_OK;
 }

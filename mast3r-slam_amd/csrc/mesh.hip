@@ -42,6 +42,7 @@
 #include "sim3_dev.h"
 #include "map_points.h"
 #pragma clang fp contract(off)
+#include "compact_dev.h"
 
 namespace {
 
@@ -49,8 +50,6 @@ constexpr int kSeg = 256;                     // grid columns per row segment (o
 constexpr int kTileRows = 8;                  // cell rows per k_mesh_cells workgroup: two per wave
 constexpr int kPitch = kSeg + 8;              // staged floats per vertex row: 257 columns, a lead of <= 3 and a tail of <= 3
 constexpr int kGroups = kPitch / kPts;        // 4-point load groups per staged row
-constexpr int kScanThreads = 1024;
-constexpr int kHdrWords = 4;                  // ws words: [0] V, [1] F, [2..3] unused
 constexpr int kLaunches = 5;                  // cells, used-vertex count, scan | vertex scatter, face scatter
 
 struct Grid {
@@ -99,28 +98,14 @@ __device__ __forceinline__ bool edge_ok(const P3 &p, const P3 &q, float rp, floa
 
 // Validity of the <= 4 points t.n0 ... below nlim by the export rule, and their camera-frame coordinates into
 // sx / sy / sz[at ...]; an invalid point is staged as NaN.
-__device__ __forceinline__ void stage_points(const float *__restrict__ Xk, const float *__restrict__ Ck, const Tile &t,
-                                             int nlim, const Pose<float> &T, float nk, int use_thresh, float thresh,
-                                             float *__restrict__ sx, float *__restrict__ sy, float *__restrict__ sz, int at) {
+__device__ __forceinline__ void stage_points(const Tile &t, int nlim, const Pose<float> &T, float nk, int use_thresh,
+                                             float thresh, float *__restrict__ sx, float *__restrict__ sy,
+                                             float *__restrict__ sz, int at) {
     float avg[kPts];
-    unsigned keep = conf_pass(Ck, t, nlim, nk, use_thresh, thresh, avg);
+    unsigned keep = conf_pass(t, nlim, nk, use_thresh, thresh, avg);
     float x[3 * kPts] = {};
     V3<float> p[kPts];
-    if (keep && t.vec) {
-        // world_points does not hand out the camera-frame values, so they are loaded here, in the block that dominates
-        // its own (identical) loads: the compiler merges the two (four 16-byte loads per group in the ISA, C included)
-        const float4 *src = (const float4 *)(Xk + (size_t)3 * t.n0);
-        const float4 a = src[0], b = src[1], c = src[2];
-        x[0] = a.x; x[1] = a.y; x[2] = a.z; x[3] = a.w; x[4] = b.x; x[5] = b.y; x[6] = b.z; x[7] = b.w;
-        x[8] = c.x; x[9] = c.y; x[10] = c.z; x[11] = c.w;
-        keep = world_points(Xk, t, T, keep, p);
-    } else if (keep) {
-        keep = world_points(Xk, t, T, keep, p);
-#pragma unroll
-        for (int j = 0; j < kPts; ++j)
-#pragma unroll
-            for (int d = 0; d < 3; ++d) x[3 * j + d] = (keep >> j) & 1u ? Xk[(size_t)3 * (t.n0 + j) + d] : 0.f;
-    }
+    if (keep) keep = world_points(t, T, keep, p, x);
 #pragma unroll
     for (int j = 0; j < kPts; ++j) {
         if (t.n0 + j >= nlim) continue;
@@ -150,17 +135,14 @@ __global__ void __launch_bounds__(kThreads) k_mesh_cells(const float *const *__r
     const Pose<float> T = load_pose<float>(poses + 8 * k);
     const float nk = (float)Nk[k];
     if constexpr (DENSE) {
-        const bool veck = N % 4 == 0 && aligned16(Xk) && aligned16(Ck);
         for (int it = threadIdx.x; it < (kTileRows + 1) * kGroups; it += kThreads) {
             const int r = it / kGroups, y = cy0 + r;
             if (y >= g.H) break;
             const int row = y * g.W + cx0, end = y * g.W + min(cx0 + kSeg + 1, g.W);
-            Tile t;
-            t.k = k;
-            t.n0 = (row & ~3) + (it - r * kGroups) * kPts;
-            if (t.n0 >= end) continue;
-            t.vec = veck && t.n0 + kPts <= N;
-            stage_points(Xk, Ck, t, N, T, nk, use_thresh, thresh, sx, sy, sz, r * kPitch + (t.n0 - (row & ~3)));
+            const int n0 = (row & ~3) + (it - r * kGroups) * kPts;
+            if (n0 >= end) continue;
+            stage_points(tile_at(k, n0, N, Xk, Ck), N, T, nk, use_thresh, thresh, sx, sy, sz,
+                         r * kPitch + (n0 - (row & ~3)));
         }
     } else {
         for (int it = threadIdx.x; it < (kTileRows + 1) * (kSeg + 1); it += kThreads) {
@@ -168,11 +150,8 @@ __global__ void __launch_bounds__(kThreads) k_mesh_cells(const float *const *__r
             const int gy = cy0 + r, gx = cx0 + c;
             if (gy >= g.Hg) break;
             if (gx >= g.Wg) continue;
-            Tile t;
-            t.k = k;
-            t.n0 = gy * g.s * g.W + gx * g.s;
-            t.vec = false;
-            stage_points(Xk, Ck, t, t.n0 + 1, T, nk, use_thresh, thresh, sx, sy, sz, r * kPitch + c);
+            const int n0 = gy * g.s * g.W + gx * g.s, nlim = n0 + 1;           // a group of one point: the scalar path
+            stage_points(tile_at(k, n0, nlim, Xk, Ck), nlim, T, nk, use_thresh, thresh, sx, sy, sz, r * kPitch + c);
         }
     }
     __syncthreads();
@@ -236,34 +215,10 @@ __device__ __forceinline__ unsigned used_bits(const unsigned char *__restrict__ 
     return keep;
 }
 
-// Position of this thread's first kept point among the workgroup's kept points (source order: thread, then bit), and the
-// workgroup's total, as map_export.hip takes them.  keep: bit j = point j of this thread is kept.
-__device__ __forceinline__ int block_prefix(unsigned keep, int &total) {
-    __shared__ int wsum[kThreads / M3_WAVE];
-    int before = 0, wtot = 0;
-#pragma unroll
-    for (int j = 0; j < kPts; ++j) {
-        const unsigned long long b = __ballot((keep >> j) & 1u);
-        before += __builtin_amdgcn_mbcnt_hi((unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, 0u));
-        wtot += __popcll(b);
-    }
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) wsum[w] = wtot;
-    __syncthreads();
-    int base = 0;
-    total = 0;
-#pragma unroll
-    for (int i = 0; i < kThreads / M3_WAVE; ++i) {
-        base += i < w ? wsum[i] : 0;
-        total += wsum[i];
-    }
-    return base + before;
-}
-
 // Used vertices per 1024-point tile: the export's grid, so that vertices come out in ascending source index.
 __global__ void __launch_bounds__(kThreads) k_mesh_count_vertices(const unsigned char *__restrict__ flags, Grid g, int tiles,
                                                                    int32_t *__restrict__ cntV) {
-    const Tile t = tile_of(g.H * g.W, tiles);
+    const Tile t = tile_of(tiles);
     int total;
     block_prefix(used_bits(flags, g, t), total);
     if (threadIdx.x == 0) cntV[blockIdx.x] = total;
@@ -280,50 +235,6 @@ __device__ __forceinline__ bool segment_of(int64_t nseg, int rows, int segs, int
     return true;
 }
 
-__device__ __forceinline__ int lanes_before(unsigned long long b) {
-    return __builtin_amdgcn_mbcnt_hi((unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, 0u));
-}
-
-// Exclusive scan in place, one workgroup per array: blockIdx 0 scans cntV into hdr[0], blockIdx 1 cntF into hdr[1].
-__global__ void __launch_bounds__(kScanThreads) k_mesh_scan(int32_t *__restrict__ cntV, int64_t nV, int32_t *__restrict__ cntF,
-                                                             int64_t nF, int32_t *__restrict__ hdr) {
-    __shared__ int wsum[kScanThreads / M3_WAVE];
-    int32_t *cnt = blockIdx.x ? cntF : cntV;
-    const int64_t B = blockIdx.x ? nF : nV;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int carry = 0;
-    for (int64_t i0 = 0; i0 < B; i0 += kScanThreads * 4) {
-        const int64_t i = i0 + threadIdx.x * 4;
-        int v[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = i + j < B ? cnt[i + j] : 0;
-        const int mine = (v[0] + v[1]) + (v[2] + v[3]);
-        int incl = mine;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const int o = __shfl_up(incl, off, 64);
-            if (lane >= off) incl += o;
-        }
-        if (lane == 63) wsum[w] = incl;
-        __syncthreads();
-        int base = carry, all = 0;
-#pragma unroll
-        for (int ww = 0; ww < kScanThreads / M3_WAVE; ++ww) {
-            base += ww < w ? wsum[ww] : 0;
-            all += wsum[ww];
-        }
-        int run = base + incl - mine;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            if (i + j < B) cnt[i + j] = run;
-            run += v[j];
-        }
-        carry += all;
-        __syncthreads();                               // wsum is rewritten by the next round
-    }
-    if (threadIdx.x == 0) hdr[blockIdx.x] = carry;
-}
-
 // Used vertices to rows offV[tile] + rank inside the tile; remap[grid vertex] = its row.  The shape of k_export_scatter
 // - a thread owns four consecutive points and takes their world points from one world_points call - so that the
 // compiler sees the exporter's arithmetic in the exporter's context and the bytes are the exporter's.  Stride 1 takes
@@ -337,33 +248,24 @@ __global__ void __launch_bounds__(kThreads) k_mesh_vertices(const float *const *
                                                              int32_t *__restrict__ remap, float *__restrict__ points,
                                                              unsigned char *__restrict__ colors, int64_t *__restrict__ index) {
     const int N = g.H * g.W;
-    Tile t = tile_of(N, tiles);
-    const float *Xk = X[t.k];
+    Tile t = tile_of(tiles);
+    t.X = X[t.k];
     const void *Ik = img[t.k];
-    t.vec = g.s == 1 && t.n0 + kPts <= N && N % 4 == 0 && aligned16(Xk);
+    t.vec = g.s == 1 && vec_ok(t.n0, N, t.X, t.X);                              // C is not read here
     // Validity was decided once, by k_mesh_cells; the count pass counted exactly these bits, so every one of them is
     // written and the finiteness result of this call is not consulted.
     const unsigned keep = used_bits(flags, g, t);
     V3<float> p[kPts];
-    if (keep) world_points(Xk, t, load_pose<float>(poses + 8 * t.k), keep, p);
+    if (keep) world_points(t, load_pose<float>(poses + 8 * t.k), keep, p);
     int total;
     int64_t o = (int64_t)offs[blockIdx.x] + block_prefix(keep, total);
     if (!keep) return;
     unsigned char rgb[kPts][3];
-#pragma unroll
-    for (int j = 0; j < kPts; ++j)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            if (!((keep >> j) & 1u)) rgb[j][c] = 0;
-            else if constexpr (LAYOUT == 0) rgb[j][c] = to_u8(((const float *)Ik)[(size_t)c * N + t.n0 + j]);
-            else rgb[j][c] = ((const unsigned char *)Ik)[(size_t)3 * (t.n0 + j) + c];
-        }
+    fetch_rgb<LAYOUT>(Ik, t, N, keep, rgb);
 #pragma unroll
     for (int j = 0; j < kPts; ++j) {
         if (!((keep >> j) & 1u) || o >= V) continue;                            // o < V always holds for a ws from the same inputs
-        points[3 * o] = p[j].x; points[3 * o + 1] = p[j].y; points[3 * o + 2] = p[j].z;
-        colors[3 * o] = rgb[j][0]; colors[3 * o + 1] = rgb[j][1]; colors[3 * o + 2] = rgb[j][2];
-        if (index) index[o] = (int64_t)t.k * N + t.n0 + j;
+        store_row(o, p[j], rgb[j], (int64_t)t.k * N + t.n0 + j, points, colors, index);
         const int y = (t.n0 + j) / g.W, x = t.n0 + j - y * g.W;
         remap[((size_t)t.k * g.Hg + y / g.s) * g.Wg + x / g.s] = (int32_t)o;
         ++o;
@@ -439,7 +341,7 @@ int m3_mesh_count(const float *const *X, const float *const *C, const float *pos
                            thresh, t2, flags, cntF);
     const int tiles = m3_cdiv(g.H * g.W, kTile);
     hipLaunchKernelGGL(k_mesh_count_vertices, dim3(K * tiles), dim3(kThreads), 0, st, flags, g, tiles, cntV);
-    hipLaunchKernelGGL(k_mesh_scan, dim3(2), dim3(kScanThreads), 0, st, cntV, m.ntileV, cntF, m.nsegF, (int32_t *)ws);
+    launch_scan(st, (int32_t *)ws, ScanJob{cntV, m.ntileV}, ScanJob{cntF, m.nsegF});              // V to word 0, F to word 1
     M3_CHECK_LAUNCH("m3_mesh_count");
     return M3_OK;
 }

@@ -36,15 +36,13 @@ __global__ void __launch_bounds__(kThreads) k_render_splat(const float *const *_
                                                             unsigned long long *keys) {
     __shared__ float sv[kViewWords];
     if (threadIdx.x == 0) view_inverse(view, sv);
-    Tile t = tile_of(N, tiles);
-    const float *Xk = X[t.k], *Ck = C[t.k];
-    t.vec = t.n0 + kPts <= N && N % 4 == 0 && aligned16(Xk) && aligned16(Ck);
+    const Tile t = tile_of(N, tiles, X, C);
     float avg[kPts];
-    unsigned keep = conf_pass(Ck, t, N, (float)Nk[t.k], use_thresh, thresh, avg);
+    unsigned keep = conf_pass(t, N, (float)Nk[t.k], use_thresh, thresh, avg);
     __syncthreads();
     if (!keep) return;
     V3<float> p[kPts];
-    keep = world_points(Xk, t, load_pose<float>(poses + 8 * t.k), keep, p);
+    keep = world_points(t, load_pose<float>(poses + 8 * t.k), keep, p);
     constexpr int R = PS / 2;
 #pragma unroll
     for (int j = 0; j < kPts; ++j) {
@@ -72,7 +70,7 @@ __global__ void __launch_bounds__(kThreads) k_render_splat(const float *const *_
     }
 }
 
-// A thread owns 4 consecutive output pixels.  LAYOUT as k_export_scatter.
+// A thread owns 4 consecutive output pixels.  LAYOUT as fetch_rgb takes it.
 template <int LAYOUT>
 __global__ void __launch_bounds__(kThreads) k_render_resolve(const unsigned long long *__restrict__ keys,
                                                               const void *const *__restrict__ img, int N, int64_t P,
@@ -104,15 +102,7 @@ __global__ void __launch_bounds__(kThreads) k_render_resolve(const unsigned long
         const unsigned k = s / (unsigned)N, n = s - k * (unsigned)N;
         z[j] = __uint_as_float((unsigned)(key[j] >> 32));
         src[j] = (int64_t)s;
-        if constexpr (LAYOUT == 0) {
-            const float *I = (const float *)img[k];
-#pragma unroll
-            for (int ch = 0; ch < 3; ++ch) c[j][ch] = to_u8(I[(size_t)ch * N + n]);
-        } else {
-            const unsigned char *I = (const unsigned char *)img[k];
-#pragma unroll
-            for (int ch = 0; ch < 3; ++ch) c[j][ch] = I[(size_t)3 * n + ch];
-        }
+        fetch_rgb<LAYOUT>(img[k], N, n, c[j]);
     }
     if (vec) {
         unsigned w[3] = {0u, 0u, 0u};
@@ -138,10 +128,6 @@ __global__ void __launch_bounds__(kThreads) k_render_resolve(const unsigned long
 
 inline bool view_ok(int Hv, int Wv) { return Hv >= 1 && Wv >= 1 && Hv <= 16384 && Wv <= 16384; }
 
-inline bool map_ok(int K, int N) {
-    return K == 0 || (K >= 1 && N >= 1 && (int64_t)K * N <= 0x7fffffff && (int64_t)K * m3_cdiv(N, kTile) <= (1 << 30));
-}
-
 }  // namespace
 
 extern "C" {
@@ -155,7 +141,7 @@ int m3_render_map(const float *const *X, const float *const *C, const void *cons
                   float fx, float fy, float cx, float cy, int Hv, int Wv, float near, float far, int point_size, int bg_r,
                   int bg_g, int bg_b, void *ws, int64_t ws_bytes, uint8_t *rgb, float *depth, int64_t *index,
                   void *stream) {
-    M3_REQUIRE(view_ok(Hv, Wv) && map_ok(K, N) && ws && rgb && depth);
+    M3_REQUIRE(view_ok(Hv, Wv) && (K == 0 || map_shape_ok(K, N)) && ws && rgb && depth);     // an empty map is drawn
     M3_REQUIRE(K == 0 || (X && C && img && poses && Nk && view_pose));
     M3_REQUIRE((use_thresh == 0 || use_thresh == 1) && ((uintptr_t)ws & 15) == 0 && ws_bytes >= m3_render_ws_bytes(Hv, Wv));
     M3_REQUIRE(layout == M3_MAP_IMG_F32_CHW || layout == M3_MAP_IMG_U8_HWC);

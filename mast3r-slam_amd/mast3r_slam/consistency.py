@@ -31,7 +31,7 @@ from typing import Optional
 import torch
 
 from . import _ffi
-from .export import _MapTables, _grid_size, _map_tables, _with_pointmap
+from .export import _MapTables, _check_workspace, _conf_gate, _grid_size, _map_tables, _with_pointmap
 from .render import _pinhole
 
 __all__ = ["multiview_support", "consistent_keyframes", "nearest_neighbours", "ConsistentFrame"]
@@ -157,10 +157,8 @@ def multiview_support(keyframes, K, neighbours=8, c_conf_threshold: Optional[flo
             raise ValueError(f"out {name} must be contiguous and 16-byte aligned")
     if workspace is None:
         workspace = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
-    _ffi.check(workspace, torch.uint8, "workspace")
-    if workspace.numel() < ws_bytes or not workspace.is_contiguous() or workspace.data_ptr() % 16:
-        raise ValueError(f"workspace must be a contiguous, 16-byte aligned uint8 tensor of at least {ws_bytes} bytes")
-    use, thr = (0, 0.0) if c_conf_threshold is None else (1, float(c_conf_threshold))
+    _check_workspace(workspace, ws_bytes)
+    use, thr = _conf_gate(c_conf_threshold)
     _ffi.call("m3_consistency", _ffi.ptr(m.table[0]), _ffi.ptr(m.table[1]), _ffi.ptr(poses), _ffi.ptr(m.nk), k, h, w, use, thr,
               fx, fy, cx, cy, _ffi.ptr(nbr) if v else None, v, z_min, rtol, mv, mc, _ffi.ptr(workspace), ws_bytes,
               _ffi.ptr(out[0]), _ffi.ptr(out[1]), _ffi.ptr(out[2]), _ffi.stream_ptr())

@@ -68,6 +68,18 @@ class _MapTables:
     __slots__ = ("k", "n", "layout", "device", "table", "nk", "poses", "hold", "frames")
 
 
+def _check_workspace(workspace: torch.Tensor, ws_bytes: int) -> None:
+    """ValueError unless `workspace` is a contiguous, 16-byte aligned uint8 tensor of at least ws_bytes bytes."""
+    _ffi.check(workspace, torch.uint8, "workspace")
+    if workspace.numel() < ws_bytes or not workspace.is_contiguous() or workspace.data_ptr() % 16:
+        raise ValueError(f"workspace must be a contiguous, 16-byte aligned uint8 tensor of at least {ws_bytes} bytes")
+
+
+def _conf_gate(c_conf_threshold: Optional[float]):
+    """(use_thresh, thresh) as the kernels take the confidence test; None: no test."""
+    return (0, 0.0) if c_conf_threshold is None else (1, float(c_conf_threshold))
+
+
 def _with_pointmap(keyframes) -> list:
     return [f for f in (keyframes._frames if hasattr(keyframes, "_frames") else list(keyframes)) if f.X_canon is not None]
 
@@ -125,7 +137,7 @@ def collect_map(keyframes, c_conf_threshold: Optional[float] = 1.5, voxel_size: 
     L = _ffi.lib()
     ws_bytes = int(L.m3_map_export_ws_bytes(k, n))
     ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
-    use, thr = (0, 0.0) if c_conf_threshold is None else (1, float(c_conf_threshold))
+    use, thr = _conf_gate(c_conf_threshold)
     st = _ffi.stream_ptr()
     _ffi.call("m3_map_export_count", _ffi.ptr(table[0]), _ffi.ptr(table[1]), _ffi.ptr(poses), _ffi.ptr(nk), k, n, use, thr,
               _ffi.ptr(ws), ws_bytes, st)
@@ -219,7 +231,7 @@ def collect_mesh(keyframes, c_conf_threshold: Optional[float] = 1.5, stride: int
     if ws_bytes <= 0:
         raise ValueError(f"{k} keyframes of {h}x{w} at stride {stride} are too many cells for one mesh (limit 2^30 - 1)")
     ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
-    use, thr = (0, 0.0) if c_conf_threshold is None else (1, float(c_conf_threshold))
+    use, thr = _conf_gate(c_conf_threshold)
     st = _ffi.stream_ptr()
     _ffi.call("m3_mesh_count", _ffi.ptr(table[0]), _ffi.ptr(table[1]), _ffi.ptr(m_.poses), _ffi.ptr(m_.nk), k, h, w, stride,
               use, thr, ratio, _ffi.ptr(ws), ws_bytes, st)
@@ -242,6 +254,22 @@ def _host(a, dtype) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=dtype)
 
 
+def _write_vertices(f, p: np.ndarray, c: np.ndarray, binary: bool, faces: Optional[int] = None) -> None:
+    """Header and vertex body of a PLY (with a face element of `faces` rows when given): one structured array, or the
+    reference's ASCII lines (%.6f)."""
+    face = "" if faces is None else f"element face {faces}\nproperty list uchar int vertex_indices\n"
+    f.write(("ply\nformat {} 1.0\nelement vertex {}\nproperty float x\nproperty float y\nproperty float z\n"
+             "property uchar red\nproperty uchar green\nproperty uchar blue\n{}end_header\n"
+             ).format("binary_little_endian" if binary else "ascii", p.shape[0], face).encode("ascii"))
+    if binary:
+        body = np.empty(p.shape[0], dtype=_PLY_DTYPE)
+        body["x"], body["y"], body["z"] = p[:, 0], p[:, 1], p[:, 2]
+        body["red"], body["green"], body["blue"] = c[:, 0], c[:, 1], c[:, 2]
+        body.tofile(f)
+    elif p.shape[0]:
+        np.savetxt(f, np.concatenate([p.astype(np.float64), c.astype(np.float64)], axis=1), fmt="%.6f %.6f %.6f %d %d %d")
+
+
 def save_ply(path, points, colors, binary: bool = True) -> int:
     """PLY with the reference's vertex properties (float x y z, uchar red green blue; slam.py:395-412).  binary: one
     structured array written in `binary_little_endian 1.0`; else the reference's ASCII lines (%.6f).  Returns M."""
@@ -249,21 +277,9 @@ def save_ply(path, points, colors, binary: bool = True) -> int:
     c = _host(colors, np.uint8).reshape(-1, 3)
     if p.shape[0] != c.shape[0]:
         raise ValueError(f"{p.shape[0]} points but {c.shape[0]} colours")
-    m = p.shape[0]
-    header = ("ply\nformat {} 1.0\nelement vertex {}\nproperty float x\nproperty float y\nproperty float z\n"
-              "property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n"
-              ).format("binary_little_endian" if binary else "ascii", m)
     with open(os.fspath(path), "wb") as f:
-        f.write(header.encode("ascii"))
-        if binary:
-            body = np.empty(m, dtype=_PLY_DTYPE)
-            body["x"], body["y"], body["z"] = p[:, 0], p[:, 1], p[:, 2]
-            body["red"], body["green"], body["blue"] = c[:, 0], c[:, 1], c[:, 2]
-            body.tofile(f)
-        elif m:
-            rows = np.concatenate([p.astype(np.float64), c.astype(np.float64)], axis=1)
-            np.savetxt(f, rows, fmt="%.6f %.6f %.6f %d %d %d")
-    return m
+        _write_vertices(f, p, c, binary)
+    return p.shape[0]
 
 
 def save_ply_mesh(path, vertices, colors, faces, binary: bool = True):
@@ -278,26 +294,14 @@ def save_ply_mesh(path, vertices, colors, faces, binary: bool = True):
     v, f = p.shape[0], t.shape[0]
     if f and (int(t.min()) < 0 or int(t.max()) >= v):
         raise ValueError(f"face indices span [{int(t.min())}, {int(t.max())}], the mesh has {v} vertices")
-    header = ("ply\nformat {} 1.0\nelement vertex {}\nproperty float x\nproperty float y\nproperty float z\n"
-              "property uchar red\nproperty uchar green\nproperty uchar blue\nelement face {}\n"
-              "property list uchar int vertex_indices\nend_header\n"
-              ).format("binary_little_endian" if binary else "ascii", v, f)
     with open(os.fspath(path), "wb") as fh:
-        fh.write(header.encode("ascii"))
+        _write_vertices(fh, p, c, binary, faces=f)
         if binary:
-            body = np.empty(v, dtype=_PLY_DTYPE)
-            body["x"], body["y"], body["z"] = p[:, 0], p[:, 1], p[:, 2]
-            body["red"], body["green"], body["blue"] = c[:, 0], c[:, 1], c[:, 2]
-            body.tofile(fh)
             tri = np.empty(f, dtype=_PLY_FACE_DTYPE)
             tri["n"], tri["v"] = 3, t
             tri.tofile(fh)
-        else:
-            if v:
-                np.savetxt(fh, np.concatenate([p.astype(np.float64), c.astype(np.float64)], axis=1),
-                           fmt="%.6f %.6f %.6f %d %d %d")
-            if f:
-                np.savetxt(fh, t, fmt="3 %d %d %d")
+        elif f:
+            np.savetxt(fh, t, fmt="3 %d %d %d")
     return v, f
 
 

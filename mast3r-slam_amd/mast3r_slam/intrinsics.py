@@ -26,7 +26,7 @@ import numpy as np
 import torch
 
 from . import _ffi
-from .export import _MapTables, _map_tables
+from .export import _MapTables, _check_workspace, _conf_gate, _map_tables, _with_pointmap
 from .render import _frame_size
 
 __all__ = ["estimate_focal", "estimate_intrinsics", "intrinsics_from_rows", "IntrinsicsEstimate"]
@@ -63,7 +63,7 @@ def _geometry(keyframes, size, principal_point):
     if isinstance(keyframes, _MapTables):
         frames, n = keyframes.frames, keyframes.n
     else:
-        frames = [f for f in (keyframes._frames if hasattr(keyframes, "_frames") else list(keyframes)) if f.X_canon is not None]
+        frames = _with_pointmap(keyframes)
         n = frames[0].X_canon.reshape(-1, 3).shape[0] if frames else None
     if size is None and frames:
         size = _frame_size(frames[0].img)
@@ -118,10 +118,8 @@ def estimate_focal(keyframes, size: Optional[Sequence[int]] = None, principal_po
         raise ValueError("out must be contiguous")
     if workspace is None:
         workspace = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
-    _ffi.check(workspace, torch.uint8, "workspace")
-    if workspace.numel() < ws_bytes or not workspace.is_contiguous() or workspace.data_ptr() % 16:
-        raise ValueError(f"workspace must be a contiguous, 16-byte aligned uint8 tensor of at least {ws_bytes} bytes")
-    use, thr = (0, 0.0) if c_conf_threshold is None else (1, float(c_conf_threshold))
+    _check_workspace(workspace, ws_bytes)
+    use, thr = _conf_gate(c_conf_threshold)
     _ffi.call("m3_focal_estimate", _ffi.ptr(m.table[0]), _ffi.ptr(m.table[1]), _ffi.ptr(m.nk), m.k, m.n, size[0], size[1],
               use, thr, pp[0], pp[1], z_min, iters, _ffi.ptr(workspace), ws_bytes, _ffi.ptr(out), _ffi.stream_ptr())
     return out

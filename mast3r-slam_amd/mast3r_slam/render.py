@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from . import _ffi
-from .export import _MapTables, _map_tables
+from .export import _MapTables, _check_workspace, _conf_gate, _map_tables
 
 __all__ = ["render_map", "default_intrinsics", "look_at", "behind", "depth_to_rgb", "save_image", "ViewRecorder"]
 
@@ -160,10 +160,8 @@ def render_map(keyframes, T_WC, K, size, c_conf_threshold: Optional[float] = 1.5
             raise ValueError(f"out {name} must be contiguous")
     if workspace is None:
         workspace = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
-    _ffi.check(workspace, torch.uint8, "workspace")
-    if workspace.numel() < ws_bytes or not workspace.is_contiguous() or workspace.data_ptr() % 16:
-        raise ValueError(f"workspace must be a contiguous, 16-byte aligned uint8 tensor of at least {ws_bytes} bytes")
-    use, thr = (0, 0.0) if c_conf_threshold is None else (1, float(c_conf_threshold))
+    _check_workspace(workspace, ws_bytes)
+    use, thr = _conf_gate(c_conf_threshold)
     if m is None:
         tabs, poses, nk, k, n, layout = (None, None, None), None, None, 0, 1, 0
     else:

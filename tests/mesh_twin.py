@@ -128,6 +128,13 @@ def make_scene(K, H, W, seed, layout, pitch=10, block=(2, 4), blob=0.15):
     return dict(X=X, C=C, Nk=Nk, T=T, img=img, layout=layout, K=K, H=H, W=W)
 
 
+def _plane(H, W):
+    """float32 [H*W,3]: the fronto-parallel plane z = 2 as the f = W pinhole sees it."""
+    v, u = np.meshgrid(np.arange(H, dtype=np.float64), np.arange(W, dtype=np.float64), indexing="ij")
+    ray = np.stack([(u - (W - 1) / 2) / W, (v - (H - 1) / 2) / W, np.ones_like(u)], axis=-1)
+    return (2.0 * ray).reshape(H * W, 3).astype(np.float32)
+
+
 def plant(sc, rng, regions=True, empty_middle=True):
     """NaN / +inf / -inf coordinates, NaN and inf confidences, a confidence exactly at THR * N_k (strict: invalid);
     regions: in keyframe 0 ten rows with everything kept and ten with nothing kept (each more than the 8 cell rows x
@@ -135,10 +142,7 @@ def plant(sc, rng, regions=True, empty_middle=True):
     K, H, W, X, C, Nk = sc["K"], sc["H"], sc["W"], sc["X"], sc["C"], sc["Nk"]
     N = H * W
     if regions and H >= 24:
-        v, u = np.meshgrid(np.arange(H, dtype=np.float64), np.arange(W, dtype=np.float64), indexing="ij")
-        ray = np.stack([(u - (W - 1) / 2) / W, (v - (H - 1) / 2) / W, np.ones_like(u)], axis=-1)
-        flat = (2.0 * ray).reshape(N, 3).astype(np.float32)
-        X[0, :11 * W] = flat[:11 * W]                                        # rows 0 .. 10: a plane, confident
+        X[0, :11 * W] = _plane(H, W)[:11 * W]                                # rows 0 .. 10: a plane, confident
         C[0, :11 * W] = 2.25 * Nk[0]
         C[0, 12 * W:23 * W] = 0.25 * Nk[0]                                   # rows 12 .. 22: nothing valid
     if empty_middle and K >= 3:
@@ -173,6 +177,17 @@ def one_cell_scene(layout):
     edge_ratio 0.8 (f = W = 2: a pixel step is about half the range)."""
     sc = make_scene(1, 2, 2, seed=1, layout=layout, pitch=9, block=(0, 0))
     sc["C"][0] = np.array([2.0, 2.0, 2.0, 1.0], np.float32) * sc["Nk"][0]
+    return sc
+
+
+def tall_scene(layout):
+    """K = 1, 4100 x 5, for stride 1, edge_ratio 0.05 and THR: 4099 cell-row segments, three more than one round of the
+    scan (4096 counts), at 20 500 points.  The last 8 image rows are a confident plane (as plant's rows 0 .. 10), so
+    kept triangles lie in cell rows >= 4096 and a wrong carry into the second round moves their rows."""
+    sc = plant(make_scene(1, 4100, 5, seed=11, layout=layout, pitch=64, blob=0.02), np.random.default_rng(111), regions=False)
+    last = 8 * sc["W"]
+    sc["X"][0, -last:] = _plane(sc["H"], sc["W"])[-last:]
+    sc["C"][0, -last:] = 2.25 * sc["Nk"][0]
     return sc
 
 

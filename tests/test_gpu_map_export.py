@@ -124,7 +124,7 @@ def check(sc, dev, thr):
 
 
 SHAPES = [(1, 3), (3, 3), (1, 4999), (3, 4999), (17, 4999), (1, 128 * 256), (3, 128 * 256), (17, 128 * 256),
-          (1, 512 * 512), (3, 512 * 512)]
+          (1, 512 * 512), (3, 512 * 512), (4100, 3)]                          # 4100 tiles: a second round of the scan (4096)
 
 
 @pytest.mark.parametrize("layout", ["f32", "u8"])
@@ -134,6 +134,8 @@ def test_selection_points_colours_order(dev, K, N, layout):
     m = check(sc, dev, THR)
     if N > 100:
         assert 0.3 * K * N < m < 0.7 * K * N                                   # the threshold really splits the data
+    if K * -(-N // 1024) > 4096:
+        assert expected(sc, THR)[0].max() >= 4096 * N                          # kept points behind the carry of round one
 
 
 @pytest.mark.parametrize("layout", ["f32", "u8"])
