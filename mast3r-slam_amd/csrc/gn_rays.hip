@@ -11,7 +11,7 @@
 // With the reference's "simplified adjoint" Ji = -Jj (gauss_newton.py:189-213) the five
 // blocks of an edge are +-Hjj and +-gj, so only Hjj (28) and gj (7) are accumulated.
 #include "common.h"
-#include "sim3_dev.h"
+#include "accum_dev.h"
 
 // blocked float64 Cholesky solve (gn_chol.hip)
 int m3_chol_solve_launch(double *H, double *b, double *y, double *x, double *Ld, double *fail, const double *off, int dim,
@@ -21,7 +21,6 @@ int64_t m3_chol_diag_doubles(int dim);
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kSums = 36;         // 28 Hjj upper + 7 gj + 1 count
 constexpr int kMaxChunks = 128;
 constexpr int kPtsPerChunk = 2048;
 constexpr int kSolveThreads = 1024;
@@ -87,9 +86,11 @@ __device__ __forceinline__ bool gn_point(const Pose<float> &Tij, float s_inv, co
     return true;
 }
 
-// 4 consecutive points of the edge per lane and trip: validity (4 bytes), Q, idx, C_j and X_j come in as dwordx4
-// loads with the next trip's loads issued before this trip's arithmetic; only X_i / C_i at the match index are
-// gathers.  fp32 sums over the <= 4 points, one float64 fold per trip (see k_track_accum).
+// 4 consecutive points of the edge per lane and trip (walk_groups of accum_dev.h): validity (4 bytes), Q, idx, C_j and
+// X_j come in as dwordx4 loads; only X_i / C_i at the match index are gathers.  The 36 sums are 28 Hjj upper + 7 gj +
+// 1 count.
+struct BlockGroup { float4 xj[3], q, c; int4 id; unsigned v = 0; };
+
 template <int MODE>
 __global__ void __launch_bounds__(kThreads)
 k_gn_blocks(const float *__restrict__ Twc, const float *__restrict__ Xs, const float *__restrict__ Cs,
@@ -114,7 +115,7 @@ k_gn_blocks(const float *__restrict__ Twc, const float *__restrict__ Xs, const f
         const float *Xi_base = Xs + (size_t)ix * P * 3, *Xj_base = Xs + (size_t)jx * P * 3;
         const float *Ci = Cs + (size_t)ix * P, *Cj = Cs + (size_t)jx * P;
         const size_t eo = (size_t)e * P;
-        auto one = [&](int k, bool vld, float qc, int id, float cj, const V3<float> &Xj, float *h) {
+        auto one = [&](bool vld, float qc, int id, float cj, const V3<float> &Xj, float *h) {
             if (!vld) return;
             if (id < 0) id += P;
             id = id < 0 ? 0 : (id >= P ? P - 1 : id);
@@ -122,49 +123,28 @@ k_gn_blocks(const float *__restrict__ Twc, const float *__restrict__ Xs, const f
             gn_point<MODE>(Tij, s_inv, V3<float>{Xi_base[3 * id], Xi_base[3 * id + 1], Xi_base[3 * id + 2]}, Xj, qc,
                            inv_sigma, cal, h);
         };
-        const bool vec = (P % 4 == 0) && ((reinterpret_cast<size_t>(Xs) | reinterpret_cast<size_t>(Cs) | reinterpret_cast<size_t>(Q) |
-                                           reinterpret_cast<size_t>(idx)) % 16 == 0) && (reinterpret_cast<size_t>(valid) % 4 == 0);
-        if (vec) {
-            const int groups = P / 4, stride = chunks * kThreads;
-            int gi = chunk * kThreads + threadIdx.x;
-            float4 xj[3], q4, c4;
-            int4 i4;
-            unsigned v = 0;
-            auto load = [&](int g) {
-                const float4 *px = reinterpret_cast<const float4 *>(Xj_base) + 3 * (size_t)g;
-                xj[0] = px[0]; xj[1] = px[1]; xj[2] = px[2];
-                q4 = reinterpret_cast<const float4 *>(Q + eo)[g];
-                c4 = reinterpret_cast<const float4 *>(Cj)[g];
-                i4 = reinterpret_cast<const int4 *>(idx + eo)[g];
-                v = reinterpret_cast<const unsigned *>(valid + eo)[g];
-            };
-            if (gi < groups) load(gi);
-            while (gi < groups) {
-                const float4 x0 = xj[0], x1 = xj[1], x2 = xj[2], qq = q4, cc = c4;
-                const int4 id4 = i4;
-                const unsigned vv = v;
-                const int nx = gi + stride;
-                if (nx < groups) load(nx);
-                float h[kSums];
-#pragma unroll
-                for (int i = 0; i < kSums; ++i) h[i] = 0.f;
-                one(4 * gi + 0, vv & 0x000000ffu, qq.x, id4.x, cc.x, V3<float>{x0.x, x0.y, x0.z}, h);
-                one(4 * gi + 1, vv & 0x0000ff00u, qq.y, id4.y, cc.y, V3<float>{x0.w, x1.x, x1.y}, h);
-                one(4 * gi + 2, vv & 0x00ff0000u, qq.z, id4.z, cc.z, V3<float>{x1.z, x1.w, x2.x}, h);
-                one(4 * gi + 3, vv & 0xff000000u, qq.w, id4.w, cc.w, V3<float>{x2.y, x2.z, x2.w}, h);
-#pragma unroll
-                for (int i = 0; i < kSums; ++i) acc[i] += (double)h[i];
-                gi = nx;
-            }
+        if (vec16_ok(P, valid, Xs, Cs, Q, idx)) {
+            walk_groups<kSums, BlockGroup>(P / 4, chunk * kThreads + threadIdx.x, chunks * kThreads, acc,
+                [&](int g, BlockGroup &r) {
+                    const float4 *px = reinterpret_cast<const float4 *>(Xj_base) + 3 * (size_t)g;
+                    r.xj[0] = px[0]; r.xj[1] = px[1]; r.xj[2] = px[2];
+                    r.q = reinterpret_cast<const float4 *>(Q + eo)[g];
+                    r.c = reinterpret_cast<const float4 *>(Cj)[g];
+                    r.id = reinterpret_cast<const int4 *>(idx + eo)[g];
+                    r.v = reinterpret_cast<const unsigned *>(valid + eo)[g];
+                },
+                [&](int, const BlockGroup &r, float (&h)[kSums]) {
+                    V3<float> Xj[4];
+                    unpack4(r.xj[0], r.xj[1], r.xj[2], Xj);
+                    one(valid4(r.v, 0), r.q.x, r.id.x, r.c.x, Xj[0], h);
+                    one(valid4(r.v, 1), r.q.y, r.id.y, r.c.y, Xj[1], h);
+                    one(valid4(r.v, 2), r.q.z, r.id.z, r.c.z, Xj[2], h);
+                    one(valid4(r.v, 3), r.q.w, r.id.w, r.c.w, Xj[3], h);
+                });
         } else {
-            for (int k = chunk * kThreads + threadIdx.x; k < P; k += chunks * kThreads) {
-                float h[kSums];
-#pragma unroll
-                for (int i = 0; i < kSums; ++i) h[i] = 0.f;
-                one(k, valid[eo + k] != 0, Q[eo + k], idx[eo + k], Cj[k], V3<float>{Xj_base[3 * k], Xj_base[3 * k + 1], Xj_base[3 * k + 2]}, h);
-#pragma unroll
-                for (int i = 0; i < kSums; ++i) acc[i] += (double)h[i];
-            }
+            walk_points<kSums>(P, chunk * kThreads + threadIdx.x, chunks * kThreads, acc, [&](int k, float (&h)[kSums]) {
+                one(valid[eo + k] != 0, Q[eo + k], idx[eo + k], Cj[k], V3<float>{Xj_base[3 * k], Xj_base[3 * k + 1], Xj_base[3 * k + 2]}, h);
+            });
         }
     }
     m3_block_reduce36(acc, part + ((size_t)e * chunks + chunk) * kSums);
@@ -187,7 +167,7 @@ k_gn_reduce(const double *__restrict__ part, double *__restrict__ blocks, const 
         Hp[r][r + k] = s; Hp[r + k][r] = s;
     } else if (t < 35) gp[t - 28] = s;
     else if (t == 35) blocks[(size_t)e * kSums + 35] = s;
-    if (t < 49) G[t / 7][t % 7] = (t / 7 == t % 7 && t == 48) ? 1.0 : 0.0;
+    if (t < 49) G[t / 7][t % 7] = (t == 48) ? 1.0 : 0.0;        // G[6][6] = 1; thread 0 fills in the two R_i below
     __syncthreads();
     const int ix = ii[e];
     if (t == 0 && ix >= 0 && ix < K) {
@@ -275,6 +255,21 @@ k_gn_assemble(const double *__restrict__ blocks, const int32_t *__restrict__ ii,
     else if (t < 56) g[a * 7 + (t - 49)] = gv;
 }
 
+// The solve failed (a pivot that is not positive, a non-finite or overflowing step): stop, and say why.
+__device__ __forceinline__ void report_failure(double *__restrict__ info) {
+    if (threadIdx.x == 0) { info[2] = 1.0; info[3] = 1.0; }
+}
+
+// T <- exp(dx) T for the free keyframes first, first + stride, ... < K
+__device__ __forceinline__ void retract_free(float *__restrict__ Twc, const double *__restrict__ x,
+                                             const int32_t *__restrict__ local, int K, int first, int stride) {
+    for (int kf = first; kf < K; kf += stride) {
+        const int l = local[kf];
+        if (l < 0) continue;
+        store_pose(Twc + 8 * kf, retract_ops(x + 7 * l, load_pose<double>(Twc + 8 * kf)));
+    }
+}
+
 // After the solve (dx in x[0..dim)): |dx|, largest scale step, stop test, retraction T <- exp(dx) T of the free
 // keyframes.  One workgroup; shared by the single-workgroup solver and the blocked one (gn_chol.hip).
 __device__ void gn_step_tail(double *__restrict__ x, float *__restrict__ Twc, const int32_t *__restrict__ local,
@@ -302,7 +297,7 @@ __device__ void gn_step_tail(double *__restrict__ x, float *__restrict__ Twc, co
     const double dn = sqrt(nrm2);
     if (t == 0) info[1] = dn;
     if (!isfinite(dn) || smax > 30.0) {                     // a scale step e^sigma beyond float range (degenerate
-        if (t == 0) { info[2] = 1.0; info[3] = 1.0; }       // geometry): report failure, keep the poses
+        report_failure(info);                               // geometry): keep the poses
         return;
     }
     if (dn < (double)delta_thresh) {                        // stop BEFORE the update (gauss_newton.py:262-265)
@@ -310,14 +305,9 @@ __device__ void gn_step_tail(double *__restrict__ x, float *__restrict__ Twc, co
         return;
     }
     if (!apply) return;
-    for (int kf = t; kf < K; kf += (int)blockDim.x) {
-        const int l = local[kf];
-        if (l < 0) continue;
-        store_pose(Twc + 8 * kf, retract_ops(x + 7 * l, load_pose<double>(Twc + 8 * kf)));
-    }
+    retract_free(Twc, x, local, K, t, (int)blockDim.x);
     if (t == 0) info[0] += 1.0;
 }
-
 
 // One workgroup: (H + 1e-6 I) dx = -g by in-place Cholesky (lower) + two triangular solves,
 // stop test, then T <- exp(dx) T for the free keyframes.  dx is left in x[0..dim).
@@ -352,10 +342,7 @@ k_gn_step(double *__restrict__ H, double *__restrict__ g, double *__restrict__ x
         }
         __syncthreads();
     }
-    if (fail) {
-        if (t == 0) { info[2] = 1.0; info[3] = 1.0; }
-        return;
-    }
+    if (fail) return report_failure(info);
     for (int k = 0; k < dim; ++k) {                         // L y = b
         if (t == 0) x[k] = x[k] / H[(size_t)k * dim + k];
         __syncthreads();
@@ -378,10 +365,7 @@ __global__ void __launch_bounds__(kSolveThreads)
 k_gn_tail(double *__restrict__ x, float *__restrict__ Twc, const int32_t *__restrict__ local, double *__restrict__ info,
           const double *__restrict__ fail, int K, int dim, float delta_thresh, int apply) {
     if (info[2] != 0.0) return;
-    if (fail[0] != 0.0) {
-        if (threadIdx.x == 0) { info[2] = 1.0; info[3] = 1.0; }
-        return;
-    }
+    if (fail[0] != 0.0) return report_failure(info);
     gn_step_tail(x, Twc, local, info, K, dim, delta_thresh, apply);
 }
 
@@ -393,11 +377,7 @@ __global__ void k_gn_neg_rhs(const double *__restrict__ g, double *__restrict__ 
 
 __global__ void __launch_bounds__(kThreads)
 k_gn_retract(float *__restrict__ Twc, const double *__restrict__ dx, const int32_t *__restrict__ local, int K) {
-    const int kf = blockIdx.x * kThreads + threadIdx.x;
-    if (kf >= K) return;
-    const int l = local[kf];
-    if (l < 0) return;
-    store_pose(Twc + 8 * kf, retract_ops(dx + 7 * l, load_pose<double>(Twc + 8 * kf)));
+    retract_free(Twc, dx, local, K, blockIdx.x * kThreads + threadIdx.x, gridDim.x * kThreads);
 }
 
 __global__ void k_gn_info_init(double *info) {
@@ -414,46 +394,73 @@ CalibParams make_calib(const float *c) {
     return p;
 }
 
+// Hbuf = H [dim*dim] | g | x | b | y [dim each] | fail [8] | Ld [m3_chol_diag_doubles(dim), blocked solve only]
+struct HbufViews {
+    double *H, *g, *x, *b, *y, *fail, *Ld;
+    HbufViews(double *p, int dim) : H(p), g(H + (size_t)dim * dim), x(g + dim), b(x + dim), y(b + dim), fail(y + dim), Ld(fail + 8) {}
+    static int64_t doubles(int dim) {
+        return (int64_t)dim * dim + 4 * (int64_t)dim + 8 + (dim > kMaxDim ? m3_chol_diag_doubles(dim) : 0);
+    }
+};
 
 // One Gauss-Newton step from an assembled system, any size, stream-ordered: dim <= kMaxDim -> the single-workgroup
-// kernel; larger -> blocked Cholesky (gn_chol.hip) + k_gn_tail.  Hbuf = H [dim*dim] | g | x | b | y [dim each] | fail [8]
-// | Ld [m3_chol_diag_doubles(dim)] = m3_gn_rays_hbuf_doubles(dim).
-int launch_step(double *Hbuf, float *Twc, const int32_t *local, double *info, int K, int dim, float delta_thresh,
+// kernel; larger -> blocked Cholesky (gn_chol.hip) + k_gn_tail.
+int launch_step(const HbufViews &v, float *Twc, const int32_t *local, double *info, int K, int dim, float delta_thresh,
                 int apply, hipStream_t st) {
-    double *H = Hbuf, *g = Hbuf + (size_t)dim * dim, *x = g + dim, *b = x + dim, *y = b + dim, *fail = y + dim;
     if (dim <= kMaxDim) {
-        hipLaunchKernelGGL(k_gn_step, dim3(1), dim3(kSolveThreads), 0, st, H, g, x, Twc, local, info, K, dim, delta_thresh, apply);
+        hipLaunchKernelGGL(k_gn_step, dim3(1), dim3(kSolveThreads), 0, st, v.H, v.g, v.x, Twc, local, info, K, dim, delta_thresh, apply);
         M3_CHECK_LAUNCH("m3_gn_rays/step");
         return M3_OK;
     }
-    hipLaunchKernelGGL(k_gn_neg_rhs, dim3(m3_cdiv(dim, 256)), dim3(256), 0, st, (const double *)g, b, fail, dim);
-    const int rc = m3_chol_solve_launch(H, b, y, x, fail + 8, fail, info + 2, dim, 1e-6, st);
+    hipLaunchKernelGGL(k_gn_neg_rhs, dim3(m3_cdiv(dim, 256)), dim3(256), 0, st, (const double *)v.g, v.b, v.fail, dim);
+    const int rc = m3_chol_solve_launch(v.H, v.b, v.y, v.x, v.Ld, v.fail, info + 2, dim, 1e-6, st);
     if (rc != M3_OK) return rc;
-    hipLaunchKernelGGL(k_gn_tail, dim3(1), dim3(kSolveThreads), 0, st, x, Twc, local, info, (const double *)fail, K, dim,
+    hipLaunchKernelGGL(k_gn_tail, dim3(1), dim3(kSolveThreads), 0, st, v.x, Twc, local, info, (const double *)v.fail, K, dim,
                        delta_thresh, apply);
     M3_CHECK_LAUNCH("m3_gn_rays/tail");
     return M3_OK;
 }
 
-int launch_blocks(const float *Twc, const float *Xs, const float *Cs, const int32_t *ii, const int32_t *jj,
-                  const int32_t *idx, const uint8_t *valid, const float *Q, double *blocks, double *ws,
-                  const double *done, int K, int P, int E, float sigma_ray, float C_thresh, float Q_thresh,
-                  int point_mode, const CalibParams &cal, hipStream_t st) {
+// Clear H and gather the per-edge blocks into the dense system (H, g) of dim = 7 * num_free unknowns.
+int launch_assemble(const double *blocks, const int32_t *ii, const int32_t *jj, const int32_t *local, double *H, double *g,
+                    const double *done, int K, int dim, int E, const char *memset_label, const char *label, hipStream_t st) {
+    M3_CHECK_HIP(hipMemsetAsync(H, 0, (size_t)dim * dim * sizeof(double), st), memset_label);
+    hipLaunchKernelGGL(k_gn_assemble, dim3(dim / 7), dim3(64), 0, st, blocks, ii, jj, local, H, g, done, K, dim, E);
+    M3_CHECK_LAUNCH(label);
+    return M3_OK;
+}
+
+// One iteration from the per-edge blocks: assemble -> factor -> solve -> stop test -> retract; a no-op once info says stop.
+int launch_assemble_step(float *Twc, const double *blocks, const int32_t *ii, const int32_t *jj, const int32_t *local,
+                         double *Hbuf, double *info, int K, int dim, int E, float delta_thresh, const char *memset_label,
+                         const char *label, hipStream_t st) {
+    const HbufViews v(Hbuf, dim);
+    const int rc = launch_assemble(blocks, ii, jj, local, v.H, v.g, info + 2, K, dim, E, memset_label, label, st);
+    return rc != M3_OK ? rc : launch_step(v, Twc, local, info, K, dim, delta_thresh, 1, st);
+}
+
+// What m3_gn_rays_blocks and m3_gn_rays_solve pass on to the blocks launch, and what they require of it
+struct BlocksArgs {
+    const float *Twc, *Xs, *Cs; const int32_t *ii, *jj, *idx; const uint8_t *valid; const float *Q; double *blocks, *ws;
+    int K, P, E; float sigma_ray, C_thresh, Q_thresh; int point_mode; const float *calib;
+    bool ok() const {
+        return Twc && Xs && Cs && ii && jj && idx && valid && Q && blocks && ws && K > 0 && P > 0 && E > 0 && E <= 65535 &&
+               sigma_ray > 0.f && point_mode >= 0 && point_mode <= 2 && (point_mode != 2 || calib);
+    }
+};
+
+int launch_blocks(const BlocksArgs &a, const double *done, hipStream_t st) {
     // chunks per edge: enough workgroups to fill the chip (~2048 over all edges) but no more - every chunk
     // ends in a 36-value float64 block reduction.  Never more than m3_gn_rays_chunks(P), the count the
     // caller sized the workspace for.  (config 5, 180 edges x 262144 points: 1.69 -> 1.47 ms)
-    int chunks = m3_cdiv(2048, E);
-    if (chunks > gn_chunks(P)) chunks = gn_chunks(P);
+    int chunks = m3_cdiv(2048, a.E);
+    if (chunks > gn_chunks(a.P)) chunks = gn_chunks(a.P);
     if (chunks < 1) chunks = 1;
-    const float inv_sigma = (float)(1.0 / (double)sigma_ray);
-    const dim3 grid(chunks, E), blk(kThreads);
-    if (point_mode == 0)
-        hipLaunchKernelGGL(k_gn_blocks<0>, grid, blk, 0, st, Twc, Xs, Cs, ii, jj, idx, valid, Q, ws, done, K, P, chunks, inv_sigma, C_thresh, Q_thresh, cal);
-    else if (point_mode == 1)
-        hipLaunchKernelGGL(k_gn_blocks<1>, grid, blk, 0, st, Twc, Xs, Cs, ii, jj, idx, valid, Q, ws, done, K, P, chunks, inv_sigma, C_thresh, Q_thresh, cal);
-    else
-        hipLaunchKernelGGL(k_gn_blocks<2>, grid, blk, 0, st, Twc, Xs, Cs, ii, jj, idx, valid, Q, ws, done, K, P, chunks, inv_sigma, C_thresh, Q_thresh, cal);
-    hipLaunchKernelGGL(k_gn_reduce, dim3(E), dim3(64), 0, st, (const double *)ws, blocks, done, Twc, ii, K, chunks);
+    const float inv_sigma = (float)(1.0 / (double)a.sigma_ray);
+    const auto kernel = a.point_mode == 0 ? k_gn_blocks<0> : a.point_mode == 1 ? k_gn_blocks<1> : k_gn_blocks<2>;
+    hipLaunchKernelGGL(kernel, dim3(chunks, a.E), dim3(kThreads), 0, st, a.Twc, a.Xs, a.Cs, a.ii, a.jj, a.idx, a.valid, a.Q, a.ws,
+                       done, a.K, a.P, chunks, inv_sigma, a.C_thresh, a.Q_thresh, make_calib(a.calib));
+    hipLaunchKernelGGL(k_gn_reduce, dim3(a.E), dim3(64), 0, st, (const double *)a.ws, a.blocks, done, a.Twc, a.ii, a.K, chunks);
     M3_CHECK_LAUNCH("m3_gn_rays_blocks");
     return M3_OK;
 }
@@ -464,31 +471,22 @@ extern "C" {
 
 int m3_gn_rays_chunks(int P) { return gn_chunks(P); }
 int m3_gn_rays_max_dim(void) { return kMaxDim; }
-int64_t m3_gn_rays_hbuf_doubles(int dim) {
-    return (int64_t)dim * dim + 4 * (int64_t)dim + 8 + (dim > kMaxDim ? m3_chol_diag_doubles(dim) : 0);
-}
+int64_t m3_gn_rays_hbuf_doubles(int dim) { return HbufViews::doubles(dim); }
 
 int m3_gn_rays_blocks(const float *Twc, const float *Xs, const float *Cs, const int32_t *ii, const int32_t *jj,
                       const int32_t *idx, const uint8_t *valid, const float *Q, double *blocks, double *ws,
                       int K, int P, int E, float sigma_ray, float C_thresh, float Q_thresh, int point_mode, const float *calib,
                       void *stream) {
-    M3_REQUIRE(Twc && Xs && Cs && ii && jj && idx && valid && Q && blocks && ws);
-    M3_REQUIRE(K > 0 && P > 0 && E > 0 && E <= 65535 && sigma_ray > 0.f && point_mode >= 0 && point_mode <= 2);
-    M3_REQUIRE(point_mode != 2 || calib);
-    return launch_blocks(Twc, Xs, Cs, ii, jj, idx, valid, Q, blocks, ws, nullptr, K, P, E, sigma_ray, C_thresh,
-                         Q_thresh, point_mode, make_calib(calib), (hipStream_t)stream);
+    const BlocksArgs a{Twc, Xs, Cs, ii, jj, idx, valid, Q, blocks, ws, K, P, E, sigma_ray, C_thresh, Q_thresh, point_mode, calib};
+    M3_REQUIRE(a.ok());
+    return launch_blocks(a, nullptr, (hipStream_t)stream);
 }
 
 int m3_gn_rays_assemble(const double *blocks, const int32_t *ii, const int32_t *jj, const int32_t *local,
                         double *H, double *g, int K, int E, int num_free, void *stream) {
     M3_REQUIRE(blocks && ii && jj && local && H && g && K > 0 && E > 0 && num_free > 0);
-    hipStream_t st = (hipStream_t)stream;
-    const int dim = 7 * num_free;
-    M3_CHECK_HIP(hipMemsetAsync(H, 0, (size_t)dim * dim * sizeof(double), st), "m3_gn_rays_assemble/memset");
-    hipLaunchKernelGGL(k_gn_assemble, dim3(num_free), dim3(64), 0, st, blocks, ii, jj, local, H, g,
-                       (const double *)nullptr, K, dim, E);
-    M3_CHECK_LAUNCH("m3_gn_rays_assemble");
-    return M3_OK;
+    return launch_assemble(blocks, ii, jj, local, H, g, nullptr, K, 7 * num_free, E, "m3_gn_rays_assemble/memset",
+                           "m3_gn_rays_assemble", (hipStream_t)stream);
 }
 
 int m3_gn_rays_retract(float *Twc, const double *dx, const int32_t *local, int K, void *stream) {
@@ -504,24 +502,15 @@ int m3_gn_rays_solve(float *Twc, const float *Xs, const float *Cs, const int32_t
                      double *blocks, double *ws, double *Hbuf, double *info, int K, int P, int E, int num_free,
                      float sigma_ray, float C_thresh, float Q_thresh, int max_iter, float delta_thresh,
                      int point_mode, const float *calib, void *stream) {
-    M3_REQUIRE(Twc && Xs && Cs && ii && jj && idx && valid && Q && local && blocks && ws && Hbuf && info);
-    M3_REQUIRE(K > 0 && P > 0 && E > 0 && E <= 65535 && num_free > 0 && max_iter >= 0 && sigma_ray > 0.f);
-    M3_REQUIRE(point_mode >= 0 && point_mode <= 2 && (point_mode != 2 || calib));
-    const CalibParams cal = make_calib(calib);
-    const int dim = 7 * num_free;
+    const BlocksArgs a{Twc, Xs, Cs, ii, jj, idx, valid, Q, blocks, ws, K, P, E, sigma_ray, C_thresh, Q_thresh, point_mode, calib};
+    M3_REQUIRE(a.ok() && local && Hbuf && info && num_free > 0 && max_iter >= 0);
     hipStream_t st = (hipStream_t)stream;
-    double *H = Hbuf, *g = Hbuf + (size_t)dim * dim;          // Hbuf: m3_gn_rays_hbuf_doubles(dim)
-    const double *done = info + 2;
     hipLaunchKernelGGL(k_gn_info_init, dim3(1), dim3(64), 0, st, info);
     for (int it = 0; it < max_iter; ++it) {
-        int rc = launch_blocks(Twc, Xs, Cs, ii, jj, idx, valid, Q, blocks, ws, done, K, P, E, sigma_ray, C_thresh,
-                               Q_thresh, point_mode, cal, st);
-        if (rc != M3_OK) return rc;
-        M3_CHECK_HIP(hipMemsetAsync(H, 0, (size_t)dim * dim * sizeof(double), st), "m3_gn_rays_solve/memset");
-        hipLaunchKernelGGL(k_gn_assemble, dim3(num_free), dim3(64), 0, st, (const double *)blocks, ii, jj,
-                           local, H, g, done, K, dim, E);
-        M3_CHECK_LAUNCH("m3_gn_rays_solve/iter");
-        rc = launch_step(Hbuf, Twc, local, info, K, dim, delta_thresh, 1, st);
+        int rc = launch_blocks(a, info + 2, st);
+        if (rc == M3_OK)
+            rc = launch_assemble_step(Twc, blocks, ii, jj, local, Hbuf, info, K, 7 * num_free, E, delta_thresh,
+                                      "m3_gn_rays_solve/memset", "m3_gn_rays_solve/iter", st);
         if (rc != M3_OK) return rc;
     }
     return M3_OK;
@@ -533,14 +522,8 @@ int m3_gn_rays_solve(float *Twc, const float *Xs, const float *Cs, const int32_t
 int m3_gn_rays_step(float *Twc, const double *blocks, const int32_t *ii, const int32_t *jj, const int32_t *local,
                     double *Hbuf, double *info, int K, int E, int num_free, float delta_thresh, void *stream) {
     M3_REQUIRE(Twc && blocks && ii && jj && local && Hbuf && info && K > 0 && E > 0 && num_free > 0);
-    hipStream_t st = (hipStream_t)stream;
-    const int dim = 7 * num_free;
-    double *H = Hbuf, *g = Hbuf + (size_t)dim * dim;
-    M3_CHECK_HIP(hipMemsetAsync(H, 0, (size_t)dim * dim * sizeof(double), st), "m3_gn_rays_step/memset");
-    hipLaunchKernelGGL(k_gn_assemble, dim3(num_free), dim3(64), 0, st, blocks, ii, jj, local, H, g,
-                       (const double *)(info + 2), K, dim, E);
-    M3_CHECK_LAUNCH("m3_gn_rays_step/assemble");
-    return launch_step(Hbuf, Twc, local, info, K, dim, delta_thresh, 1, st);
+    return launch_assemble_step(Twc, blocks, ii, jj, local, Hbuf, info, K, 7 * num_free, E, delta_thresh,
+                                "m3_gn_rays_step/memset", "m3_gn_rays_step/assemble", (hipStream_t)stream);
 }
 
 int m3_gn_rays_info_init(double *info, void *stream) {

@@ -127,33 +127,6 @@ __device__ inline Pose<double> retract_ops(const double *xi, Pose<double> T) {  
     return R;
 }
 
-// Dense n x n solve by Gaussian elimination with partial pivoting (n <= 7), in place.
-// Returns false when a pivot is exactly zero / non-finite.
-template <int NN> __device__ inline bool solve_small(double (*A)[NN], double *b, int n) {
-    for (int k = 0; k < n; ++k) {
-        int piv = k;
-        double best = fabs(A[k][k]);
-        for (int r = k + 1; r < n; ++r) { double v = fabs(A[r][k]); if (v > best) { best = v; piv = r; } }
-        if (!(best > 0.0) || !isfinite(best)) return false;
-        if (piv != k) {
-            for (int c = 0; c < n; ++c) { double t = A[k][c]; A[k][c] = A[piv][c]; A[piv][c] = t; }
-            double t = b[k]; b[k] = b[piv]; b[piv] = t;
-        }
-        const double inv = 1.0 / A[k][k];
-        for (int r = k + 1; r < n; ++r) {
-            const double f = A[r][k] * inv;
-            for (int c = k; c < n; ++c) A[r][c] -= f * A[k][c];
-            b[r] -= f * b[k];
-        }
-    }
-    for (int k = n - 1; k >= 0; --k) {
-        double v = b[k];
-        for (int c = k + 1; c < n; ++c) v -= A[k][c] * b[c];
-        b[k] = v / A[k][k];
-    }
-    return true;
-}
-
 // ---- normal-equation contribution of one point whose Jacobian rows are J_c = M(p) a_c --------------------------
 // M(p) = [st * I ; [p]x ; p^T]  (7 x 3: J = [st * a, p x a, a . p] - Sim(3) tangent order translation, rotation,
 // scale).  With A = sum_c w_c a_c a_c^T (3 x 3 symmetric) and b = sum_c w_c r_c a_c:

@@ -22,13 +22,12 @@
 // launch sequence of both solves.  The exception is the weighted-row loop inside the two per-point functions (see there).
 #include "common.h"
 #include <cstdlib>
-#include "sim3_dev.h"
+#include "accum_dev.h"
 
 namespace {
 
 constexpr int kThreads = 256;
 constexpr int kBlocks = 256;          // most partial rows a problem can have (workspace size)
-constexpr int kSums = 36;             // 28 (H upper) + 7 (g) + 1 (cost)
 // workspace layout (doubles): two state slots and two partial buffers, indexed by the parity of the number of solved steps
 constexpr int WS_T = 0;               // T_CkCf [8]
 constexpr int WS_OLD = 8;             // old cost
@@ -343,6 +342,8 @@ struct Calib {
 // (The calibrated model first walked one point per lane with an integer division per point: 49.6 us per iteration
 // against 25.5 us for the ray-distance solve on the same streams; here it divides once per group.)
 // Sizes and pointers that do not allow 16-byte accesses, or a model that refuses groups, take the one-point loop.
+// (k_gn_blocks runs this loop from accum_dev.h.  Here it stays written out: on the shared walker the calibrated solve
+// measured 27.30 us per iteration against 26.64-27.04 us as written here - profiles/backend_gn_refactor.md, section 4.)
 template <class Model>
 __global__ void __launch_bounds__(kThreads)
 k_track_accum(const float *__restrict__ Xf, const float *__restrict__ Xk, const float *__restrict__ Qk,

@@ -129,18 +129,21 @@ def _calib_ptr(calib):
     return (ctypes.c_float * 10)(*[float(v) for v in calib])
 
 
+def _gn_blocks_call(t, edges, blocks, ws, sigma_ray, C_thresh, Q_thresh, point_mode, calib):
+    """m3_gn_rays_blocks on the prepared tensors `t` for the edge arrays `edges`: all of them, or one rank's shard."""
+    _ffi.call("m3_gn_rays_blocks", *(_ffi.ptr(x) for x in (t["Twc"], t["Xs"], t["Cs"], edges["ii"], edges["jj"], edges["idx"],
+              edges["valid"], edges["Q"], blocks, ws)), t["K"], t["P"], edges["ii"].numel(), float(sigma_ray), float(C_thresh),
+              float(Q_thresh), int(point_mode), _calib_ptr(calib), _ffi.stream_ptr())
+
+
 def gn_rays_blocks(Twc, Xs, Cs, ii, jj, idx_ii2jj, valid_match, Q, sigma_ray: float = 0.003,
-                   C_thresh: float = 0.0, Q_thresh: float = 1.5, point_mode: bool = False):
-    """Per-edge normal-equation blocks [E,36] float64 = (Hjj upper 28, gj 7, count)."""
+                   C_thresh: float = 0.0, Q_thresh: float = 1.5, point_mode: int = 0, calib=None):
+    """Per-edge normal-equation blocks [E,36] float64 = (Hjj upper 28, gj 7, count).  point_mode 0 rays / 1 (or True)
+    points / 2 calib, which needs calib = (fx, fy, cx, cy, width, height, border, z_eps, sigma_pixel, sigma_depth)."""
     t = _prep_gn(Twc, Xs, Cs, ii, jj, idx_ii2jj, valid_match, Q)
-    k, p, e = t["K"], t["P"], t["E"]
-    chunks = _ffi.lib().m3_gn_rays_chunks(p)
-    blocks = torch.empty((e, 36), dtype=torch.float64, device=t["Twc"].device)
-    ws = torch.empty(e * chunks * 36, dtype=torch.float64, device=t["Twc"].device)
-    _ffi.call("m3_gn_rays_blocks", _ffi.ptr(t["Twc"]), _ffi.ptr(t["Xs"]), _ffi.ptr(t["Cs"]), _ffi.ptr(t["ii"]),
-              _ffi.ptr(t["jj"]), _ffi.ptr(t["idx"]), _ffi.ptr(t["valid"]), _ffi.ptr(t["Q"]), _ffi.ptr(blocks),
-              _ffi.ptr(ws), k, p, e, float(sigma_ray), float(C_thresh), float(Q_thresh), int(point_mode), None,
-              _ffi.stream_ptr())
+    blocks = torch.empty((t["E"], 36), dtype=torch.float64, device=t["Twc"].device)
+    ws = torch.empty(t["E"] * _ffi.lib().m3_gn_rays_chunks(t["P"]) * 36, dtype=torch.float64, device=t["Twc"].device)
+    _gn_blocks_call(t, t, blocks, ws, sigma_ray, C_thresh, Q_thresh, point_mode, calib)
     return _out(blocks, t["np_in"])
 
 
@@ -252,10 +255,7 @@ def gauss_newton_rays(Twc, Xs, Cs, ii, jj, idx_ii2jj, valid_match, Q, sigma_ray:
         _ffi.call("m3_gn_rays_info_init", _ffi.ptr(info), st)
         for _ in range(max_iter):
             if e_loc:
-                _ffi.call("m3_gn_rays_blocks", _ffi.ptr(twc), _ffi.ptr(t["Xs"]), _ffi.ptr(t["Cs"]), _ffi.ptr(loc["ii"]),
-                          _ffi.ptr(loc["jj"]), _ffi.ptr(loc["idx"]), _ffi.ptr(loc["valid"]), _ffi.ptr(loc["Q"]),
-                          _ffi.ptr(blocks_loc), _ffi.ptr(ws), k, p, e_loc, float(sigma_ray), float(C_thresh),
-                          float(Q_thresh), int(_point_mode), _calib_ptr(_calib), st)
+                _gn_blocks_call(dict(t, Twc=twc), loc, blocks_loc, ws, sigma_ray, C_thresh, Q_thresh, _point_mode, _calib)
             blocks = m3dist.all_gather_rows(blocks_loc, e_all, group, sizes).contiguous()
             _ffi.call("m3_gn_rays_step", _ffi.ptr(twc), _ffi.ptr(blocks), _ffi.ptr(ii_all), _ffi.ptr(jj_all),
                       _ffi.ptr(local), _ffi.ptr(hbuf), _ffi.ptr(info), k, e_all, num_free, float(delta_thresh), st)

@@ -148,17 +148,9 @@ def test_gauss_newton_calib_golden(golden_dir):
     t = z["Twc"][:, :3].astype(np.float64); q = z["Twc"][:, 3:7].astype(np.float64); s = z["Twc"][:, 7].astype(np.float64)
     calib = dict(fx=500.0, fy=500.0, cx=320.0, cy=240.0, width=640, height=480, border=0, z_eps=0.0, sigma_pixel=1.0,
                  sigma_depth=0.1)
-    import ctypes  # noqa: F401
-    from mast3r_slam import _ffi
-    tt = kernels._prep_gn(z["Twc"], z["Xs"], z["Cs"], z["ii"], z["jj"], z["idx"], z["valid"], z["Q"])
-    e, p, k = tt["E"], tt["P"], tt["K"]
-    bl = torch.empty((e, 36), dtype=torch.float64, device=tt["Twc"].device)
-    ws = torch.empty(e * _ffi.lib().m3_gn_rays_chunks(p) * 36, dtype=torch.float64, device=tt["Twc"].device)
-    _ffi.call("m3_gn_rays_blocks", _ffi.ptr(tt["Twc"]), _ffi.ptr(tt["Xs"]), _ffi.ptr(tt["Cs"]), _ffi.ptr(tt["ii"]),
-              _ffi.ptr(tt["jj"]), _ffi.ptr(tt["idx"]), _ffi.ptr(tt["valid"]), _ffi.ptr(tt["Q"]), _ffi.ptr(bl), _ffi.ptr(ws),
-              k, p, e, 1.0, 0.0, 1.5, 2,
-              kernels._calib_ptr((500, 500, 320, 240, 640, 480, 0, 0.0, 1.0, 0.1)), _ffi.stream_ptr())
-    bl = bl.cpu().numpy()
+    bl = kernels.gn_rays_blocks(z["Twc"], z["Xs"], z["Cs"], z["ii"], z["jj"], z["idx"], z["valid"], z["Q"], 1.0, 0.0, 1.5,
+                                point_mode=2, calib=(500, 500, 320, 240, 640, 480, 0, 0.0, 1.0, 0.1))
+    e = len(z["ii"])
     iu = np.triu_indices(7)
     for ei in range(e):
         Hjj, gj, n = og.edge_blocks(t, q, s, z["Xs"], z["Cs"], int(z["ii"][ei]), int(z["jj"][ei]), z["idx"][ei],
@@ -345,3 +337,165 @@ def test_large_graph_solve_stays_on_the_device(dev):
     out2, info2 = kernels.gauss_newton_rays(*args, max_iter=5, delta_thresh=1e6, return_info=True)
     assert info2["stopped"] and not info2["failed"] and info2["iters"] == 0
     assert np.array_equal(out2.cpu().numpy(), noisy)
+
+
+# ---- every residual mode through every load path of k_gn_blocks --------------------------------------------------
+# Two scenes x three layouts: P = 4100 aligned (the four-point group loop: 3 chunks, 1025 groups over 768 lanes, so some
+# lanes prefetch a second group and some do not), P = 4098 (the one-point loop) and P = 4100 with the streamed arrays
+# 4 bytes (valid: 1 byte) into their allocations (the 16-byte predicate sends it to the one-point loop).  A tenth of
+# the match indices are given in the negative form idx - P that the kernel wraps.
+_PATH_CALIB = (500, 500, 320, 240, 640, 480, 8, 0.5, 1.0, 0.1)
+_PATH_CASES = [("random", 0), ("random", 1), ("chain", 0), ("chain", 2)]
+_PATH_LAYOUTS = [("aligned", 4100), ("odd", 4098), ("offset", 4100)]
+# The library before the shared streaming loop existed stays inside the project's bounds on every case but one: the
+# "points" weight 1 / (|Xi| + 1e-6) on the 4098-point random scene, where max|dH| / max|H| measured 6.103e-5 (one point
+# close to the origin carries most of the sum).  That case is held to twice that figure.
+_PATH_TOL = {("random", 1, "odd"): 2 * 6.103e-5}
+_path_cache = {}
+
+
+def _path_scene(scene, P):
+    key = ("scene", scene, P)
+    if key not in _path_cache:
+        if scene == "random":
+            g = synthetic.gn_graph(5, P, 6, seed=11)
+        else:
+            ident = np.zeros((4, 8), dtype=np.float32)
+            ident[:, 6] = 1.0; ident[:, 7] = 1.0; ident[:, 0] = 0.1 * np.arange(4)
+            g = synthetic.gn_graph(4, P, 0, seed=11, chain=True, pose_noise=0.01, poses=ident)
+            assert len(g[3]) == 12
+        Twc, Xs, Cs, ii, jj, idx, valid, Q = g
+        neg = np.random.default_rng(3).uniform(size=idx.shape) < 0.1
+        idx = np.where(neg, idx - P, idx).astype(np.int32)
+        assert (idx < 0).any()
+        _path_cache[key] = (Twc, Xs, Cs, ii, jj, idx, valid, Q)
+    return _path_cache[key]
+
+
+def _path_params(mode):
+    """(sigma_ray, C_thresh, Q_thresh, oracle calib, device calib)"""
+    if mode != 2:
+        return 0.01, 2.0, 1.5, None, None
+    c = _PATH_CALIB
+    return 1.0, 2.0, 1.5, dict(fx=c[0], fy=c[1], cx=c[2], cy=c[3], width=c[4], height=c[5], border=c[6], z_eps=c[7],
+                               sigma_pixel=c[8], sigma_depth=c[9]), c
+
+
+def _path_oracle(scene, P, mode):
+    key = ("oracle", scene, P, mode)
+    if key not in _path_cache:
+        Twc, Xs, Cs, ii, jj, idx, valid, Q = _path_scene(scene, P)
+        sig, ct, qt, ocal, _ = _path_params(mode)
+        t = Twc[:, :3].astype(np.float64); q = Twc[:, 3:7].astype(np.float64); s = Twc[:, 7].astype(np.float64)
+        _path_cache[key] = [og.edge_blocks(t, q, s, Xs, Cs, int(ii[e]), int(jj[e]), idx[e], valid[e], Q[e], sig, ct, qt,
+                                           mode, ocal) for e in range(len(ii))]
+    return _path_cache[key]
+
+
+def _shifted(a, dev):
+    """Device copy of `a` that starts one element into its allocation."""
+    a = torch.from_numpy(np.ascontiguousarray(a))
+    buf = torch.empty(a.numel() + 1, dtype=a.dtype, device=dev)
+    view = buf[1:].view(a.shape)
+    view.copy_(a)
+    return view
+
+
+def _path_blocks(scene, mode, layout, P, dev):
+    key = ("device", scene, mode, layout)
+    if key not in _path_cache:
+        Twc, Xs, Cs, ii, jj, idx, valid, Q = _path_scene(scene, P)
+        sig, ct, qt, _, dcal = _path_params(mode)
+        if layout == "offset":
+            args = [torch.from_numpy(Twc).to(dev), _shifted(Xs, dev), _shifted(Cs, dev), torch.from_numpy(ii).to(dev),
+                    torch.from_numpy(jj).to(dev), _shifted(idx, dev), _shifted(valid.astype(np.uint8), dev), _shifted(Q, dev)]
+            tt = kernels._prep_gn(*args)                    # the tensors that reach the call
+            assert all(tt[n].data_ptr() % 16 == 4 for n in ("Xs", "Cs", "Q", "idx")) and tt["valid"].data_ptr() % 4 == 1
+            bl = kernels.gn_rays_blocks(*args, sig, ct, qt, point_mode=mode, calib=dcal).cpu().numpy()
+        else:
+            bl = kernels.gn_rays_blocks(Twc, Xs, Cs, ii, jj, idx, valid, Q, sig, ct, qt, point_mode=mode, calib=dcal)
+        _path_cache[key] = bl
+    return _path_cache[key]
+
+
+@pytest.mark.parametrize("layout,P", _PATH_LAYOUTS)
+@pytest.mark.parametrize("scene,mode", _PATH_CASES)
+def test_edge_blocks_every_mode_every_load_path(dev, scene, mode, layout, P):
+    """Bounds are the project's own for the same comparison: 3e-5 of max|H| / max|g| for the 3-D residuals
+    (test_edge_blocks_match_oracle), 1e-4 for the calibrated one (test_gauss_newton_calib_golden)."""
+    bl = _path_blocks(scene, mode, layout, P, dev)
+    ref = _path_oracle(scene, P, mode)
+    tol = _PATH_TOL.get((scene, mode, layout), 1e-4 if mode == 2 else 3e-5)
+    iu = np.triu_indices(7)
+    rh = max(np.abs(bl[e, :28] - Hjj[iu]).max() / np.abs(Hjj).max() for e, (Hjj, gj, n) in enumerate(ref))
+    rg = max(np.abs(bl[e, 28:35] - gj).max() / np.abs(gj).max() for e, (Hjj, gj, n) in enumerate(ref))
+    print(f"gn path {scene} mode {mode} {layout}: max H ratio {rh:.3e}, max g ratio {rg:.3e}, "
+          f"counts {min(r[2] for r in ref)}-{max(r[2] for r in ref)}")
+    for e, (Hjj, gj, n) in enumerate(ref):
+        assert n > 1000 and bl[e, 35] == n                                 # every edge populated; integer count: exact
+        assert np.abs(bl[e, :28] - Hjj[iu]).max() <= tol * np.abs(Hjj).max()
+        assert np.abs(bl[e, 28:35] - gj).max() <= tol * np.abs(gj).max()
+    if mode == 2:                                                          # the border and depth gates reject points
+        assert all(r2[2] < r0[2] for r2, r0 in zip(ref, _path_oracle(scene, P, 0)))
+
+
+@pytest.mark.parametrize("layout,P", _PATH_LAYOUTS)
+def test_points_weight_is_applied_on_every_load_path(dev, layout, P):
+    b0, b1 = _path_blocks("random", 0, layout, P, dev), _path_blocks("random", 1, layout, P, dev)
+    assert not np.allclose(b0[:, :28], b1[:, :28]) and np.array_equal(b0[:, 35], b1[:, 35])
+
+
+# ---- both sides of the single-workgroup limit, and the two entry points the package itself never calls -----------
+def _limit_graph(num_kf):
+    return synthetic.gn_graph(num_kf, 150 if num_kf == 10 else 152, 0, seed=5, chain=True, pose_noise=0.01)
+
+
+@pytest.mark.parametrize("num_kf,dim", [(10, 63), (11, 70)])
+def test_solve_on_both_sides_of_the_single_workgroup_limit(dev, num_kf, dim):
+    """dim 63 is the last system k_gn_step factors in place; dim 70 is one block column plus a 6-row remainder."""
+    from mast3r_slam import _ffi
+    args = _limit_graph(num_kf)
+    assert 7 * kernels._local_map(args[3], args[4], num_kf, 1)[2] == dim
+    assert (dim == _ffi.lib().m3_gn_rays_max_dim()) == (num_kf == 10)
+    out, info = kernels.gauss_newton_rays(*args, max_iter=3, return_info=True)
+    ref = og.gauss_newton_rays(*args, max_iter=3)
+    assert not info["failed"] and info["iters"] == 3
+    assert np.array_equal(out[0], args[0][0])                              # pinned keyframe
+    assert np.abs(out - ref).max() < 2e-4, np.abs(out - ref).max()
+
+
+def test_assemble_and_retract_entry_points(dev):
+    """m3_gn_rays_assemble and m3_gn_rays_retract on the dim-70 graph: the assembled system against the oracle's first
+    one, then the oracle's own float64 step retracted on the device against the oracle's one-iteration poses (both
+    retract in float64 from the same dx and round once to float32; |pose entries| < 4, one float32 ulp is 2.4e-7)."""
+    from mast3r_slam import _ffi
+    Twc, Xs, Cs, ii, jj, idx, valid, Q = _limit_graph(11)
+    K, E = Twc.shape[0], len(ii)
+    ref, oinfo = og.gauss_newton_rays(Twc, Xs, Cs, ii, jj, idx, valid, Q, max_iter=1, return_info=True)
+    d = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    blocks = kernels.gn_rays_blocks(*[d(a) for a in (Twc, Xs, Cs, ii, jj, idx, valid, Q)])
+    _, local_h, num_free = kernels._local_map(ii, jj, K, 1)
+    dim = 7 * num_free
+    assert dim == 70
+    local, ii_d, jj_d = d(local_h), d(ii), d(jj)
+    H = torch.full((dim, dim), float("nan"), dtype=torch.float64, device=dev)   # the entry point clears it
+    g = torch.full((dim,), float("nan"), dtype=torch.float64, device=dev)
+    _ffi.call("m3_gn_rays_assemble", _ffi.ptr(blocks), _ffi.ptr(ii_d), _ffi.ptr(jj_d), _ffi.ptr(local), _ffi.ptr(H),
+              _ffi.ptr(g), K, E, num_free, _ffi.stream_ptr())
+    H, g = H.cpu().numpy(), g.cpu().numpy()
+    assert np.array_equal(H, H.T)                                          # symmetric bit for bit
+    H0, g0 = oinfo["first_H"], oinfo["first_g"]
+    rh, rg = np.abs(H + 1e-6 * np.eye(dim) - H0).max() / np.abs(H0).max(), np.abs(g - g0).max() / np.abs(g0).max()
+    print(f"gn assemble dim {dim}: H ratio {rh:.4e}, g ratio {rg:.4e}")
+    # 3e-5 as for the per-edge blocks, except where the library before the shared driver existed measured more: its H
+    # ratio here is 3.1387e-5 (up to six edge blocks, Huber-weighted at sigma 0.003, add into one diagonal block), so H
+    # is held to twice that figure; its g ratio is 5.4e-6
+    assert rh <= 2 * 3.1387e-5
+    assert rg <= 3e-5
+    dx = np.linalg.solve(H0, -g0)
+    twc = d(Twc).clone()
+    _ffi.call("m3_gn_rays_retract", _ffi.ptr(twc), _ffi.ptr(d(dx)), _ffi.ptr(local), K, _ffi.stream_ptr())
+    out = twc.cpu().numpy()
+    assert oinfo["iters"] == 1 and np.abs(ref).max() < 4.0
+    assert np.array_equal(out[0], Twc[0])                                  # pinned keyframe untouched
+    assert np.abs(out - ref).max() <= 1e-6, np.abs(out - ref).max()
