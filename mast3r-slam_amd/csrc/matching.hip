@@ -8,7 +8,11 @@
 // float32/float64 operation is individually rounded in exactly the order the
 // CPU oracle (oracle/matching.py) uses; parity on p / valid / idx is bit-exact.
 //
-// Reference semantics (paths under /root/reference/src/mlx_mast3r_slam):
+// refine_matches has one window search (window_search), one score (seq_dot) and three candidate sources
+// (GlobalVec, GlobalScalar, LdsTile) under two kernels: k_refine<D, TD> (D = 0: length at run time) and the
+// LDS-staged k_refine_lds<24, TD, R>, whose R = 3 form alone scores a window row at a time (its own pipeline).
+//
+// Reference semantics (paths under the reference tree's src/mlx_mast3r_slam):
 //   prep        matching.py:121-175, image.py:9-34
 //   iter_proj   backends/mpsgraph/kernels.py:151-254 (numpy twin)
 //   refine      backends/mpsgraph/kernels.py:496-537 (numpy twin)
@@ -259,9 +263,51 @@ __device__ __forceinline__ void load_desc(const TD *__restrict__ p, float *q) {
     for (int k = 0; k < D / V; ++k) DescIO<TD>::load16(p + k * V, q + k * V);
 }
 
-template <int D, typename TD>
-__device__ __forceinline__ void refine_pass(const TD *__restrict__ img, const float *q, int H, int W,
-                                            int radius, int dil, int cx, int cy, int &bx, int &by) {
+// THE score: q(k) and r(k) yield element k widened to fp32; one product and one sum per element, in element order.
+template <typename Q, typename R>
+__device__ __forceinline__ float seq_dot(int len, Q q, R r) {
+    float score = 0.0f;
+#pragma unroll
+    for (int k = 0; k < len; ++k) {
+        const float prod = q(k) * r(k);
+        score = score + prod;
+    }
+    return score;
+}
+
+// Candidate sources: score(nx, ny, W) = seq_dot of the query with the descriptor of the in-image pixel (nx, ny).  W, the
+// row length of the searched image, comes from window_search's own bounds test: read from a field of the source the
+// compiler no longer knows 0 <= nx < W and forms the row offset with two 64-bit multiplies per window row instead of one.
+template <int D, typename TD> struct GlobalVec {           // compile-time D, 16-byte global loads, query in registers
+    const TD *img; const float *q;
+    __device__ __forceinline__ float score(int nx, int ny, int W) const {
+        float r[D];
+        load_desc<D, TD>(img + ((size_t)ny * W + nx) * D, r);
+        return seq_dot(D, [&](int k) { return q[k]; }, [&](int k) { return r[k]; });
+    }
+};
+template <typename TD> struct GlobalScalar {               // any D >= 1 at run time: query re-read from global (L1-resident)
+    const TD *img, *q; int D;
+    __device__ __forceinline__ float score(int nx, int ny, int W) const {
+        const TD *r = img + ((size_t)ny * W + nx) * D;
+        return seq_dot(D, [&](int k) { return DescIO<TD>::load1(q + k); }, [&](int k) { return DescIO<TD>::load1(r + k); });
+    }
+};
+template <int D> struct LdsTile {                          // the region [x0, x0 + rw) x [y0, ..) staged by k_refine_lds
+    const float4 *tile; const float *q; int x0, y0, rw;
+    __device__ __forceinline__ float score(int nx, int ny, int) const {
+        const float4 *r4 = tile + ((ny - y0) * rw + (nx - x0)) * (D / 4 + 1);
+        float r[D];
+#pragma unroll
+        for (int k = 0; k < D / 4; ++k) { const float4 v = r4[k]; r[4 * k] = v.x; r[4 * k + 1] = v.y; r[4 * k + 2] = v.z; r[4 * k + 3] = v.w; }
+        return seq_dot(D, [&](int k) { return q[k]; }, [&](int k) { return r[k]; });
+    }
+};
+
+// THE window search: candidates (cx + dx * dil, cy + dy * dil) in raster order, the first best one wins.
+template <typename Src>
+__device__ __forceinline__ void window_search(const Src &src, int H, int W, int radius, int dil, int cx, int cy,
+                                              int &bx, int &by) {
     float best = -INFINITY;
     bx = cx; by = cy;
     for (int dy = -radius; dy <= radius; ++dy) {
@@ -270,37 +316,37 @@ __device__ __forceinline__ void refine_pass(const TD *__restrict__ img, const fl
         for (int dx = -radius; dx <= radius; ++dx) {
             const int nx = cx + dx * dil;
             if (nx < 0 || nx >= W) continue;
-            float r[D];
-            load_desc<D, TD>(img + ((size_t)ny * W + nx) * D, r);
-            float score = 0.0f;
-#pragma unroll
-            for (int k = 0; k < D; ++k) score = score + q[k] * r[k];
+            const float score = src.score(nx, ny, W);
             if (score > best) { best = score; bx = nx; by = ny; }
         }
     }
 }
 
+// D > 0: the descriptor length at compile time, GlobalVec.  D == 0: any length Dn >= 1 at run time, GlobalScalar.
+// The unchained pass keeps a branch (and so a dil == 1 copy of the search) of its own: as one loop from
+// `chained ? dil_max : 1` k_refine<64, float> took 3.05 instead of 2.78 ms for 8 maps of 512 x 512
+// (profiles/matching_refactor.md).
 template <int D, typename TD>
 __global__ void __launch_bounds__(kThreads)
 k_refine(const TD *__restrict__ D11, const TD *__restrict__ D21, const int32_t *__restrict__ p_in,
-         int32_t *__restrict__ p_out, int H, int W, int N, int radius, int dil_max, int chained, int tiled) {
+         int32_t *__restrict__ p_out, int H, int W, int N, int radius, int dil_max, int chained, int tiled, int Dn) {
     const int b = blockIdx.y;
     const int n = point_of_thread(blockIdx.x, threadIdx.x, W, tiled);
     if (n >= N) return;
     const size_t pt = (size_t)b * N + n;
-    const TD *img = D11 + (size_t)b * H * W * D;
-    float q[D];
-    load_desc<D, TD>(D21 + pt * D, q);
+    const int len = D > 0 ? D : Dn;
+    const TD *img = D11 + (size_t)b * H * W * len;
+    float q[D > 0 ? D : 1];
+    if constexpr (D > 0) load_desc<D, TD>(D21 + pt * len, q);
     int cx = p_in[pt * 2 + 0], cy = p_in[pt * 2 + 1];
     int bx = cx, by = cy;
-    if (chained) {
-        for (int dil = dil_max; dil >= 1; --dil) {
-            refine_pass<D, TD>(img, q, H, W, radius, dil, cx, cy, bx, by);
-            cx = bx; cy = by;
-        }
-    } else {
-        refine_pass<D, TD>(img, q, H, W, radius, 1, cx, cy, bx, by);
-    }
+    auto pass = [&](int dil) {
+        if constexpr (D > 0) window_search(GlobalVec<D, TD>{img, q}, H, W, radius, dil, cx, cy, bx, by);
+        else window_search(GlobalScalar<TD>{img, D21 + pt * len, len}, H, W, radius, dil, cx, cy, bx, by);
+        cx = bx; cy = by;
+    };
+    if (chained) { for (int dil = dil_max; dil >= 1; --dil) pass(dil); }
+    else pass(1);
     p_out[pt * 2 + 0] = bx;
     p_out[pt * 2 + 1] = by;
 }
@@ -320,12 +366,12 @@ constexpr int kRefineLdsBytes = 64 * 1024;
 // that chain's latency was the kernel's time), no per-candidate bounds branches (out-of-image candidates read a clamped
 // address and are masked at selection), no index multiply per candidate.  Each score is still the same sequential
 // fp32 sum and the selection still walks the candidates in raster order with a strict '>': identical bits.
-// DMA (round 4, fp32 descriptors only - half ones are widened on the way in): the candidate region goes global -> LDS by
+// DMA (R > 0 and fp32 descriptors - half ones are widened on the way in): the candidate region goes global -> LDS by
 // LDS-DMA (global_load_lds, 16 bytes per lane, no register round trip, every piece of the workgroup in flight at once and
 // ONE wait) instead of load -> wait -> ds_write through VGPRs.  The LDS image is unchanged (7 sixteen-byte slots per
 // pixel, the seventh is padding): a wave-instruction fills 64 consecutive slots, slot s = (pixel s / 7, chunk s % 7), the
 // padding slots re-read chunk 5.  Same image, same inner loop: same bits.
-template <int D, typename TD, int R, bool DMA = false>
+template <int D, typename TD, int R>
 __global__ void __launch_bounds__(kThreads, 2)
 k_refine_lds(const TD *__restrict__ D11, const TD *__restrict__ D21, const int32_t *__restrict__ p_in,
              int32_t *__restrict__ p_out, int H, int W, int N, int radius) {
@@ -377,8 +423,8 @@ k_refine_lds(const TD *__restrict__ D11, const TD *__restrict__ D21, const int32
         // variant, which stages half the pieces, was 50-65 us faster for that reason alone).
         const int per_row = rw * CH, total = rh * per_row;
         constexpr int U = 4;                                   // (8 in flight measured the same)
-        if constexpr (DMA) {
-            static_assert(DescIO<TD>::kVec == 4, "LDS-DMA staging copies bytes: fp32 descriptors only");
+        constexpr bool dma = R > 0 && DescIO<TD>::kVec == 4;   // LDS-DMA copies bytes: fp32 descriptors only
+        if constexpr (dma) {
             const int slots = rw * rh * PS4, nslots = (slots + 63) & ~63;      // <= 4096 = the 64 KiB of the tile
             for (int i0 = threadIdx.x; i0 < nslots; i0 += kThreads) {
                 const int sl = i0 < slots ? i0 : slots - 1;
@@ -475,70 +521,22 @@ k_refine_lds(const TD *__restrict__ D11, const TD *__restrict__ D21, const int32
                 }
             }
         } else {
-        for (int dy = -radius; dy <= radius; ++dy) {
-            const int ny = cy + dy;
-            if (ny < 0 || ny >= H) continue;
-            for (int dx = -radius; dx <= radius; ++dx) {
-                const int nx = cx + dx;
-                if (nx < 0 || nx >= W) continue;
-                const float4 *r4 = tile + ((ny - y0) * rw + (nx - x0)) * PS4;
-                float score = 0.0f;
-#pragma unroll
-                for (int k = 0; k < D / 4; ++k) {
-                    const float4 v = r4[k];
-                    score = score + q[4 * k + 0] * v.x;
-                    score = score + q[4 * k + 1] * v.y;
-                    score = score + q[4 * k + 2] * v.z;
-                    score = score + q[4 * k + 3] * v.w;
-                }
-                if (score > best) { best = score; bx = nx; by = ny; }
-            }
-        }
+            window_search(LdsTile<D>{tile, q, x0, y0, rw}, H, W, radius, 1, cx, cy, bx, by);
         }
     } else {
-        refine_pass<D, TD>(img, q, H, W, radius, 1, cx, cy, bx, by);
-    }
-    p_out[pt * 2 + 0] = bx;
-    p_out[pt * 2 + 1] = by;
-}
-
-// generic descriptor length (any D >= 1): query re-read from global (L1-resident)
-template <typename TD>
-__global__ void __launch_bounds__(kThreads)
-k_refine_generic(const TD *__restrict__ D11, const TD *__restrict__ D21,
-                 const int32_t *__restrict__ p_in, int32_t *__restrict__ p_out, int H, int W, int D, int N,
-                 int radius, int dil_max, int chained) {
-    const int b = blockIdx.y;
-    const int n = blockIdx.x * kThreads + threadIdx.x;
-    if (n >= N) return;
-    const size_t pt = (size_t)b * N + n;
-    const TD *img = D11 + (size_t)b * H * W * D;
-    const TD *q = D21 + pt * D;
-    int cx = p_in[pt * 2 + 0], cy = p_in[pt * 2 + 1];
-    int bx = cx, by = cy;
-    const int first = chained ? dil_max : 1;
-    for (int dil = first; dil >= 1; --dil) {
-        float best = -INFINITY;
-        bx = cx; by = cy;
-        for (int dy = -radius; dy <= radius; ++dy) {
-            const int ny = cy + dy * dil;
-            if (ny < 0 || ny >= H) continue;
-            for (int dx = -radius; dx <= radius; ++dx) {
-                const int nx = cx + dx * dil;
-                if (nx < 0 || nx >= W) continue;
-                const TD *r = img + ((size_t)ny * W + nx) * D;
-                float score = 0.0f;
-                for (int k = 0; k < D; ++k) score = score + DescIO<TD>::load1(q + k) * DescIO<TD>::load1(r + k);
-                if (score > best) { best = score; bx = nx; by = ny; }
-            }
-        }
-        cx = bx; cy = by;
+        window_search(GlobalVec<D, TD>{img, q}, H, W, radius, 1, cx, cy, bx, by);
     }
     p_out[pt * 2 + 0] = bx;
     p_out[pt * 2 + 1] = by;
 }
 
 // ---------------------------------------------------------------- epilogue / simple
+// occlusion test: the two 3-D points are closer than thresh
+__device__ __forceinline__ bool near3(const float *a, const float *c, float thresh) {
+    const float d0 = a[0] - c[0], d1 = a[1] - c[1], d2 = a[2] - c[2];
+    return sqrtf((d0 * d0 + d1 * d1) + d2 * d2) < thresh;
+}
+
 __global__ void __launch_bounds__(kThreads)
 k_epilogue(const float *__restrict__ X11, const float *__restrict__ X21, const int32_t *__restrict__ p_i32,
            const float *__restrict__ p_f32, const uint8_t *__restrict__ valid_proj,
@@ -553,10 +551,8 @@ k_epilogue(const float *__restrict__ X11, const float *__restrict__ X21, const i
     else { u = (int)p_f32[pt * 2]; v = (int)p_f32[pt * 2 + 1]; }
     const int xc = min(max(u, 0), W - 1), yc = min(max(v, 0), H - 1);
     const float *a = X11 + ((size_t)b * N + (size_t)yc * W + xc) * 3;
-    const float *c = X21 + pt * 3;
-    const float d0 = a[0] - c[0], d1 = a[1] - c[1], d2 = a[2] - c[2];
-    const float dist = sqrtf((d0 * d0 + d1 * d1) + d2 * d2);
-    valid_out[pt] = (valid_proj[pt] != 0) && (dist < thresh);
+    const bool near = near3(a, X21 + pt * 3, thresh);
+    valid_out[pt] = (valid_proj[pt] != 0) && near;
     idx_out[pt] = (int64_t)u + (int64_t)W * (int64_t)v;
 }
 
@@ -573,15 +569,23 @@ k_match_simple(const float *__restrict__ X11, const float *__restrict__ X21,
     if (id < 0) id += N;                       // numpy/mlx negative indexing
     id = id < 0 ? 0 : (id >= N ? N - 1 : id);  // never fault on bad input
     const float *a = X11 + ((size_t)b * N + (size_t)id) * 3;
-    const float *c = X21 + pt * 3;
-    const float d0 = a[0] - c[0], d1 = a[1] - c[1], d2 = a[2] - c[2];
-    valid_out[pt] = sqrtf((d0 * d0 + d1 * d1) + d2 * d2) < thresh;
+    valid_out[pt] = near3(a, X21 + pt * 3, thresh);
 }
 
 __global__ void __launch_bounds__(kThreads)
 k_trunc(const float *__restrict__ p, int32_t *__restrict__ out, int64_t count) {
     const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
     if (i < count) out[i] = (int32_t)p[i];
+}
+
+// point_of_thread's tiled mapping applies: the points are the pixels of an image that splits into 16x16 tiles
+inline int tiled_points(int N, int H, int W) { return (N == H * W && H % 16 == 0 && W % 16 == 0) ? 1 : 0; }
+
+// the per-map entry points: B maps of H x W pixels, one thread per pixel; false = arguments out of range
+inline bool map_grid(int B, int H, int W, dim3 &grid) {
+    if (!(B > 0 && H > 0 && W > 0 && (int64_t)H * W < (1ll << 31) && B <= 65535)) return false;
+    grid = dim3(m3_cdiv((int64_t)H * W, kThreads), B);
+    return true;
 }
 
 }  // namespace
@@ -592,8 +596,8 @@ extern "C" {
 int m3_prep_iter_proj(const float *X11, const float *X21, const int64_t *idx_init, float *rwg,
                       float *tgt, float *p_init, int B, int H, int W, void *stream) {
     M3_REQUIRE(X11 && X21 && rwg && tgt && p_init);
-    M3_REQUIRE(B > 0 && H > 0 && W > 0 && (int64_t)H * W < (1ll << 31) && B <= 65535);
-    dim3 grid(m3_cdiv((int64_t)H * W, kThreads), B);
+    dim3 grid;
+    M3_REQUIRE(map_grid(B, H, W, grid));
     hipLaunchKernelGGL(k_prep, grid, dim3(kThreads), 0, (hipStream_t)stream, X11, X21, idx_init, rwg, tgt,
                        p_init, H, W);
     M3_CHECK_LAUNCH("m3_prep_iter_proj");
@@ -616,7 +620,7 @@ int m3_iter_proj(const float *rwg, const float *tgt, const float *p_init, float 
     uint32_t *stepmax = ws, *limit = ws + (size_t)B * max_iter * nwav, *red = limit + B;
     const float xhi = (float)((double)W - 1.001), yhi = (float)((double)H - 1.001);
     dim3 grid(nblk, B);
-    const int tiled = (N == H * W && H % 16 == 0 && W % 16 == 0) ? 1 : 0;
+    const int tiled = tiled_points(N, H, W);
     hipLaunchKernelGGL(k_iter_proj<true>, grid, dim3(kThreads), 0, st, rwg, tgt, p_init, p_out, valid_out,
                        stepmax, (const uint32_t *)limit, H, W, N, max_iter, lambda_init, xhi, yhi, tiled);
     M3_CHECK_LAUNCH("m3_iter_proj/pass1");
@@ -646,25 +650,18 @@ int refine_launch(const TD *D11, const TD *D21, const int32_t *p_in, int32_t *p_
     dim3 grid(m3_cdiv(N, kThreads), B), blk(kThreads);
     // vector path: 16-byte loads need aligned bases and a pixel stride that is a multiple of 16 bytes
     const bool aligned = (((uintptr_t)D11 | (uintptr_t)D21) & 15) == 0;
-    const int tiled = (N == H * W && H % 16 == 0 && W % 16 == 0) ? 1 : 0;
-#define M3_REFINE(DD) hipLaunchKernelGGL((k_refine<DD, TD>), grid, blk, 0, st, D11, D21, p_in, p_out, H, W, N, radius, dmax, chained, tiled)
+    const int tiled = tiled_points(N, H, W);
+#define M3_REFINE(DD) hipLaunchKernelGGL((k_refine<DD, TD>), grid, blk, 0, st, D11, D21, p_in, p_out, H, W, N, radius, dmax, chained, tiled, D)
+#define M3_REFINE_LDS(RR) hipLaunchKernelGGL((k_refine_lds<24, TD, RR>), grid, blk, kRefineLdsBytes, st, D11, D21, p_in, p_out, H, W, N, radius)
     const bool single_pass = !chained || dmax == 1;
-    if (aligned && D == 24 && tiled && single_pass && radius <= 4) {
-        static const bool dma = [] { const char *e = getenv("M3_REFINE_DMA"); return !(e && atoi(e) == 0); }();
-        if constexpr (DescIO<TD>::kVec == 4) {
-            if (dma && radius == 3) {
-                hipLaunchKernelGGL((k_refine_lds<24, TD, 3, true>), grid, blk, kRefineLdsBytes, st, D11, D21, p_in, p_out, H, W, N, radius);
-                M3_CHECK_LAUNCH("m3_refine_matches");
-                return M3_OK;
-            }
-        }
-        if (radius == 3) hipLaunchKernelGGL((k_refine_lds<24, TD, 3>), grid, blk, kRefineLdsBytes, st, D11, D21, p_in, p_out, H, W, N, radius);
-        else hipLaunchKernelGGL((k_refine_lds<24, TD, 0>), grid, blk, kRefineLdsBytes, st, D11, D21, p_in, p_out, H, W, N, radius);
-    } else if (aligned && D == 24) M3_REFINE(24);
+    if (aligned && D == 24 && tiled && single_pass && radius == 3) M3_REFINE_LDS(3);
+    else if (aligned && D == 24 && tiled && single_pass && radius <= 4) M3_REFINE_LDS(0);
+    else if (aligned && D == 24) M3_REFINE(24);
     else if (aligned && D == 16) M3_REFINE(16);
     else if (aligned && D == 32) M3_REFINE(32);
     else if (aligned && D == 64) M3_REFINE(64);
-    else hipLaunchKernelGGL((k_refine_generic<TD>), grid, blk, 0, st, D11, D21, p_in, p_out, H, W, D, N, radius, dmax, chained);
+    else M3_REFINE(0);
+#undef M3_REFINE_LDS
 #undef M3_REFINE
     M3_CHECK_LAUNCH("m3_refine_matches");
     return M3_OK;
@@ -687,8 +684,8 @@ int m3_match_epilogue(const float *X11, const float *X21, const int32_t *p_i32, 
                       const uint8_t *valid_proj, int64_t *idx_out, uint8_t *valid_out, int B, int H, int W,
                       float dist_thresh, void *stream) {
     M3_REQUIRE(X11 && X21 && (p_i32 || p_f32) && valid_proj && idx_out && valid_out);
-    M3_REQUIRE(B > 0 && H > 0 && W > 0 && (int64_t)H * W < (1ll << 31) && B <= 65535);
-    dim3 grid(m3_cdiv((int64_t)H * W, kThreads), B);
+    dim3 grid;
+    M3_REQUIRE(map_grid(B, H, W, grid));
     hipLaunchKernelGGL(k_epilogue, grid, dim3(kThreads), 0, (hipStream_t)stream, X11, X21, p_i32, p_f32,
                        valid_proj, idx_out, valid_out, H, W, dist_thresh);
     M3_CHECK_LAUNCH("m3_match_epilogue");
@@ -698,8 +695,8 @@ int m3_match_epilogue(const float *X11, const float *X21, const int32_t *p_i32, 
 int m3_match_simple(const float *X11, const float *X21, const int64_t *idx_init, int64_t *idx_out,
                     uint8_t *valid_out, int B, int H, int W, float dist_thresh, void *stream) {
     M3_REQUIRE(X11 && X21 && idx_out && valid_out);
-    M3_REQUIRE(B > 0 && H > 0 && W > 0 && (int64_t)H * W < (1ll << 31) && B <= 65535);
-    dim3 grid(m3_cdiv((int64_t)H * W, kThreads), B);
+    dim3 grid;
+    M3_REQUIRE(map_grid(B, H, W, grid));
     hipLaunchKernelGGL(k_match_simple, grid, dim3(kThreads), 0, (hipStream_t)stream, X11, X21, idx_init,
                        idx_out, valid_out, H * W, dist_thresh);
     M3_CHECK_LAUNCH("m3_match_simple");

@@ -59,17 +59,20 @@ def prep_for_iter_proj(X11, X21, idx_1_to_2_init=None):
     return rays, tgt, p0
 
 
+def _match_simple_call(X11, X21, idx, b, h, w):
+    """m3_match_simple on checked inputs -> (idx [B,N] int64, near [B,N] bool: |X11[idx[n]] - X21[n]| < dist_thresh)."""
+    out = torch.empty((b, h * w), dtype=torch.int64, device=X11.device)
+    near = torch.empty((b, h * w), dtype=torch.uint8, device=X11.device)
+    _ffi.call("m3_match_simple", _ffi.ptr(X11), _ffi.ptr(X21), _ffi.ptr(idx), _ffi.ptr(out), _ffi.ptr(near),
+              b, h, w, float(get_config()["matching"]["dist_thresh"]), _ffi.stream_ptr())
+    return out, near.bool()
+
+
 def match_simple(X11, X21, D11=None, D21=None, idx_1_to_2_init=None):
     """matching.py:41-90 -> (idx [B,N] int64, valid [B,N,1] bool)."""
-    cfg = get_config()["matching"]
     X11, X21, b, h, w = _check_maps(X11, X21)
-    n = h * w
-    idx = _check_idx(idx_1_to_2_init, b, n)
-    out = torch.empty((b, n), dtype=torch.int64, device=X11.device)
-    valid = torch.empty((b, n), dtype=torch.uint8, device=X11.device)
-    _ffi.call("m3_match_simple", _ffi.ptr(X11), _ffi.ptr(X21), _ffi.ptr(idx), _ffi.ptr(out), _ffi.ptr(valid),
-              b, h, w, float(cfg["dist_thresh"]), _ffi.stream_ptr())
-    return out, valid.bool()[:, :, None]
+    out, near = _match_simple_call(X11, X21, _check_idx(idx_1_to_2_init, b, h * w), b, h, w)
+    return out, near[:, :, None]
 
 
 def match_iterative_proj(X11, X21, D11, D21, idx_1_to_2_init=None, *, stop_scope: str = "batch"):
@@ -274,11 +277,8 @@ def match_fast_nn(X11, X21, D11, D21, idx_1_to_2_init=None):
         raise ValueError(f"D11 / D21 must hold {b}x{h}x{w}x{d} values, got {tuple(D11.shape)} / {tuple(D21.shape)}")
     m = fast_reciprocal_nn_maps(D11.reshape(b, h, w, d), D21.reshape(b, h, w, d), subsample=int(cfg.get("fast_nn_subsample", 8)),
                                 max_iter=int(cfg.get("fast_nn_rounds", 3)), tracker_maps=True)
-    idx = torch.empty((b, n), dtype=torch.int64, device=X11.device)
-    near = torch.empty((b, n), dtype=torch.uint8, device=X11.device)
-    _ffi.call("m3_match_simple", _ffi.ptr(X11), _ffi.ptr(X21), _ffi.ptr(m["idx"]), _ffi.ptr(idx), _ffi.ptr(near),
-              b, h, w, float(cfg["dist_thresh"]), _ffi.stream_ptr())
-    return idx, (m["valid"][:, :, 0] & near.bool())[:, :, None]
+    idx, near = _match_simple_call(X11, X21, m["idx"], b, h, w)
+    return idx, (m["valid"][:, :, 0] & near)[:, :, None]
 
 
 def fast_reciprocal_nn_device(D1: torch.Tensor, D2: torch.Tensor, subsample: int = 8, max_iter: int = 10):

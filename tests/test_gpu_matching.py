@@ -261,3 +261,121 @@ def test_fp16_features_dense_match_lds_path_and_agreement(dev):
         assert val.mean() > 0.9 and np.median(err[val]) < 1.0 and (err[val] < 2.5).mean() > 0.99
     finally:
         config.reset_config()
+
+
+# ----------------------------------------------------------------- every path of refine_matches on a tileable shape
+_TB, _TH, _TW = 2, 32, 48                                     # twelve 16 x 16 tiles
+_TILE_KINDS = ["shift", "jitter", "scatter", "out", "shift", "scatter"]
+_TILED_INPUTS: dict = {}
+_TILED_ORACLE: dict = {}
+
+
+def _tiled_inputs(d=24):
+    """D11 [B,H,W,d], D21 [B,H*W,d] (normal) and p1 [B,H*W,2] built tile by tile: 'shift' = the pixel grid plus one integer
+    offset per tile, 'jitter' = that plus a per-pixel offset in {-1, 0, 1}, 'scatter' = uniform over the image and 4
+    pixels around it, 'out' = every candidate left of the image.  Built once per d; callers do not modify it."""
+    if d not in _TILED_INPUTS:
+        rng = np.random.default_rng(7)
+        b, h, w = _TB, _TH, _TW
+        D11 = rng.normal(size=(b, h, w, d)).astype(np.float32)
+        D21 = rng.normal(size=(b, h * w, d)).astype(np.float32)
+        vv, uu = np.meshgrid(np.arange(16), np.arange(16), indexing="ij")
+        p1 = np.zeros((b, h, w, 2), dtype=np.int32)
+        for bi in range(b):
+            for ty in range(h // 16):
+                for tx in range(w // 16):
+                    kind = _TILE_KINDS[(ty * 3 + tx + bi) % 6]
+                    x, y = tx * 16 + uu, ty * 16 + vv
+                    if kind in ("shift", "jitter"):
+                        off = rng.integers(-5, 6, size=2)
+                        x, y = x + off[0], y + off[1]
+                        if kind == "jitter":
+                            x, y = x + rng.integers(-1, 2, size=(16, 16)), y + rng.integers(-1, 2, size=(16, 16))
+                    elif kind == "scatter":
+                        x, y = rng.integers(-4, w + 4, size=(16, 16)), rng.integers(-4, h + 4, size=(16, 16))
+                    else:
+                        x = x - w - 10
+                    p1[bi, ty * 16:ty * 16 + 16, tx * 16:tx * 16 + 16] = np.stack([x, y], -1)
+        _TILED_INPUTS[d] = (D11, D21, p1.reshape(b, h * w, 2))
+    return _TILED_INPUTS[d]
+
+
+def _staged_tiles(p1, radius, d=24):
+    """The staging rule of the tiled LDS kernel restated from the inputs: a tile's region is the min / max of its p1,
+    widened by the radius and clamped to the image; it is staged when both sides are positive and it holds at most
+    65536 // ((d // 4 + 1) * 16) pixels.  Returns (staged, fallback) tile counts."""
+    p = p1.reshape(_TB, _TH // 16, 16, _TW // 16, 16, 2)
+    lo, hi = p.min(axis=(2, 4)).astype(np.int64), p.max(axis=(2, 4)).astype(np.int64)
+    x0, x1 = np.maximum(lo[..., 0] - radius, 0), np.minimum(hi[..., 0] + radius, _TW - 1)
+    y0, y1 = np.maximum(lo[..., 1] - radius, 0), np.minimum(hi[..., 1] + radius, _TH - 1)
+    rw, rh = x1 - x0 + 1, y1 - y0 + 1
+    staged = (rw > 0) & (rh > 0) & (rw * rh <= 65536 // ((d // 4 + 1) * 16))
+    return int(staged.sum()), int((~staged).sum())
+
+
+def _tiled_oracle(d, half, radius, dmax, chained):
+    """oracle.matching.refine_matches on _tiled_inputs(d) (half: on the half-rounded values widened to float32), once per case."""
+    key = (d, half, radius, dmax, chained)
+    if key not in _TILED_ORACLE:
+        D11, D21, p1 = _tiled_inputs(d)
+        if half:
+            D11, D21 = D11.astype(np.float16).astype(np.float32), D21.astype(np.float16).astype(np.float32)
+        _TILED_ORACLE[key] = om.refine_matches(D11, D21, p1, radius, dmax, chained=chained)
+    return _TILED_ORACLE[key]
+
+
+def _tiled_run(dev, d, half, radius, dmax, chained):
+    D11, D21, p1 = _tiled_inputs(d)
+    dt = np.float16 if half else np.float32
+    return kernels.refine_matches(_t(D11.astype(dt), dev), _t(D21.astype(dt), dev), _t(p1, dev), radius, dmax,
+                                  chained=chained).cpu().numpy()
+
+
+@pytest.mark.parametrize("dmax", [0, 2])
+@pytest.mark.parametrize("half", [False, True], ids=["fp32", "fp16"])
+@pytest.mark.parametrize("radius", [2, 3, 4])
+def test_refine_tiled_lds_staged_and_fallback_tiles_all_radii(dev, radius, half, dmax):
+    """k_refine_lds<24, TD, 3> (radius 3) and <24, TD, 0> (radius 2, 4) on twelve tiles of which some are staged in LDS and
+    some take the global search inside the same kernel (region too large, or empty: the 'out' tiles have rw <= 0)."""
+    staged, fallback = _staged_tiles(_tiled_inputs()[2], radius)
+    assert staged >= 4 and fallback >= 4, (staged, fallback)        # a condition on the INPUT: both branches are taken
+    r = _tiled_run(dev, 24, half, radius, dmax, False)
+    assert np.array_equal(r, _tiled_oracle(24, half, radius, dmax, False))
+
+
+@pytest.mark.parametrize("radius", [3, 2])
+def test_refine_tiled_lds_ties_first_candidate_in_raster_order(dev, radius):
+    """All-ones descriptors: every in-image candidate scores the same, the first one in raster order must win - in the
+    masked selection of the row-at-a-time form (radius 3) and in the shared window search (radius 2)."""
+    D11, D21, p1 = _tiled_inputs()
+    D11c, D21c = np.ones_like(D11), np.ones_like(D21)
+    r = kernels.refine_matches(_t(D11c, dev), _t(D21c, dev), _t(p1, dev), radius, 0).cpu().numpy()
+    assert np.array_equal(r, om.refine_matches(D11c, D21c, p1, radius, 0))
+
+
+@pytest.mark.parametrize("half", [False, True], ids=["fp32", "fp16"])
+def test_refine_d24_chained_under_tiled_thread_mapping(dev, half):
+    """chained=True with dilation 2 is not a single pass: k_refine<24> with the 16 x 16 tile thread mapping."""
+    assert np.array_equal(_tiled_run(dev, 24, half, 3, 2, True), _tiled_oracle(24, half, 3, 2, True))
+
+
+@pytest.mark.parametrize("chained", [False, True])
+def test_refine_runtime_descriptor_length_on_tileable_shape(dev, chained):
+    """D = 20 has no vector instantiation: the run-time-length search, on a shape that allows the tiled mapping."""
+    assert np.array_equal(_tiled_run(dev, 20, False, 3, 2, chained), _tiled_oracle(20, False, 3, 2, chained))
+
+
+def test_refine_misaligned_descriptor_base(dev):
+    """D = 24 descriptors that start 4 bytes into their buffers cannot take 16-byte loads: the run-time-length search
+    must give the oracle's result, and the result of the same call on aligned copies."""
+    D11, D21, p1 = _tiled_inputs()
+    views = []
+    for a in (D11, D21):
+        buf = torch.empty(a.size + 4, dtype=torch.float32, device=dev)
+        v = buf[1:1 + a.size].view(a.shape)
+        v.copy_(_t(a, dev))
+        assert v.is_contiguous() and v.data_ptr() % 16 == 4
+        views.append(v)
+    r = kernels.refine_matches(views[0], views[1], _t(p1, dev), 3, 2).cpu().numpy()
+    assert np.array_equal(r, _tiled_oracle(24, False, 3, 2, False))
+    assert np.array_equal(r, _tiled_run(dev, 24, False, 3, 2, False))
