@@ -537,6 +537,102 @@ int m3_consistency(const float *const *X, const float *const *C, const float *po
                    float z_min, float depth_rtol, int min_views, int max_conflicts, void *ws, int64_t ws_bytes,
                    uint8_t *support, uint8_t *conflict, float *conf, void *stream);
 
+/* ----------------------------------------------------------- volumetric fusion */
+
+/* TSDF fusion of the keyframe map and one surface mesh from it.  Host side:
+ * mast3r_slam/fusion.py.  The map arrives as for m3_consistency (device tables X, C, img, poses [K,8] and Nk [K] in
+ * DEVICE memory, layout M3_MAP_IMG_*, N = H * W in row-major order, the pinhole of that grid).
+ *
+ * Integration rule.
+ * Inputs: the keyframe tables (X float32 [K,N,3] in each keyframe's own camera frame, C float32 [K,N], img, poses
+ * float32 [K,8], N_k), the common grid H x W (N = H * W), a pinhole (fx, fy, cx, cy) of that grid, thr (or none), z_min,
+ * and a volume: origin fp32 [3], voxel size vs > 0, trunc > 0 and dims Dx, Dy, Dz, each in 2 ... 1024 with
+ * Dx * Dy * Dz <= 2^30.
+ *   observation plane   D[j][m] = X_j[m].z when point (j, m) passes the exporter's confidence test (C / N_j > thr: fp32
+ *                       divide, strict, NaN fails; thr none: no test), that z is finite and z > z_min; otherwise NaN.
+ *                       This is exactly step 1 of the consistency rule.
+ *   voxel (iz, iy, ix)  centre p.x = origin.x + ((float)ix + 0.5f) * vs, likewise y and z.  It holds sum = 0.f, n = 0
+ *                       and the colour sums r = g = b = 0, cn = 0 as uint32.
+ *   for j = 0 .. K-1    in ascending order, every keyframe:
+ *                       c = view_point(view_inverse(T_j), p) as in view_dev.h.  Skip unless c.z > z_min (strict, NaN
+ *                       fails).
+ *                       px = floorf((fx * (c.x / c.z) + cx) + 0.5f), py likewise.  Skip unless 0 <= px < W and
+ *                       0 <= py < H, compared as floats before converting to int.
+ *                       d = D[j][py * W + px].  Skip if d is NaN.
+ *                       sdf = (d - c.z) * s_j, s_j the pose's scale in fp32 (camera units to world units).  Skip unless
+ *                       sdf >= -trunc: the voxel is occluded in j.
+ *                       t = fminf(sdf / trunc, 1.f); sum += t; n += 1.  A voxel far in front of the surface counts as
+ *                       free space with t = 1: this carves away floating outliers.
+ *                       If sdf <= trunc: add the colour of pixel (py, px) of keyframe j (the export's colour rule:
+ *                       uint8 passed through, float (uint8)floorf(min(max(v, 0), 1) * 255.0f)) to r, g, b; cn += 1.
+ *   outputs             tsdf float32 [Dz,Dy,Dx] = sum / (float)n, or 1.f when n == 0; weight int32 [Dz,Dy,Dx] = n;
+ *                       color uint8 [Dz,Dy,Dx,3] = (2 * r + cn) / (2 * cn) in integer division per channel, or 0 when
+ *                       cn == 0; colored uint8 [Dz,Dy,Dx] = (cn > 0), the bit the extraction's colour rule needs.
+ * Every fp32 operation is separately rounded, and the divides are IEEE.
+ * The sdf is projective (along z) with nearest-pixel depth; the pointmap is treated as a depth image of the pinhole (the
+ * consistency filter's approximation, exact when the points lie on the rays of the pinhole); weights are counts, not
+ * confidences.
+ *
+ * Extraction rule (naive surface nets).
+ * Inputs: tsdf, weight, color, colored, origin, vs and min_weight >= 1.
+ *   valid voxel         weight >= min_weight.       inside voxel: tsdf < 0 (strict: a value of 0 is outside).
+ *   cell (z, y, x)      for z < Dz-1, y < Dy-1, x < Dx-1, with the 8 corner voxels (z+dz, y+dy, x+dx).  Active iff all 8
+ *                       corners are valid and are neither all inside nor all outside.
+ *   vertex              one per active cell, in ascending (z, y, x).  Walk the 12 cell edges - the 4 x-edges by
+ *                       (dz,dy) = (0,0),(0,1),(1,0),(1,1); then the 4 y-edges by (dz,dx); then the 4 z-edges by (dy,dx)
+ *                       - and add the crossing point of every edge whose ends differ in "inside" to acc = 0 (per
+ *                       component, in that order).  An edge from corner a to b = a + e_d has tt = Fa / (Fa - Fb); its
+ *                       crossing point is a's 0/1 offsets as floats, with tt along d.  local = acc / (float)count;
+ *                       world.x = origin.x + (((float)x + 0.5f) + local.x) * vs, likewise y and z.  Colour per channel:
+ *                       the rounded integer mean over the corners with colored set, (2 * sum + m) / (2 * m), or 0 when
+ *                       there is none.
+ *   faces               visit every grid edge from voxel (z, y, x) along d, d in the order x, y, z.  It yields faces when
+ *                       its ends differ in "inside" and its four surrounding cells all exist and are active: cells
+ *                       (z-1..z, y-1..y, x) for d = x, (z-1..z, y, x-1..x) for d = y, (z, y-1..y, x-1..x) for d = z.
+ *                       With (u, v, d) right-handed - d=x: (y,z), d=y: (z,x), d=z: (x,y) - the cells at (du,dv) =
+ *                       (-1,-1),(0,-1),(0,0),(-1,0) are q0..q3.  First end inside: (q0,q1,q2),(q0,q2,q3); otherwise
+ *                       (q3,q2,q1),(q3,q1,q0).  Face normals then point to the free-space side.  Faces come in
+ *                       ascending (z, y, x, d, triangle).
+ *   outputs             vertices float32 [V,3], colors uint8 [V,3], faces int32 [F,3] (rows of the vertex arrays).
+ *
+ * m3_tsdf_integrate: m3_tsdf_integrate_launches() = 3 launches are queued on `stream` (inverse poses, observation planes,
+ * one thread per voxel) whatever K >= 1 and the dims are; K = 0 queues the voxel kernel alone, which writes the
+ * unobserved volume (tsdf 1, weight 0, colour 0; the tables and ws may then be NULL).  No allocation, no host
+ * synchronisation, no atomics and no floating-point reduction across threads: the call can be captured into a graph and
+ * the bytes of every output are the same on every call.  colored may be NULL (not written).
+ * ws: m3_tsdf_integrate_ws_bytes(K, N) bytes (64 per keyframe for the inverse poses, then K * N floats of planes;
+ * 0 = K == 0 or unsupported: K * N must stay below 2^31), 16-byte aligned, contents ignored on entry.
+ *
+ * m3_tsdf_extract_count: three launches (the flag byte of every voxel - valid, inside, active cell - and the active
+ * cells per workgroup of 256 consecutive voxels; face-yielding edges per workgroup; an exclusive scan of both).
+ * Afterwards ws int32 [0] = V and [1] = F / 2 (the face-yielding edges): the host reads both in one copy.
+ * m3_tsdf_extract_scatter: two launches (vertices, which also write the cell -> row remap into ws; faces, which read it)
+ * with the SAME volume, min_weight and ws, V and F as read back (V >= 1, F >= 2: the host launches nothing when
+ * F = 0).  m3_tsdf_extract_launches() = 5 whatever the dims and the content are.  colored NULL: every voxel counts as
+ * coloured.  Positions are workgroup offset + rank inside it, never an atomic counter: two calls give identical bytes.
+ * ws: m3_tsdf_extract_ws_bytes(Dx, Dy, Dz) bytes, 16-byte aligned, contents ignored on entry: int32 [4] header, two int32
+ * offset tables of ceil(Dx*Dy*Dz / 256) entries (each padded to 16 bytes), int32 remap per voxel, one flag byte per voxel
+ * (padded to 16).  0 = unsupported: edges are counted in int32, so 3 * Dx * Dy * Dz must stay below 2^31.
+ *
+ * M3_ERR_INVALID_ARG, before any HIP call, for NULL pointers, a dim outside 2 ... 1024 or more than 2^30 voxels, a
+ * non-finite origin, voxel_size or trunc (or one that is not > 0), a negative or NaN z_min, fx / fy not positive and
+ * finite, min_weight < 1, an odd F, a misaligned or short ws, or tsdf / weight / vertices / faces not 4-byte aligned. */
+int64_t m3_tsdf_integrate_ws_bytes(int K, int N);
+int m3_tsdf_integrate_launches(void);
+int m3_tsdf_integrate(const float *const *X, const float *const *C, const void *const *img, const float *poses,
+                      const int32_t *Nk, int K, int H, int W, int use_thresh, float thresh, int layout, float fx, float fy,
+                      float cx, float cy, float z_min, float ox, float oy, float oz, float voxel_size, float trunc, int Dx,
+                      int Dy, int Dz, void *ws, int64_t ws_bytes, float *tsdf, int32_t *weight, uint8_t *color,
+                      uint8_t *colored, void *stream);
+int64_t m3_tsdf_extract_ws_bytes(int Dx, int Dy, int Dz);
+int m3_tsdf_extract_launches(void);
+int m3_tsdf_extract_count(const float *tsdf, const int32_t *weight, int Dx, int Dy, int Dz, int min_weight, void *ws,
+                          int64_t ws_bytes, void *stream);
+int m3_tsdf_extract_scatter(const float *tsdf, const int32_t *weight, const uint8_t *color, const uint8_t *colored, float ox,
+                            float oy, float oz, float voxel_size, int Dx, int Dy, int Dz, int min_weight, void *ws,
+                            int64_t ws_bytes, int64_t V, int64_t F, float *vertices, uint8_t *colors, int32_t *faces,
+                            void *stream);
+
 /* ---------------------------------------------------------- camera intrinsics */
 
 /* Focal length of every keyframe from its own pointmap.  Host side: mast3r_slam/intrinsics.py.

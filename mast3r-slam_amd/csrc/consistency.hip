@@ -13,54 +13,12 @@
 #include "map_points.h"
 #pragma clang fp contract(off)
 #include "view_dev.h"
+#include "cons_planes.h"                        // k_cons_inverse, k_cons_plane: shared with tsdf.hip
 
 namespace {
 
-constexpr int kInvStride = 16;                // floats per keyframe in the inverse-pose table: kViewWords, padded to 64 bytes
-
-inline int64_t inv_bytes(int K) { return (int64_t)K * kInvStride * 4; }
-
 // An empty map is accepted (and nothing is launched for it).
 inline bool shape_ok(int K, int N) { return (K == 0 && N >= 1) || map_shape_ok(K, N); }
-
-// One thread per keyframe: the view_inverse of its pose.
-__global__ void __launch_bounds__(kThreads) k_cons_inverse(const float *__restrict__ poses, int K, float *__restrict__ inv) {
-    const int k = blockIdx.x * kThreads + threadIdx.x;
-    if (k >= K) return;
-    float o[kInvStride];
-    view_inverse(poses + 8 * k, o);
-#pragma unroll
-    for (int i = kViewWords; i < kInvStride; ++i) o[i] = 0.f;
-#pragma unroll
-    for (int i = 0; i < kInvStride; i += 4) *(float4 *)(inv + (size_t)kInvStride * k + i) = float4{o[i], o[i + 1], o[i + 2], o[i + 3]};
-}
-
-// Grid as k_export_count.  D[k][n] = X[k][n].z where the point passes the confidence test and z is finite and > z_min,
-// else NaN.
-__global__ void __launch_bounds__(kThreads) k_cons_plane(const float *const *__restrict__ X, const float *const *__restrict__ C,
-                                                          const int32_t *__restrict__ Nk, int N, int tiles, int use_thresh,
-                                                          float thresh, float z_min, float *__restrict__ D) {
-    const Tile t = tile_of(N, tiles, X, C);
-    if (t.n0 >= N) return;
-    float avg[kPts];
-    const unsigned pass = conf_pass(t, N, (float)Nk[t.k], use_thresh, thresh, avg);
-    float x[3 * kPts];
-    load_points(t.X, t, pass, x);                                                // only z is used
-    float d[kPts];
-#pragma unroll
-    for (int j = 0; j < kPts; ++j) {
-        const float z = x[3 * j + 2];
-        d[j] = (((pass >> j) & 1u) && isfinite(z) && z > z_min) ? z : __builtin_nanf("");
-    }
-    float *Dk = D + (size_t)t.k * N + t.n0;
-    if (t.vec) {
-        *(float4 *)Dk = float4{d[0], d[1], d[2], d[3]};                          // D is 16-byte aligned and N % 4 == 0
-    } else {
-#pragma unroll
-        for (int j = 0; j < kPts; ++j)
-            if (t.n0 + j < N) Dk[j] = d[j];
-    }
-}
 
 // Grid as k_export_count: a workgroup belongs to one keyframe, a thread owns 4 consecutive points.  The neighbour loop is
 // outermost; the neighbour index and its inverse pose depend on the workgroup and the slot alone, so they are read

@@ -19,7 +19,8 @@ the map, mesh and trajectory writers of mast3r_slam/export.py (collect_map, coll
 save_trajectory; slam.py:320-415) and
 the headless map renderer of mast3r_slam/render.py (render_map, ViewRecorder and its camera helpers) and the focal
 estimate of mast3r_slam/intrinsics.py (estimate_focal, estimate_intrinsics) and the multi-view consistency filter of
-mast3r_slam/consistency.py (multiview_support, consistent_keyframes).
+mast3r_slam/consistency.py (multiview_support, consistent_keyframes) and the volumetric fusion of
+mast3r_slam/fusion.py (fuse_tsdf, extract_surface).
 """
 from __future__ import annotations
 
@@ -38,6 +39,7 @@ from .preprocess import adjust_intrinsics, resample_tables, resize_geometry, res
 from .render import ViewRecorder, behind, default_intrinsics, depth_to_rgb, look_at, render_map, save_image
 from .consistency import ConsistentFrame, consistent_keyframes, multiview_support, nearest_neighbours
 from .intrinsics import IntrinsicsEstimate, estimate_focal, estimate_intrinsics, intrinsics_from_rows
+from .fusion import TSDFVolume, extract_surface, fuse_tsdf
 
 __all__ = [
     "load_mast3r", "resize_img", "frame_to_numpy", "downsample", "mast3r_inference_mono", "mast3r_asymmetric_inference",
@@ -48,6 +50,7 @@ __all__ = [
     "render_map", "default_intrinsics", "look_at", "behind", "depth_to_rgb", "save_image", "ViewRecorder",
     "estimate_focal", "estimate_intrinsics", "intrinsics_from_rows", "IntrinsicsEstimate",
     "multiview_support", "consistent_keyframes", "nearest_neighbours", "ConsistentFrame",
+    "fuse_tsdf", "extract_surface", "TSDFVolume",
 ]
 
 

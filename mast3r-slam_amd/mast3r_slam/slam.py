@@ -20,7 +20,7 @@ from typing import Callable, Iterable, Optional
 
 import torch
 
-from . import export, intrinsics, render
+from . import export, fusion, intrinsics, render
 from .config import get_config
 from .consistency import consistent_keyframes
 from .dataloader import Dataset, load_dataset
@@ -248,6 +248,39 @@ class SLAM:
         """The keyframes' triangle mesh as a PLY with a face element; returns (vertices, faces) written.  For a mesh of
         the consistency-filtered map write export.save_ply_mesh(path, *self.mesh(..., consistency=True))."""
         vertices, colors, faces = self.mesh(c_conf_threshold, stride, edge_ratio)
+        return export.save_ply_mesh(path, vertices, colors, faces, binary=binary)
+
+    def fused_mesh(self, voxel_size: Optional[float] = None, trunc: Optional[float] = None,
+                   c_conf_threshold: Optional[float] = 1.5, min_weight: int = 1, consistency=None, bounds=None):
+        """One connected surface of the whole map: fusion.fuse_tsdf over the keyframes and their current poses, then
+        fusion.extract_surface: (vertices [V,3] float32, colours [V,3] uint8, faces [F,3] int32).  Opt-in: nothing in the
+        loop uses it.  The pinhole is the keyframes' intrinsics when there are any, else "estimate".  bounds None: the box of
+        the exported points (fusion.map_bounds); voxel_size None: the longest side of the bounds over 256; trunc None:
+        4 * voxel_size.  These defaults and min_weight = 1 are this project's choice, untuned on real data.  consistency
+        as for reconstruction.  No keyframes: an empty mesh."""
+        if consistency is None or consistency is False:
+            frames, thr = self.keyframes, c_conf_threshold
+        else:
+            frames, thr = self._consistent(consistency, c_conf_threshold)
+        if not export._with_pointmap(frames):
+            return export._empty_mesh("cuda" if torch.cuda.is_available() else "cpu", False)
+        if bounds is None:
+            bounds = fusion.map_bounds(frames, thr)
+        if voxel_size is None:
+            side = max(float(h) - float(l) for l, h in zip(*bounds))
+            if not side > 0.0:
+                raise ValueError("the bounds have no extent: pass voxel_size")
+            voxel_size = side / 256.0
+        K = self.keyframes.get_intrinsics()
+        volume = fusion.fuse_tsdf(frames, "estimate" if K is None else K, voxel_size, bounds=bounds, trunc=trunc,
+                                  c_conf_threshold=thr)
+        return fusion.extract_surface(volume, min_weight=min_weight)
+
+    def save_fused_mesh(self, path, voxel_size: Optional[float] = None, trunc: Optional[float] = None,
+                        c_conf_threshold: Optional[float] = 1.5, min_weight: int = 1, consistency=None, bounds=None,
+                        binary: bool = True):
+        """fused_mesh as a PLY with a face element, written by export.save_ply_mesh; returns (vertices, faces) written."""
+        vertices, colors, faces = self.fused_mesh(voxel_size, trunc, c_conf_threshold, min_weight, consistency, bounds)
         return export.save_ply_mesh(path, vertices, colors, faces, binary=binary)
 
     def save_trajectory(self, path, format: str = "tum", keyframes_only: bool = False) -> int:
