@@ -1,6 +1,6 @@
 // Nearest neighbour in descriptor space (maximum dot product) - the search primitive of "fast reciprocal NN" matching
 // (MASt3R, Leroy et al. 2024, section 3.3; mast3r/fast_nn.py of the public implementation).  Three forms, same result:
-// an fp32 FMA-chain kernel (k_nn_search), the brute-force search on the matrix cores (k_nn_mfma) and, since round 4, an
+// an fp32 FMA-chain kernel (k_nn_search), the brute-force search on the matrix cores (k_nn_mfma) and an
 // exact search that bounds most of the database away first (k_frnn_blockstats / _seed_lb / _survivors / _eval, further
 // down) with k_nn_mfma as its device-side fallback.  BASELINE.json's north_star names this matcher; the reference tree has no implementation
 // of it, so the semantics below are this repo's and are pinned by its own oracle:
@@ -15,6 +15,8 @@
 // per-split winners are merged with ONE 64-bit atomicMax per query on a key = (order-preserving score bits,
 // inverted index), which also implements the lowest-index tie-break deterministically.
 //
+// Device side, each written once: the key codec (make_key / key_index / key_score), Queries (which packed row is query q
+// of pair b), score_tile (the MFMA sequence that defines a score), merge_lane_groups, block_origin / pixel_or_origin.
 // Host side (below the kernels): PackedMap / BlockStats / PruneWs define each buffer layout once - pointers and size -,
 // plan_search the database split, launch_nn_mfma / launch_pack the two template dispatches, and frnn_round is the one
 // round body behind m3_frnn_round, m3_frnn_round_active and m3_frnn_round_pruned.
@@ -25,6 +27,9 @@ namespace {
 
 constexpr int kThreads = 256;
 
+// ---- the 64-bit merge key: (order-preserving score bits) << 32 | (0xffffffff - n) ----
+// atomicMax on it keeps the larger score and, among equal scores, the lower index.  Key 0 means "nothing found": every
+// real key is larger (the score bits of -inf are 0x007fffff), and it decodes to index -1, which a reader clamps or ignores.
 __device__ __forceinline__ unsigned ordered_bits(float f) {      // monotone float -> uint map
     const unsigned u = __float_as_uint(f);
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
@@ -32,6 +37,11 @@ __device__ __forceinline__ unsigned ordered_bits(float f) {      // monotone flo
 __device__ __forceinline__ float from_ordered(unsigned k) {
     return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
 }
+__device__ __forceinline__ unsigned long long make_key(float score, int n) {
+    return ((unsigned long long)ordered_bits(score) << 32) | (unsigned long long)(0xffffffffu - (unsigned)n);
+}
+__device__ __forceinline__ int32_t key_index(unsigned long long key) { return (int32_t)(0xffffffffu - (unsigned)(key & 0xffffffffull)); }
+__device__ __forceinline__ float key_score(unsigned long long key) { return from_ordered((unsigned)(key >> 32)); }
 
 constexpr int kQPL = 2;                                       // queries per lane: halves the scalar row traffic per FMA
 
@@ -77,9 +87,7 @@ k_nn_search(const float *__restrict__ Q, const float *__restrict__ DB, unsigned 
 #pragma unroll
         for (int u = 0; u < kQPL; ++u) {
             if (sidx[u] >= S) continue;
-            const unsigned long long key = ((unsigned long long)ordered_bits(best[u]) << 32) |
-                                           (unsigned long long)(0xffffffffu - (unsigned)best_n[u]);
-            atomicMax(keys + (size_t)b * S + sidx[u], key);
+            atomicMax(keys + (size_t)b * S + sidx[u], make_key(best[u], best_n[u]));
         }
     }
 }
@@ -89,9 +97,8 @@ k_nn_unpack(const unsigned long long *__restrict__ keys, int32_t *__restrict__ i
             long long total) {
     const long long i = (long long)blockIdx.x * kThreads + threadIdx.x;
     if (i >= total) return;
-    const unsigned long long k = keys[i];
-    idx[i] = (int32_t)(0xffffffffu - (unsigned)(k & 0xffffffffull));
-    if (score) score[i] = from_ordered((unsigned)(k >> 32));
+    idx[i] = key_index(keys[i]);
+    if (score) score[i] = key_score(keys[i]);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -141,17 +148,64 @@ constexpr int kQPW = kQT * 16;              // queries per wave
 constexpr int kQPB = kQPW * (kThreads / 64);   // queries per workgroup: 512
 constexpr int kRows = 128;                  // database rows per LDS step (two workgroup barriers per step; 64 rows: 1564 us per round, 128: 1509)
 
-// Round 3.  The round-2 loop issued ONE MFMA at a time: its result went to an AGPR quad that the next instructions
-// read back (v_accvgpr_read x 4), so the following MFMA waited out the matrix core's full latency, and the ragged-tail
-// compares ran on every tile: 358 TFLOP/s (K padded to 32) = 0.14 of the peak.  Now (a) the file is built with
-// -amdgpu-mfma-vgpr-form (results land in VGPRs), (b) the 2 x 4 MFMAs of two row tiles x four query tiles are issued
-// back to back into eight accumulators and only then reduced (max over a lane's 8 scores of a query: 3 x v_max3 + v_max,
-// one compare + wave vote per PAIR of tiles), (c) the ragged tail is a separate instantiation of the step (RAGGED) taken
-// for the last step of a split only, (d) queries are gathered BY INDEX from a packed map (qidx), so a descriptor map is
-// packed once per matcher call and serves as database of one search direction and query source of the other.
-template <int PASSES, bool RAGGED>
+// Which packed row is query q of pair b.  A search has S_all seed slots per pair; keys, mlb and qnorm are indexed by the
+// slot.  qidx [P][S_all] (null: row = slot, NQ = S_all) names the packed row a slot currently sits on, so a descriptor map
+// is packed once per matcher call and serves as database of one search direction and query source of the other.  Active-set
+// form (rounds >= 2 of the reciprocal matcher): only the first qcount[b] entries of qlist[b] are queries - the slots that
+// have not converged yet, in the caller's order.  Built on the host (frnn_search / m3_nn_search_mfma), passed by value.
+struct Queries {
+    const unsigned short *hi, *lo;          // packed rows [P][NQ][32]; lo only for fp32 descriptors
+    const int32_t *qidx, *qlist, *qcount;
+    int S_all, NQ;
+    __device__ __forceinline__ int count(int b) const { return qcount ? qcount[b] : S_all; }
+    // position q in the list of pair b (S = count(b)) -> seed slot; positions past the end shadow the last query
+    __device__ __forceinline__ int slot(int b, int q, int S) const {
+        q = q < S ? q : S - 1;
+        return qlist ? qlist[(size_t)b * S_all + q] : q;
+    }
+    __device__ __forceinline__ size_t row(int b, int slot) const {           // seed slot -> packed row, pair offset included
+        int qr = qidx ? qidx[(size_t)b * S_all + slot] : slot;
+        qr = qr < 0 ? 0 : (qr >= NQ ? NQ - 1 : qr);
+        return (size_t)b * NQ + qr;
+    }
+    // MFMA fragment of a packed row: k = 8 g .. 8 g + 7
+    __device__ __forceinline__ f16x8 frag(const unsigned short *plane, size_t row, int g) const {
+        return *reinterpret_cast<const f16x8 *>(plane + row * 32 + g * 8);
+    }
+};
+
+// THE score of 16 database rows (A operand) x 16 queries (B operand): hi.hi, then hi.lo, then lo.hi into one accumulator
+// (LO: fp32 descriptors), hi.hi alone otherwise.  The brute-force search (nn_step) and the block-bound search (k_frnn_eval)
+// both score through it, so their scores are the same bits by construction.
+template <bool LO>
+__device__ __forceinline__ f32x4 score_tile(f16x8 a_hi, f16x8 a_lo, f16x8 q_hi, f16x8 q_lo) {
+    f32x4 c = {0.f, 0.f, 0.f, 0.f};
+    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a_hi, q_hi, c, 0, 0, 0);
+    if (LO) {
+        c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a_hi, q_lo, c, 0, 0, 0);
+        c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a_lo, q_hi, c, 0, 0, 0);
+    }
+    return c;
+}
+
+// the 4 lane groups of a wave hold disjoint row subsets of the same query: keep the larger score, ties -> lower index
+__device__ __forceinline__ void merge_lane_groups(float &best, int &n) {
+#pragma unroll
+    for (int sh = 16; sh <= 32; sh <<= 1) {
+        const float os = __shfl_xor(best, sh, 64);
+        const int on = __shfl_xor(n, sh, 64);
+        if (os > best || (os == best && on < n)) { best = os; n = on; }
+    }
+}
+
+// One LDS step of the brute-force search.  The file is built with -amdgpu-mfma-vgpr-form (results land in VGPRs; through
+// AGPRs every MFMA waited out the matrix core's latency behind 4 v_accvgpr_read); the 2 x 4 score_tiles of two row tiles x
+// four query tiles are issued back to back into eight accumulators and only then reduced (max over a lane's 8 scores of a
+// query: 3 x v_max3 + v_max, one compare + wave vote per PAIR of tiles); the ragged tail is a separate instantiation
+// (RAGGED) taken for the last step of a split only.  One MFMA at a time ran at 358 TFLOP/s = 0.14 of the peak.
+template <bool LO, bool RAGGED>
 __device__ __forceinline__ void nn_step(const unsigned char *__restrict__ hi_s, const unsigned char *__restrict__ lo_s,
-                                        const f16x8 (&qh)[kQT], const f16x8 (&ql)[PASSES == 3 ? kQT : 1],
+                                        const f16x8 (&qh)[kQT], const f16x8 (&ql)[LO ? kQT : 1],
                                         float (&best)[kQT], int (&bestn)[kQT], int nbase, int n1, int col, int g) {
 #pragma unroll
     for (int rp = 0; rp < kRows / 32; ++rp) {                                 // pairs of 16-row tiles
@@ -162,7 +216,7 @@ __device__ __forceinline__ void nn_step(const unsigned char *__restrict__ hi_s, 
             const int off = row * 64 + ((g ^ ((0 - (row >> 2)) & 3)) << 4);
             ah[h] = *reinterpret_cast<const f16x8 *>(hi_s + off);
             al[h] = ah[h];
-            if (PASSES == 3) al[h] = *reinterpret_cast<const f16x8 *>(lo_s + off);
+            if (LO) al[h] = *reinterpret_cast<const f16x8 *>(lo_s + off);
         }
         const int nrow = nbase + rp * 32 + g * 4;                             // first of this lane's 2 x 4 output rows
 #pragma unroll
@@ -171,15 +225,7 @@ __device__ __forceinline__ void nn_step(const unsigned char *__restrict__ hi_s, 
 #pragma unroll
             for (int tt = 0; tt < 4; ++tt)
 #pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    f32x4 c = {0.f, 0.f, 0.f, 0.f};
-                    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[h], qh[t0 + tt], c, 0, 0, 0);
-                    if (PASSES == 3) {
-                        c = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[h], ql[t0 + tt], c, 0, 0, 0);
-                        c = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[h], qh[t0 + tt], c, 0, 0, 0);
-                    }
-                    acc[tt][h] = c;
-                }
+                for (int h = 0; h < 2; ++h) acc[tt][h] = score_tile<LO>(ah[h], al[h], qh[t0 + tt], ql[LO ? t0 + tt : 0]);
 #pragma unroll
             for (int tt = 0; tt < 4; ++tt) {
                 const int t = t0 + tt;
@@ -213,31 +259,24 @@ __device__ __forceinline__ void nn_step(const unsigned char *__restrict__ hi_s, 
     }
 }
 
-// Qhi / Qlo: packed rows [P][NQ][32]; qidx int32 [P][S] selects the query rows (null: query s = row s, NQ = S).
-template <int PASSES>
-__global__ void __launch_bounds__(kThreads, PASSES == 1 ? 4 : 2)       // fp16 descriptors: 4 waves per SIMD (<= 128 registers)
-k_nn_mfma(const unsigned short *__restrict__ Qhi, const unsigned short *__restrict__ Qlo, const int32_t *__restrict__ qidx,
-          const unsigned short *__restrict__ Dhi, const unsigned short *__restrict__ Dlo,
-          unsigned long long *__restrict__ keys, int S_all, int NQ, int N, int per_split,
-          const int32_t *__restrict__ qlist, const int32_t *__restrict__ qcount,
-          const int32_t *__restrict__ gate_total, int gate_nb) {
+template <bool LO>
+__global__ void __launch_bounds__(kThreads, LO ? 2 : 4)                 // fp16 descriptors: 4 waves per SIMD (<= 128 registers)
+k_nn_mfma(const Queries Q, const unsigned short *__restrict__ Dhi, const unsigned short *__restrict__ Dlo,
+          unsigned long long *__restrict__ keys, int N, int per_split, const int32_t *__restrict__ gate_total, int gate_nb) {
     __shared__ __attribute__((aligned(16))) unsigned char lds[2][2][kRows * 64];   // [stage][hi|lo][64 rows x 64 B]
     const int b = blockIdx.z, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int S = Q.count(b);
     // fallback of the block-bound search (k_frnn_eval below): runs only when the bounds pruned too little
-    if (gate_total && !prune_overflow(gate_total[b], qcount ? qcount[b] : S_all, gate_nb)) return;
+    if (gate_total && !prune_overflow(gate_total[b], S, gate_nb)) return;
     const int col = lane & 15, g = lane >> 4;
-    const size_t qb = (size_t)b * NQ, db = (size_t)b * N, kb = (size_t)b * S_all;
-    // active-set form (rounds >= 2 of the reciprocal matcher): only the first qcount[b] entries of qlist[b] are queries -
-    // the seed slots that have not converged yet, in ascending order; a workgroup past the end has nothing to do
-    // (workgroup-uniform exit in front of every barrier).  keys / qidx stay indexed by the seed SLOT.
-    const int S = qcount ? qcount[b] : S_all;
+    const size_t db = (size_t)b * N, kb = (size_t)b * Q.S_all;
     int bx = blockIdx.x, by = blockIdx.y;
-    if (qcount) {
-        // The grid was sized for S_all queries (gridDim.x query blocks x gridDim.y database splits = one round of the
-        // chip).  With only nb = ceil(S / 512) query blocks left, the same workgroups are re-dealt as nb query blocks x
-        // (slots / nb) database splits: every CU still works, each on a shorter database range - the round's time shrinks
-        // with the active set instead of staying one full-length workgroup long.  (The per-split winners merge by atomicMax
-        // whatever the number of splits.)
+    if (Q.qcount) {
+        // Active-set form.  The grid was sized for S_all queries (gridDim.x query blocks x gridDim.y database splits = one
+        // round of the chip).  With only nb = ceil(S / 512) query blocks left, the same workgroups are re-dealt as nb query
+        // blocks x (slots / nb) database splits: every CU still works, each on a shorter database range - the round's time
+        // shrinks with the active set instead of staying one full-length workgroup long.  (The per-split winners merge by
+        // atomicMax whatever the number of splits; a workgroup past the end leaves in front of every barrier.)
         if (S <= 0) return;
         const int nb = (S + kQPB - 1) / kQPB, slots = (int)(gridDim.x * gridDim.y);
         const int w = by * (int)gridDim.x + bx, nsplit = slots / nb;
@@ -246,17 +285,13 @@ k_nn_mfma(const unsigned short *__restrict__ Qhi, const unsigned short *__restri
         per_split = (((N + nsplit - 1) / nsplit) + kRows - 1) / kRows * kRows;
     }
     // query fragments (MFMA B operand): lane -> query col, k = 8 g .. 8 g + 7
-    f16x8 qh[kQT], ql[PASSES == 3 ? kQT : 1];
+    f16x8 qh[kQT], ql[LO ? kQT : 1];
     const int q0 = bx * kQPB + wave * kQPW;
 #pragma unroll
     for (int t = 0; t < kQT; ++t) {
-        int q = q0 + t * 16 + col;
-        q = q < S ? q : S - 1;
-        const int slot = qlist ? qlist[kb + q] : q;
-        int qr = qidx ? qidx[kb + slot] : slot;
-        qr = qr < 0 ? 0 : (qr >= NQ ? NQ - 1 : qr);
-        qh[t] = *reinterpret_cast<const f16x8 *>(Qhi + (qb + qr) * 32 + g * 8);
-        if (PASSES == 3) ql[t] = *reinterpret_cast<const f16x8 *>(Qlo + (qb + qr) * 32 + g * 8);
+        const size_t qr = Q.row(b, Q.slot(b, q0 + t * 16 + col, S));
+        qh[t] = Q.frag(Q.hi, qr, g);
+        if (LO) ql[t] = Q.frag(Q.lo, qr, g);
     }
     const int n0 = by * per_split, n1 = min(n0 + per_split, N);
     float best[kQT];
@@ -272,7 +307,7 @@ k_nn_mfma(const unsigned short *__restrict__ Qhi, const unsigned short *__restri
             n = n < N ? n : N - 1;
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) unsigned *)(Dhi + (db + n) * 32 + sc * 8),
                                              (__attribute__((address_space(3))) unsigned *)(&lds[buf][0][i * 4096 + wave * 1024]), 16, 0, 0);
-            if (PASSES == 3)
+            if (LO)
                 __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) unsigned *)(Dlo + (db + n) * 32 + sc * 8),
                                                  (__attribute__((address_space(3))) unsigned *)(&lds[buf][1][i * 4096 + wave * 1024]), 16, 0, 0);
         }
@@ -284,44 +319,34 @@ k_nn_mfma(const unsigned short *__restrict__ Qhi, const unsigned short *__restri
         if (blk + 1 < nblk) {
             stage(blk + 1, buf ^ 1);
             static_assert(kRows == 128, "the counted waits below assume two 64-row issues per plane and stage");
-            if (PASSES == 3) asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+            if (LO) asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
         } else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
         const int nbase = n0 + blk * kRows;
-        if (nbase + kRows > n1) nn_step<PASSES, true>(lds[buf][0], lds[buf][1], qh, ql, best, bestn, nbase, n1, col, g);   // last step of a split only
-        else nn_step<PASSES, false>(lds[buf][0], lds[buf][1], qh, ql, best, bestn, nbase, n1, col, g);
+        if (nbase + kRows > n1) nn_step<LO, true>(lds[buf][0], lds[buf][1], qh, ql, best, bestn, nbase, n1, col, g);   // last step of a split only
+        else nn_step<LO, false>(lds[buf][0], lds[buf][1], qh, ql, best, bestn, nbase, n1, col, g);
         __builtin_amdgcn_sched_barrier(0);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();                                         // reads of `buf` done before it is restaged
         __builtin_amdgcn_sched_barrier(0);
     }
     if (n0 >= n1) return;
-    // the 4 lane groups hold disjoint row subsets of the same query: keep the larger score, ties -> lower index
 #pragma unroll
     for (int t = 0; t < kQT; ++t) {
-#pragma unroll
-        for (int sh = 16; sh <= 32; sh <<= 1) {
-            const float os = __shfl_xor(best[t], sh, 64);
-            const int on = __shfl_xor(bestn[t], sh, 64);
-            if (os > best[t] || (os == best[t] && on < bestn[t])) { best[t] = os; bestn[t] = on; }
-        }
+        merge_lane_groups(best[t], bestn[t]);
         const int q = q0 + t * 16 + col;
-        if (g == 0 && q < S) {
-            const unsigned long long key = ((unsigned long long)ordered_bits(best[t]) << 32) |
-                                           (unsigned long long)(0xffffffffu - (unsigned)bestn[t]);
-            atomicMax(keys + kb + (qlist ? qlist[kb + q] : q), key);
-        }
+        if (g == 0 && q < S) atomicMax(keys + kb + Q.slot(b, q, S), make_key(best[t], bestn[t]));
     }
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// Round 4: the SAME arg-max with most of the database never touched.  The brute-force search above scores every seed
+// The SAME arg-max with most of the database never touched.  The brute-force search above scores every seed
 // against every pixel of the other view (4096 x 262 144 x 2 directions per pair and round); a descriptor map is smooth,
 // so whole patches of pixels can be excluded by a bound.  Per map, once per matcher call (k_frnn_blockstats): for every
-// block = 8 x 8 pixel tile (a first version used 64 consecutive pixels of an image row: radius 0.63 on the synthetic
-// scene's unit descriptors, a quarter of all blocks survived; a square tile is four times more compact) a reference point
+// block = 8 x 8 pixel tile (64 consecutive pixels of an image row have radius 0.63 on the synthetic scene's unit
+// descriptors and a quarter of all blocks survive; a square tile is four times more compact) a reference point
 // c (the centroid, rounded to fp16 so that it is an exact MFMA operand), the radius r = max ||x - c|| and ||c|| + r.
 // Blocks are numbered by * ceil(W / 8) + bx; block-local row 8 ry + rx is pixel (8 by + ry, 8 bx + rx); the packed map
 // itself stays in raster order (a packed row is 64 bytes: the tile's rows are gathered by address).
@@ -332,13 +357,25 @@ k_nn_mfma(const unsigned short *__restrict__ Qhi, const unsigned short *__restri
 //      a lower bound m(q) of the final maximum (minus a slack for the rounding differences to the MFMA scores);
 //   2. k_frnn_survivors: <q, c> for all (query, block) pairs on the matrix core (1/64 of the full search), one bit per
 //      (16-query tile, block): set unless  <q, c> + ||q|| (r + slack)  <  m(q)  for all 16 queries;
-//   3. k_frnn_eval scores the surviving blocks with the SAME MFMA sequence as nn_step (bit-identical scores) and keeps
+//   3. k_frnn_eval scores the surviving blocks through score_tile, as nn_step does (bit-identical scores), and keeps
 //      (score, lowest PIXEL index) - tiles are not visited in raster order, so ties compare indices explicitly - then the
 //      same 64-bit key merge; a block that holds the maximum, or a tie with it, always survives (its bound is >= its
 //      best score >= m), so index AND score equal the brute-force result bit for bit;
 //   4. if more than a quarter of the pairs survived (descriptors without spatial coherence, e.g. a random-weight
 //      network), k_frnn_eval stands down and k_nn_mfma runs instead (both test the same device counter).
 // Finite descriptors are assumed (this file is built with -fno-honor-nans, as the brute-force kernel always was).
+constexpr float kRoundUp = 1.000244140625f;    // (1 + 2^-12): makes an fp32 norm or distance an upper bound of the exact one
+
+struct Block { int y0, x0; };                  // top left pixel of a block
+__device__ __forceinline__ Block block_origin(int blk, int W) {
+    const int BW = (W + 7) >> 3, by = blk / BW;
+    return {by * 8, (blk - by * BW) * 8};
+}
+// row of pixel (y, x) in its map; a pixel of the block that lies outside the map reads the block's origin instead
+__device__ __forceinline__ size_t pixel_or_origin(bool inside, int y, int x, Block o, int W) {
+    return inside ? (size_t)y * W + x : (size_t)o.y0 * W + o.x0;
+}
+
 __device__ __forceinline__ void load_row32(const unsigned short *__restrict__ hi, const unsigned short *__restrict__ lo, size_t row,
                                            float (&x)[32]) {
 #pragma unroll
@@ -358,8 +395,8 @@ __device__ __forceinline__ void load_row32(const unsigned short *__restrict__ hi
 // cen [P][NBp][32] fp16, rad / bn [P][NBp] fp32; NBp = blocks rounded up to a multiple of 64 (padding: rad = -inf).
 // One wave per tile: lane = (tile row ry = lane >> 3, dimension quad dq = lane & 7) owns the 8 pixels of its row x 4
 // dimensions (8-byte loads; the 8 lanes of a row cover the pixels' 64-byte packed rows), so the centroid needs 3 shuffle
-// steps per dimension quad and the squared distances 3 per pixel (a first version - lane = pixel, 32 wave reductions - took
-// 78 us per 8 maps, more than the searches it serves).
+// steps per dimension quad and the squared distances 3 per pixel (lane = pixel with 32 wave reductions: 78 us per 8 maps,
+// more than the searches it serves).
 __global__ void __launch_bounds__(kThreads)
 k_frnn_blockstats(const unsigned short *__restrict__ hi, const unsigned short *__restrict__ lo, unsigned short *__restrict__ cen,
                   float *__restrict__ rad, float *__restrict__ bn, int H, int W, int NB, int NBp) {
@@ -371,15 +408,15 @@ k_frnn_blockstats(const unsigned short *__restrict__ hi, const unsigned short *_
         if (lane == 0) { rad[sb] = -INFINITY; bn[sb] = 0.f; }
         return;
     }
-    const int BW = (W + 7) >> 3, by = blk / BW, bx = blk - by * BW;
+    const Block o = block_origin(blk, W);
     const int ry = lane >> 3, dq = lane & 7;
-    const int y = by * 8 + ry, ch = H - by * 8 < 8 ? H - by * 8 : 8, cw = W - bx * 8 < 8 ? W - bx * 8 : 8;
+    const int y = o.y0 + ry, ch = H - o.y0 < 8 ? H - o.y0 : 8, cw = W - o.x0 < 8 ? W - o.x0 : 8;
     const bool rowok = y < H;
     float v[8][4];
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
         const bool ok = rowok && i < cw;
-        const size_t row = (size_t)b * H * W + (ok ? (size_t)y * W + bx * 8 + i : (size_t)by * 8 * W + bx * 8);
+        const size_t row = (size_t)b * H * W + pixel_or_origin(ok, y, o.x0 + i, o, W);
         union { uint2 q; _Float16 h[4]; } A;
         A.q = *reinterpret_cast<const uint2 *>(hi + row * 32 + dq * 4);
 #pragma unroll
@@ -420,36 +457,32 @@ k_frnn_blockstats(const unsigned short *__restrict__ hi, const unsigned short *_
     for (int sh = 8; sh <= 32; sh <<= 1) dmax = fmaxf(dmax, __shfl_xor(dmax, sh, 64));
     if (ry == 0) reinterpret_cast<uint2 *>(cen + sb * 32)[dq] = C.q;
     if (lane == 0) {
-        const float r = sqrtf(dmax) * 1.000244140625f;                          // (1 + 2^-12): the fp32 rounding of the distance
+        const float r = sqrtf(dmax) * kRoundUp;
         rad[sb] = r;
-        bn[sb] = sqrtf(c2) * 1.000244140625f + r;                               // >= ||x|| for every row of the block
+        bn[sb] = sqrtf(c2) * kRoundUp + r;                                      // >= ||x|| for every row of the block
     }
 }
 
 // one wave per query: the exact-enough maximum over the rows of the block the centroid search chose -> mlb, ||q||
-template <bool SPLIT>
+template <bool LO>
 __global__ void __launch_bounds__(kThreads)
-k_frnn_seed_lb(const unsigned short *__restrict__ Qhi, const unsigned short *__restrict__ Qlo, const int32_t *__restrict__ qidx,
-               const unsigned short *__restrict__ Dhi, const unsigned short *__restrict__ Dlo, const float *__restrict__ bn,
-               unsigned long long *__restrict__ keysC, float *__restrict__ mlb, float *__restrict__ qnorm, int S_all, int NQ,
-               int H, int W, int NB, int NBp, const int32_t *__restrict__ qlist, const int32_t *__restrict__ qcount) {
+k_frnn_seed_lb(const Queries Q, const unsigned short *__restrict__ Dhi, const unsigned short *__restrict__ Dlo,
+               const float *__restrict__ bn, unsigned long long *__restrict__ keysC, float *__restrict__ mlb,
+               float *__restrict__ qnorm, int H, int W, int NB, int NBp) {
     const int b = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int S = qcount ? qcount[b] : S_all;
+    const int S = Q.count(b);
     const int q = blockIdx.x * (kThreads / 64) + wave;
     if (q >= S) return;
-    const size_t kb = (size_t)b * S_all;
-    const int slot = qlist ? qlist[kb + q] : q;
-    int qr = qidx ? qidx[kb + slot] : slot;
-    qr = qr < 0 ? 0 : (qr >= NQ ? NQ - 1 : qr);
-    const unsigned long long key = keysC[kb + slot];
-    int bs = key == 0ull ? 0 : (int)(0xffffffffu - (unsigned)(key & 0xffffffffull));
+    const size_t kb = (size_t)b * Q.S_all;
+    const int slot = Q.slot(b, q, S);
+    int bs = key_index(keysC[kb + slot]);                                        // key 0 -> -1 -> block 0
     bs = bs < 0 ? 0 : (bs >= NB ? NB - 1 : bs);
     float qv[32], x[32];
-    load_row32(Qhi, SPLIT ? Qlo : nullptr, (size_t)b * NQ + qr, qv);
-    const int BW = (W + 7) >> 3, by = bs / BW, bx = bs - by * BW;
-    const int py = by * 8 + (lane >> 3), px = bx * 8 + (lane & 7);
+    load_row32(Q.hi, LO ? Q.lo : nullptr, Q.row(b, slot), qv);
+    const Block o = block_origin(bs, W);
+    const int py = o.y0 + (lane >> 3), px = o.x0 + (lane & 7);
     const bool ok = py < H && px < W;
-    load_row32(Dhi, SPLIT ? Dlo : nullptr, (size_t)b * H * W + (ok ? (size_t)py * W + px : (size_t)by * 8 * W + bx * 8), x);
+    load_row32(Dhi, LO ? Dlo : nullptr, (size_t)b * H * W + pixel_or_origin(ok, py, px, o, W), x);
     float sc = 0.f, q2 = 0.f;
 #pragma unroll
     for (int d = 0; d < 32; ++d) { sc = fmaf(qv[d], x[d], sc); q2 = fmaf(qv[d], qv[d], q2); }
@@ -457,7 +490,7 @@ k_frnn_seed_lb(const unsigned short *__restrict__ Qhi, const unsigned short *__r
 #pragma unroll
     for (int sh = 32; sh >= 1; sh >>= 1) sc = fmaxf(sc, __shfl_xor(sc, sh, 64));
     if (lane == 0) {
-        const float qn = sqrtf(q2) * 1.000244140625f;
+        const float qn = sqrtf(q2) * kRoundUp;
         mlb[kb + slot] = sc - kSlack * qn * bn[(size_t)b * NBp + bs];
         qnorm[kb + slot] = qn;
         keysC[kb + slot] = 0ull;                                                 // the scratch keys are left zero
@@ -465,43 +498,34 @@ k_frnn_seed_lb(const unsigned short *__restrict__ Qhi, const unsigned short *__r
 }
 
 // surv [P][nqt_all][NBp / 64] words: bit i of word w = block 64 w + i may hold the maximum of one of the tile's 16 queries.
-// <q, c> on the matrix core with the QUERIES as the A operand: a lane then holds one block (column lane & 15) against four
-// queries (rows 4 g + j), ORs its four tests, two shuffles OR the four lane groups and ONE ballot yields the tile's 16
-// block bits.  (With the blocks as rows every (block, lane group) bit had to be cut out of four ballots on the scalar
-// unit - 120 instructions per MFMA, 82 us per search: more than the scoring of the survivors.)
+// This kernel computes a BOUND, not a score: <q, c> from two MFMAs (hi.hi + lo.hi of the queries, the centroid has no lo
+// plane) with the QUERIES as the A operand, so it does not go through score_tile.  A lane then holds one block (column
+// lane & 15) against four queries (rows 4 g + j), ORs its four tests, two shuffles OR the four lane groups and ONE ballot
+// yields the tile's 16 block bits.  (With the blocks as rows every (block, lane group) bit had to be cut out of four
+// ballots on the scalar unit - 120 instructions per MFMA, 82 us per search: more than the scoring of the survivors.)
 constexpr int kQG = 4;                      // query tiles per wave in k_frnn_survivors
-constexpr int kQE = 1;                      // query tiles per workgroup in k_frnn_eval (4: 135 instead of 55 us per search - the kernel is
-                                            // bound by the serial work of a wave, not by the gathers the tiles would share)
 constexpr int kEvalY = 4;                   // workgroups per query tile in k_frnn_eval (1 / 2 / 4 / 8: 1292 / 1148 / 1065 / 1084 us per matcher call)
-template <bool SPLIT>
+template <bool LO>
 __global__ void __launch_bounds__(kThreads)
-k_frnn_survivors(const unsigned short *__restrict__ Qhi, const unsigned short *__restrict__ Qlo, const int32_t *__restrict__ qidx,
-                 const unsigned short *__restrict__ cen, const float *__restrict__ rad, const float *__restrict__ bn,
-                 const float *__restrict__ mlb, const float *__restrict__ qnorm, unsigned long long *__restrict__ surv,
-                 int32_t *__restrict__ total, int S_all, int NQ, int NBp, int nqt_all, int wpw,
-                 const int32_t *__restrict__ qlist, const int32_t *__restrict__ qcount) {
+k_frnn_survivors(const Queries Q, const unsigned short *__restrict__ cen, const float *__restrict__ rad,
+                 const float *__restrict__ bn, const float *__restrict__ mlb, const float *__restrict__ qnorm,
+                 unsigned long long *__restrict__ surv, int32_t *__restrict__ total, int NBp, int nqt_all, int wpw) {
     const int b = blockIdx.z, lane = threadIdx.x & 63, wave = threadIdx.x >> 6, col = lane & 15, g = lane >> 4;
-    const int S = qcount ? qcount[b] : S_all;
+    const int S = Q.count(b);
     const int qt0 = (blockIdx.x * (kThreads / 64) + wave) * kQG;                 // kQG consecutive query tiles share every centroid fragment
     if (qt0 * 16 >= S) return;
     const int nt = (S - qt0 * 16 + 15) / 16 < kQG ? (S - qt0 * 16 + 15) / 16 : kQG;   // wave-uniform
-    const size_t kb = (size_t)b * S_all, sbase = (size_t)b * NBp;
-    f16x8 qh[kQG], ql[SPLIT ? kQG : 1];
+    const size_t kb = (size_t)b * Q.S_all, sbase = (size_t)b * NBp;
+    f16x8 qh[kQG], ql[LO ? kQG : 1];
     float mq[kQG][4], nq[kQG][4];                                                // the four queries per tile this lane gets scores of
 #pragma unroll
     for (int u = 0; u < kQG; ++u) {
-        int q = (qt0 + u) * 16 + col;
-        q = q < S ? q : S - 1;
-        const int slot = qlist ? qlist[kb + q] : q;
-        int qr = qidx ? qidx[kb + slot] : slot;
-        qr = qr < 0 ? 0 : (qr >= NQ ? NQ - 1 : qr);
-        qh[u] = *reinterpret_cast<const f16x8 *>(Qhi + ((size_t)b * NQ + qr) * 32 + g * 8);   // A: row = query col, k chunk g
-        if (SPLIT) ql[u] = *reinterpret_cast<const f16x8 *>(Qlo + ((size_t)b * NQ + qr) * 32 + g * 8);
+        const size_t qr = Q.row(b, Q.slot(b, (qt0 + u) * 16 + col, S));
+        qh[u] = Q.frag(Q.hi, qr, g);                                             // A: row = query col, k chunk g
+        if (LO) ql[u] = Q.frag(Q.lo, qr, g);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            int qq = (qt0 + u) * 16 + 4 * g + j;
-            qq = qq < S ? qq : S - 1;
-            const int sj = qlist ? qlist[kb + qq] : qq;
+            const int sj = Q.slot(b, (qt0 + u) * 16 + 4 * g + j, S);
             mq[u][j] = mlb[kb + sj];
             nq[u][j] = qnorm[kb + sj];
         }
@@ -527,7 +551,7 @@ k_frnn_survivors(const unsigned short *__restrict__ Qhi, const unsigned short *_
             for (int t = 0; t < 4; ++t) {
                 f32x4 acc = {0.f, 0.f, 0.f, 0.f};
                 acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(qh[u], c[t], acc, 0, 0, 0);
-                if (SPLIT) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(ql[u], c[t], acc, 0, 0, 0);
+                if (LO) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(ql[u], c[t], acc, 0, 0, 0);
                 bool keep = false;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) keep = keep || !(acc[j] + nq[u][j] * e[t] < mq[u][j]);
@@ -543,50 +567,32 @@ k_frnn_survivors(const unsigned short *__restrict__ Qhi, const unsigned short *_
     if (lane == 0 && cnt) atomicAdd(total + b, cnt);
 }
 
-// grid (groups of QG query tiles, Y, P): a group's 4 Y waves take the words of the UNION of its tiles' survivor rows
-// round-robin (interleaved by 64-block word so that a cluster of survivors spreads).  Every gathered block is scored against
-// all QG tiles of the group - consecutive tiles are neighbours on the seed grid (seed_order) and need nearly the same
-// blocks, so the gathers, which bound this kernel (a block is 4 - 8 KB for 4 MFMAs per tile), are shared; scoring a block a
-// tile did not ask for only adds real candidates.  The rows of the NEXT surviving block are requested before the current
+// grid (query tiles, kEvalY, P): ONE 16-query tile per workgroup, whose 4 x kEvalY waves take the words of the tile's
+// survivor row round-robin (interleaved by 64-block word so that a cluster of survivors spreads).  (Four tiles per
+// workgroup sharing every gathered block: 135 instead of 55 us per search - the kernel is bound by the serial work of a
+// wave, not by the gathers the tiles would share.)  The rows of the NEXT surviving block are requested before the current
 // block is scored (two register sets, alternating: with one set and a copy the wait for the copy exposed every round trip).
-template <int PASSES, int QG>
+template <bool LO>
 __global__ void __launch_bounds__(kThreads)
-k_frnn_eval(const unsigned short *__restrict__ Qhi, const unsigned short *__restrict__ Qlo, const int32_t *__restrict__ qidx,
-            const unsigned short *__restrict__ Dhi, const unsigned short *__restrict__ Dlo,
+k_frnn_eval(const Queries Q, const unsigned short *__restrict__ Dhi, const unsigned short *__restrict__ Dlo,
             const unsigned long long *__restrict__ surv, const int32_t *__restrict__ total, unsigned long long *__restrict__ keys,
-            int S_all, int NQ, int H, int W, int NB, int NBp, int nqt_all, const int32_t *__restrict__ qlist,
-            const int32_t *__restrict__ qcount) {
+            int H, int W, int NB, int NBp, int nqt_all) {
     const int b = blockIdx.z, lane = threadIdx.x & 63, wave = threadIdx.x >> 6, col = lane & 15, g = lane >> 4;
-    const int S = qcount ? qcount[b] : S_all;
-    const int qt0 = blockIdx.x * QG;
-    if (qt0 * 16 >= S || prune_overflow(total[b], S, NB)) return;
-    const int nt = (S - qt0 * 16 + 15) / 16 < QG ? (S - qt0 * 16 + 15) / 16 : QG;   // workgroup-uniform
-    const size_t kb = (size_t)b * S_all, db = (size_t)b * H * W;
-    const int BW = (W + 7) >> 3;
-    f16x8 qh[QG], ql[PASSES == 3 ? QG : 1];
-    int slot[QG];
-    float best[QG];
-    int bestn[QG];
-#pragma unroll
-    for (int u = 0; u < QG; ++u) {
-        const int q = (qt0 + u) * 16 + col, qc = q < S ? q : S - 1;
-        slot[u] = qlist ? qlist[kb + qc] : qc;
-        int qr = qidx ? qidx[kb + slot[u]] : slot[u];
-        qr = qr < 0 ? 0 : (qr >= NQ ? NQ - 1 : qr);
-        qh[u] = *reinterpret_cast<const f16x8 *>(Qhi + ((size_t)b * NQ + qr) * 32 + g * 8);
-        if (PASSES == 3) ql[u] = *reinterpret_cast<const f16x8 *>(Qlo + ((size_t)b * NQ + qr) * 32 + g * 8);
-        best[u] = -INFINITY;
-        bestn[u] = 0;
-    }
+    const int S = Q.count(b), qt = blockIdx.x;
+    if (qt * 16 >= S || prune_overflow(total[b], S, NB)) return;
+    const size_t kb = (size_t)b * Q.S_all, db = (size_t)b * H * W;
+    const int slot = Q.slot(b, qt * 16 + col, S);
+    const size_t qr = Q.row(b, slot);
+    const f16x8 qh = Q.frag(Q.hi, qr, g), ql = LO ? Q.frag(Q.lo, qr, g) : qh;
+    float best = -INFINITY;
+    int bestn = 0;
     const int NBW = NBp / 64;
-    const unsigned long long *srow = surv + ((size_t)b * nqt_all + qt0) * NBW;
-    constexpr int NA = PASSES == 3 ? 8 : 4;
+    const unsigned long long *srow = surv + ((size_t)b * nqt_all + qt) * NBW;
+    constexpr int NA = LO ? 8 : 4;
     const int stride = (kThreads / 64) * (int)gridDim.y, first = wave + (kThreads / 64) * (int)blockIdx.y;
     for (int wbase = first; wbase < NBW; wbase += 64 * stride) {                // 64 words of this wave at a time (one per lane)
         const int wmine = wbase + lane * stride;
-        unsigned long long mine = 0ull;
-        if (wmine < NBW)
-            for (int u = 0; u < nt; ++u) mine |= srow[(size_t)u * NBW + wmine];
+        const unsigned long long mine = wmine < NBW ? srow[wmine] : 0ull;
         int k = -1;
         unsigned long long bits = 0ull;
         auto next_block = [&]() -> int {                                         // wave-uniform; -1 = no more
@@ -600,58 +606,46 @@ k_frnn_eval(const unsigned short *__restrict__ Qhi, const unsigned short *__rest
             return (wbase + k * stride) * 64 + i;
         };
         auto load_rows = [&](int blk, f16x8 (&a)[NA]) {                          // A rows 16 h + col = pixel (y0 + 2 h + (col >> 3), x0 + (col & 7))
-            const int by = blk / BW, bx = blk - by * BW;
+            const Block o = block_origin(blk, W);
 #pragma unroll
             for (int h = 0; h < 4; ++h) {
-                int py = by * 8 + 2 * h + (col >> 3), px = bx * 8 + (col & 7);
+                int py = o.y0 + 2 * h + (col >> 3), px = o.x0 + (col & 7);      // outside the map: the nearest pixel, masked in score
                 py = py < H ? py : H - 1;
                 px = px < W ? px : W - 1;
                 const size_t row = db + (size_t)py * W + px;
                 a[h] = *reinterpret_cast<const f16x8 *>(Dhi + row * 32 + g * 8);
-                if (PASSES == 3) a[4 + h] = *reinterpret_cast<const f16x8 *>(Dlo + row * 32 + g * 8);
+                if (LO) a[4 + h] = *reinterpret_cast<const f16x8 *>(Dlo + row * 32 + g * 8);
             }
         };
         auto score = [&](int blk, const f16x8 (&a)[NA]) {
-            const int by = blk / BW, bx = blk - by * BW;
-            const int y0 = by * 8, x0 = bx * 8;
+            const Block o = block_origin(blk, W);
+            const int y0 = o.y0, x0 = o.x0;
             // this lane's outputs: tile h, j -> block row 16 h + 4 g + j = pixel (y0 + 2 h + (g >> 1), x0 + 4 (g & 1) + j)
             const int ox = x0 + 4 * (g & 1);
             const bool edge = y0 + 8 > H || x0 + 8 > W;                         // tiles on the bottom / right edge
+            f32x4 acc[4];
 #pragma unroll
-            for (int u = 0; u < QG; ++u) {
-                if (u >= nt) break;
-                f32x4 acc[4];
-#pragma unroll
-                for (int h = 0; h < 4; ++h) {
-                    f32x4 c = {0.f, 0.f, 0.f, 0.f};
-                    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[h], qh[u], c, 0, 0, 0);   // the MFMA sequence of nn_step: same bits
-                    if (PASSES == 3) {
-                        c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[h], ql[u], c, 0, 0, 0);
-                        c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[4 + h], qh[u], c, 0, 0, 0);
-                    }
-                    acc[h] = c;
-                }
-                if (edge) {
-#pragma unroll
-                    for (int h = 0; h < 4; ++h)
-#pragma unroll
-                        for (int j = 0; j < 4; ++j)
-                            if (y0 + 2 * h + (g >> 1) >= H || ox + j >= W) acc[h][j] = -INFINITY;
-                }
-                float mx = acc[0][0];
+            for (int h = 0; h < 4; ++h) acc[h] = score_tile<LO>(a[h], a[LO ? 4 + h : h], qh, ql);   // nn_step's scores: same bits
+            if (edge) {
 #pragma unroll
                 for (int h = 0; h < 4; ++h)
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) mx = __builtin_fmaxf(mx, acc[h][j]);
-                const bool ge = mx >= best[u] && mx > -INFINITY;                // ties included: the LOWEST pixel index must win
-                if (__any(ge)) {                                                // rare after the first few blocks
-                    int nn = 0x7fffffff;                                        // lowest pixel index of this lane that holds mx
+                    for (int j = 0; j < 4; ++j)
+                        if (y0 + 2 * h + (g >> 1) >= H || ox + j >= W) acc[h][j] = -INFINITY;
+            }
+            float mx = acc[0][0];
 #pragma unroll
-                    for (int h = 3; h >= 0; --h)
+            for (int h = 0; h < 4; ++h)
 #pragma unroll
-                        for (int j = 3; j >= 0; --j) nn = (acc[h][j] == mx) ? (y0 + 2 * h + (g >> 1)) * W + ox + j : nn;
-                    if (ge && (mx > best[u] || nn < bestn[u])) { best[u] = mx; bestn[u] = nn; }
-                }
+                for (int j = 0; j < 4; ++j) mx = __builtin_fmaxf(mx, acc[h][j]);
+            const bool ge = mx >= best && mx > -INFINITY;                       // ties included: the LOWEST pixel index must win
+            if (__any(ge)) {                                                    // rare after the first few blocks
+                int nn = 0x7fffffff;                                            // lowest pixel index of this lane that holds mx
+#pragma unroll
+                for (int h = 3; h >= 0; --h)
+#pragma unroll
+                    for (int j = 3; j >= 0; --j) nn = (acc[h][j] == mx) ? (y0 + 2 * h + (g >> 1)) * W + ox + j : nn;
+                if (ge && (mx > best || nn < bestn)) { best = mx; bestn = nn; }
             }
         };
         f16x8 ra[NA], rb[NA];
@@ -667,22 +661,8 @@ k_frnn_eval(const unsigned short *__restrict__ Qhi, const unsigned short *__rest
             score(bb, rb);
         }
     }
-#pragma unroll
-    for (int u = 0; u < QG; ++u) {
-        if (u >= nt) break;
-        float bs = best[u];
-        int bn_ = bs == -INFINITY ? 0 : bestn[u];
-#pragma unroll
-        for (int sh = 16; sh <= 32; sh <<= 1) {
-            const float os = __shfl_xor(bs, sh, 64);
-            const int on = __shfl_xor(bn_, sh, 64);
-            if (os > bs || (os == bs && on < bn_)) { bs = os; bn_ = on; }
-        }
-        if (g == 0 && (qt0 + u) * 16 + col < S) {
-            const unsigned long long key = ((unsigned long long)ordered_bits(bs) << 32) | (unsigned long long)(0xffffffffu - (unsigned)bn_);
-            atomicMax(keys + kb + slot[u], key);
-        }
-    }
+    merge_lane_groups(best, bestn);                                             // a lane that scored nothing holds (-inf, 0)
+    if (g == 0 && qt * 16 + col < S) atomicMax(keys + kb + slot, make_key(best, bestn));
 }
 
 // ---- one round of fast reciprocal NN on the device (matching.fast_reciprocal_nn_device), batched over P pairs -----------
@@ -691,31 +671,40 @@ __global__ void __launch_bounds__(kThreads)
 k_frnn_mid(unsigned long long *__restrict__ keys, int32_t *__restrict__ xy2, long long total) {
     const long long i = (long long)blockIdx.x * kThreads + threadIdx.x;
     if (i >= total) return;
-    xy2[i] = (int32_t)(0xffffffffu - (unsigned)(keys[i] & 0xffffffffull));   // (inactive slots: key 0 -> a value nobody reads)
+    xy2[i] = key_index(keys[i]);                                              // (inactive slots: key 0 -> -1, which nobody reads)
     keys[i] = 0ull;
 }
+// Ordered compaction, one step of 256 entries: the rank of a flagged thread among the workgroup's flagged threads in thread
+// order (one ballot per wave, the wave counts through LDS) and their number.  wsum: [2][kThreads / 64], the halves taken
+// in turn (step & 1), so that ONE barrier per step separates the writes of a step from the reads of the step before.
+__device__ __forceinline__ int ballot_rank(bool flag, int (*wsum)[kThreads / 64], int step, int &total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned long long m = __ballot(flag);
+    int *ws = wsum[step & 1];
+    if (lane == 0) ws[wave] = __popcll(m);
+    __syncthreads();
+    int off = 0;
+    total = 0;
+#pragma unroll
+    for (int w = 0; w < kThreads / 64; ++w) { off += w < wave ? ws[w] : 0; total += ws[w]; }
+    return off + __popcll(m & ((1ull << lane) - 1ull));
+}
 // compact: the still-active seed slots of every pair, ascending, + their number - the query list of the next round's
-// searches.  One workgroup per pair walks its S flags in order (ballot + prefix counts): deterministic.
+// searches.  One workgroup per pair walks its S flags in order: deterministic.
 __global__ void __launch_bounds__(kThreads)
 k_frnn_compact(const uint8_t *__restrict__ active, const int32_t *__restrict__ order, int32_t *__restrict__ list,
                int32_t *__restrict__ count, int S) {
-    __shared__ int base, wsum[kThreads / 64];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (tid == 0) base = 0;
-    __syncthreads();
-    for (int s0 = 0; s0 < S; s0 += kThreads) {
+    __shared__ int wsum[2][kThreads / 64];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    int base = 0;
+    for (int s0 = 0, step = 0; s0 < S; s0 += kThreads, ++step) {
         const int pos = s0 + tid;
         const int sl = (order && pos < S) ? order[pos] : pos;                   // walk the slots in the caller's order (NULL: ascending)
         const bool a = pos < S && sl >= 0 && sl < S && active[(size_t)b * S + sl] != 0;
-        const unsigned long long m = __ballot(a);
-        if (lane == 0) wsum[wave] = __popcll(m);
-        __syncthreads();
-        int off = base;
-        for (int w = 0; w < wave; ++w) off += wsum[w];
-        if (a) list[(size_t)b * S + off + __popcll(m & ((1ull << lane) - 1ull))] = sl;
-        __syncthreads();
-        if (tid == 0) { int t = 0; for (int w = 0; w < kThreads / 64; ++w) t += wsum[w]; base += t; }
-        __syncthreads();
+        int n;
+        const int r = ballot_rank(a, wsum, step, n);
+        if (a) list[(size_t)b * S + base + r] = sl;
+        base += n;
     }
     if (tid == 0) count[b] = base;
 }
@@ -734,16 +723,22 @@ k_frnn_scatter(const int32_t *__restrict__ got1, const int32_t *__restrict__ got
     if (idx2) { idx2[(size_t)b * N2 + p2] = p1; valid2[(size_t)b * N2 + p2] = 1; }
 }
 // the distinct pairs as a list sorted by (pair, p1): ordered compaction of map1 in two launches (per-chunk counts, then
-// offsets = sum of the counts in front + an in-chunk prefix) - what torch.unique (a sort and a host synchronisation) did
+// offsets = sum of the counts in front + the rank inside the chunk) - what torch.unique (a sort and a host synchronisation) did
 constexpr int kChunk = kThreads * 16;
+// the steps of chunk c of a map1 row m: f(step, i, kept) for this thread's entry i of every step, kept = a pixel with a partner
+template <class F>
+__device__ __forceinline__ void chunk_keep(const int32_t *__restrict__ m, int c, int N1, F &&f) {
+    for (int k = 0; k < kChunk / kThreads; ++k) {
+        const int i = c * kChunk + k * kThreads + (int)threadIdx.x;
+        f(k, i, i < N1 && m[i] >= 0);
+    }
+}
 __global__ void __launch_bounds__(kThreads)
 k_frnn_count(const int32_t *__restrict__ map1, int32_t *__restrict__ chunk_cnt, int N1, int nchunk) {
     __shared__ int wsum[kThreads / 64];
     const int b = blockIdx.y, c = blockIdx.x, tid = threadIdx.x;
-    const int32_t *m = map1 + (size_t)b * N1;
-    int n = 0;
-    for (int k = 0; k < 16; ++k) { const int i = c * kChunk + tid * 16 + k; n += (i < N1 && m[i] >= 0) ? 1 : 0; }
-    for (int sh = 32; sh >= 1; sh >>= 1) n += __shfl_xor(n, sh, 64);
+    int n = 0;                                                                   // wave-uniform
+    chunk_keep(map1 + (size_t)b * N1, c, N1, [&](int, int, bool kept) { n += __popcll(__ballot(kept)); });
     if ((tid & 63) == 0) wsum[tid >> 6] = n;
     __syncthreads();
     if (tid == 0) { int t = 0; for (int w = 0; w < kThreads / 64; ++w) t += wsum[w]; chunk_cnt[b * nchunk + c] = t; }
@@ -751,34 +746,18 @@ k_frnn_count(const int32_t *__restrict__ map1, int32_t *__restrict__ chunk_cnt, 
 __global__ void __launch_bounds__(kThreads)
 k_frnn_emit(const int32_t *__restrict__ map1, const int32_t *__restrict__ chunk_cnt, int32_t *__restrict__ pairs,
             int32_t *__restrict__ count, int N1, int nchunk, int cap) {
-    __shared__ int pre[kThreads];
-    __shared__ int off0;
-    const int b = blockIdx.y, c = blockIdx.x, tid = threadIdx.x;
+    __shared__ int wsum[2][kThreads / 64];
+    const int b = blockIdx.y, c = blockIdx.x;
     const int32_t *m = map1 + (size_t)b * N1;
-    if (tid == 0) {
-        int o = 0, tot = 0;
-        for (int k = 0; k < nchunk; ++k) { const int v = chunk_cnt[b * nchunk + k]; if (k < c) o += v; tot += v; }
-        off0 = o;
-        if (c == 0) count[b] = tot < cap ? tot : cap;
-    }
-    int n = 0;
-    for (int k = 0; k < 16; ++k) { const int i = c * kChunk + tid * 16 + k; n += (i < N1 && m[i] >= 0) ? 1 : 0; }
-    pre[tid] = n;
-    __syncthreads();
-    for (int d = 1; d < kThreads; d <<= 1) {                       // inclusive scan of the 256 per-thread counts
-        const int v = tid >= d ? pre[tid - d] : 0;
-        __syncthreads();
-        pre[tid] += v;
-        __syncthreads();
-    }
-    int o = off0 + pre[tid] - n;
-    for (int k = 0; k < 16; ++k) {
-        const int i = c * kChunk + tid * 16 + k;
-        if (i < N1 && m[i] >= 0) {
-            if (o < cap) { pairs[((size_t)b * cap + o) * 2] = i; pairs[((size_t)b * cap + o) * 2 + 1] = m[i]; }
-            ++o;
-        }
-    }
+    int o = 0, tot = 0;                                                          // pairs of this map in front of chunk c / in all chunks
+    for (int k = 0; k < nchunk; ++k) { const int v = chunk_cnt[b * nchunk + k]; o += k < c ? v : 0; tot += v; }
+    if (c == 0 && threadIdx.x == 0) count[b] = tot < cap ? tot : cap;
+    chunk_keep(m, c, N1, [&](int step, int i, bool kept) {
+        int n;
+        const int at = o + ballot_rank(kept, wsum, step, n);
+        if (kept && at < cap) { pairs[((size_t)b * cap + at) * 2] = i; pairs[((size_t)b * cap + at) * 2 + 1] = m[i]; }
+        o += n;
+    });
 }
 // end: keys of the backward search -> back; a seed that returned to where it started is a reciprocal pair (recorded in
 // row `round` of got1 / got2, -1 elsewhere) and leaves the active set, the others continue from where they landed
@@ -787,7 +766,7 @@ k_frnn_end(unsigned long long *__restrict__ keys, const int32_t *__restrict__ xy
            uint8_t *__restrict__ active, int32_t *__restrict__ got1, int32_t *__restrict__ got2, long long total) {
     const long long i = (long long)blockIdx.x * kThreads + threadIdx.x;
     if (i >= total) return;
-    const int32_t back = (int32_t)(0xffffffffu - (unsigned)(keys[i] & 0xffffffffull));
+    const int32_t back = key_index(keys[i]);
     keys[i] = 0ull;
     const int32_t c = cur[i];
     const bool act = active[i] != 0, conv = act && back == c;
@@ -849,13 +828,17 @@ SearchPlan plan_search(int qblocks, int N, int P, int target, int max_splits, in
 // ~4 workgroups per CU over the whole call, whole LDS steps except in the last split
 SearchPlan plan_mfma_search(int S, int N, int P) { return plan_search(m3_cdiv(S, kQPB), N, P, 1024, 1024, kRows); }
 
-// The brute-force MFMA search of S queries (rows qidx of q; null: row s) in d: one pass for lo-less maps, three otherwise.
-// qlist / qcount: the active-set form; gate_total / gate_nb: the fallback form of the block-bound search.
-void launch_nn_mfma(const PackedMap &q, const int32_t *qidx, const PackedMap &d, unsigned long long *keys, int S,
-                    const SearchPlan &pl, hipStream_t st, const int32_t *qlist = nullptr, const int32_t *qcount = nullptr,
+// The queries of a search: S seed slots per pair whose rows (qidx; null: row s) lie in the packed map q
+Queries queries(const PackedMap &q, const int32_t *qidx, int S, const int32_t *qlist = nullptr, const int32_t *qcount = nullptr) {
+    return {q.hi, q.lo, qidx, qlist, qcount, S, q.N};
+}
+
+// The brute-force MFMA search of the queries in d: one pass for lo-less maps, three otherwise.
+// gate_total / gate_nb: the fallback form of the block-bound search.
+void launch_nn_mfma(const Queries &q, const PackedMap &d, unsigned long long *keys, const SearchPlan &pl, hipStream_t st,
                     const int32_t *gate_total = nullptr, int gate_nb = 0) {
-    hipLaunchKernelGGL(d.lo ? k_nn_mfma<3> : k_nn_mfma<1>, pl.grid, dim3(kThreads), 0, st, q.hi, q.lo, qidx, d.hi, d.lo, keys, S,
-                       q.N, d.N, pl.per_split, qlist, qcount, gate_total, gate_nb);
+    hipLaunchKernelGGL(d.lo ? k_nn_mfma<true> : k_nn_mfma<false>, pl.grid, dim3(kThreads), 0, st, q, d.hi, d.lo, keys, d.N,
+                       pl.per_split, gate_total, gate_nb);
 }
 
 // X [m.P * m.N][D], IEEE fp16 for a lo-less map and fp32 otherwise, to the K-padded planes of m
@@ -871,39 +854,37 @@ void launch_unpack(const unsigned long long *keys, int32_t *idx_out, float *scor
                        score_out, total);
 }
 
-// One search of a round: S queries (rows qidx of q) against d, merged into keys - the brute-force kernel.  With ds, the
-// statistics of d, the block bounds run first (prune_ws: PruneWs scratch) and gate it.
-int frnn_search(const PackedMap &q, const int32_t *qidx, const PackedMap &d, const BlockStats *ds, unsigned long long *keys,
-                int S, hipStream_t st, const int32_t *qlist, const int32_t *qcount, void *prune_ws) {
-    const int P = d.P, NQ = q.N;
+// One search of a round: the queries against d, merged into keys - the brute-force kernel.  With ds, the statistics of d,
+// the block bounds run first (prune_ws: PruneWs scratch) and gate it.
+int frnn_search(const Queries &q, const PackedMap &d, const BlockStats *ds, unsigned long long *keys, hipStream_t st,
+                void *prune_ws) {
+    const int P = d.P, S = q.S_all;
     const int32_t *gate_total = nullptr;
     if (ds) {
         const int H = ds->H, W = ds->W, NB = ds->NB, NBp = ds->NBp, NBW = NBp / 64, nqt = m3_cdiv(S, 16);
         const PruneWs ws(prune_ws, P, S, NBp);
         M3_CHECK_HIP(hipMemsetAsync(ws.keysC, 0, (size_t)ws.head_bytes, st), "m3_frnn_round_pruned/memset");
         // 1. the most promising block per query: the brute-force kernel on the centroids (hi plane of the queries).  The
-        // centroid table is [P][NBp][32]: the search runs over NBp rows so that pair b's rows start at b * NBp as
-        // k_frnn_blockstats laid them out (with N = NB every pair b > 0 scored the wrong rows whenever NB % 64 != 0, e.g.
-        // 224 x 224: results stayed exact, the lower bound - and with it the pruning - did not); the padding rows are zero
-        // vectors and k_frnn_seed_lb clamps the chosen block to < NB
-        launch_nn_mfma(PackedMap(q.hi, P, NQ, 1), qidx, PackedMap(ds->cen, P, NBp, 1), ws.keysC, S, plan_mfma_search(S, NBp, P), st,
-                       qlist, qcount);
+        // centroid table is [P][NBp][32] and the search runs over NBp rows, so that pair b's rows start at b * NBp as
+        // k_frnn_blockstats laid them out; the padding rows are zero vectors and k_frnn_seed_lb clamps the chosen block
+        // to < NB
+        launch_nn_mfma(q, PackedMap(ds->cen, P, NBp, 1), ws.keysC, plan_mfma_search(S, NBp, P), st);
         const dim3 blk(kThreads), gl(m3_cdiv(S, kThreads / 64), P);
         const int ngrp = m3_cdiv(nqt, kQG);
         int ysplit = m3_cdiv(8192, ngrp * P);
         ysplit = ysplit < 1 ? 1 : (ysplit > NBW ? NBW : ysplit);
         const int wpw = m3_cdiv(NBW, ysplit);
-        const dim3 gs(m3_cdiv(ngrp, kThreads / 64), m3_cdiv(NBW, wpw), P), ge(m3_cdiv(nqt, kQE), kEvalY, P);
+        const dim3 gs(m3_cdiv(ngrp, kThreads / 64), m3_cdiv(NBW, wpw), P), ge(nqt, kEvalY, P);
         // 2. - 3. lower bound per query, surviving blocks per query tile, exact scores of the survivors
-        hipLaunchKernelGGL(d.lo ? k_frnn_seed_lb<true> : k_frnn_seed_lb<false>, gl, blk, 0, st, q.hi, q.lo, qidx, d.hi, d.lo, ds->bn,
-                           ws.keysC, ws.mlb, ws.qn, S, NQ, H, W, NB, NBp, qlist, qcount);
-        hipLaunchKernelGGL(d.lo ? k_frnn_survivors<true> : k_frnn_survivors<false>, gs, blk, 0, st, q.hi, q.lo, qidx, ds->cen,
-                           ds->rad, ds->bn, ws.mlb, ws.qn, ws.surv, ws.total, S, NQ, NBp, nqt, wpw, qlist, qcount);
-        hipLaunchKernelGGL((d.lo ? k_frnn_eval<3, kQE> : k_frnn_eval<1, kQE>), ge, blk, 0, st, q.hi, q.lo, qidx, d.hi, d.lo, ws.surv,
-                           ws.total, keys, S, NQ, H, W, NB, NBp, nqt, qlist, qcount);
+        hipLaunchKernelGGL(d.lo ? k_frnn_seed_lb<true> : k_frnn_seed_lb<false>, gl, blk, 0, st, q, d.hi, d.lo, ds->bn, ws.keysC,
+                           ws.mlb, ws.qn, H, W, NB, NBp);
+        hipLaunchKernelGGL(d.lo ? k_frnn_survivors<true> : k_frnn_survivors<false>, gs, blk, 0, st, q, ds->cen, ds->rad, ds->bn,
+                           ws.mlb, ws.qn, ws.surv, ws.total, NBp, nqt, wpw);
+        hipLaunchKernelGGL(d.lo ? k_frnn_eval<true> : k_frnn_eval<false>, ge, blk, 0, st, q, d.hi, d.lo, ws.surv, ws.total, keys,
+                           H, W, NB, NBp, nqt);
         gate_total = ws.total;      // 4. gated on the survivor count, the workgroups below leave at once when the bounds worked
     }
-    launch_nn_mfma(q, qidx, d, keys, S, plan_mfma_search(S, d.N, P), st, qlist, qcount, gate_total, ds ? ds->NB : 0);
+    launch_nn_mfma(q, d, keys, plan_mfma_search(S, d.N, P), st, gate_total, ds ? ds->NB : 0);
     return M3_OK;
 }
 
@@ -919,10 +900,10 @@ int frnn_round(const PackedMap &m1, const PackedMap &m2, const BlockStats *s1, c
     const long long total = (long long)P * S;
     const dim3 eb(kThreads), eg((unsigned)m3_cdiv(total, (long long)kThreads));
     if (act_ws) hipLaunchKernelGGL(k_frnn_compact, dim3(P), eb, 0, st, active, seed_order, list, count, S);
-    int rc = frnn_search(m1, cur, m2, s2, keys, S, st, list, count, prune_ws);                    // view 1 -> view 2
+    int rc = frnn_search(queries(m1, cur, S, list, count), m2, s2, keys, st, prune_ws);           // view 1 -> view 2
     if (rc != M3_OK) return rc;
     hipLaunchKernelGGL(k_frnn_mid, eg, eb, 0, st, keys, xy2_ws, total);
-    rc = frnn_search(m2, xy2_ws, m1, s1, keys, S, st, list, count, prune_ws);                     // and back
+    rc = frnn_search(queries(m2, xy2_ws, S, list, count), m1, s1, keys, st, prune_ws);            // and back
     if (rc != M3_OK) return rc;
     hipLaunchKernelGGL(k_frnn_end, eg, eb, 0, st, keys, xy2_ws, cur, active, got1, got2, total);
     M3_CHECK_LAUNCH(where);
@@ -968,7 +949,7 @@ int m3_nn_search_mfma(const void *Q, const void *DB, int32_t *idx_out, float *sc
     M3_CHECK_LAUNCH("m3_nn_search_mfma/pack");
     M3_CHECK_HIP(hipMemsetAsync(keys_ws, 0, (size_t)B * S * 8, st), "m3_nn_search_mfma/memset");
     unsigned long long *keys = reinterpret_cast<unsigned long long *>(keys_ws);
-    launch_nn_mfma(q, nullptr, d, keys, S, plan_mfma_search(S, N, B), st);
+    launch_nn_mfma(queries(q, nullptr, S), d, keys, plan_mfma_search(S, N, B), st);
     M3_CHECK_LAUNCH("m3_nn_search_mfma");
     launch_unpack(keys, idx_out, score_out, (long long)B * S, st);
     M3_CHECK_LAUNCH("m3_nn_search_mfma/unpack");

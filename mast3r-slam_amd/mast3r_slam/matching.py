@@ -148,6 +148,18 @@ def nn_search(Q: torch.Tensor, DB: torch.Tensor, return_score: bool = False, met
     return (idx, score) if return_score else idx
 
 
+def _seed_grid(h: int, w: int, sub: int, dev=None):
+    """The seeds of fast reciprocal NN: the pixels (y, x) with y in arange(sub // 2, h, sub) and x in arange(sub // 2, w, sub).
+    -> (rows, columns) of the grid and, with a device, the seeds' linear indices y * w + x (int64 [rows * columns], row-major;
+    None without a device)."""
+    hs, ws = len(range(sub // 2, h, sub)), len(range(sub // 2, w, sub))
+    if dev is None:
+        return hs, ws, None
+    ys = torch.arange(sub // 2, h, sub, device=dev)
+    xs = torch.arange(sub // 2, w, sub, device=dev)
+    return hs, ws, (ys[:, None] * w + xs[None, :]).reshape(-1)
+
+
 _PATCH_ORDER: dict = {}
 
 
@@ -190,9 +202,8 @@ def fast_reciprocal_nn_maps(D1: torch.Tensor, D2: torch.Tensor, subsample: int =
     P, h1, w1, d = A.shape
     n1, n2 = h1 * w1, B.shape[1] * B.shape[2]
     dev = A.device
-    ys = torch.arange(subsample // 2, h1, subsample, device=dev)
-    xs = torch.arange(subsample // 2, w1, subsample, device=dev)
-    seeds = (ys[:, None] * w1 + xs[None, :]).reshape(-1).to(torch.int32)
+    hs, ws, seeds = _seed_grid(h1, w1, subsample, dev)
+    seeds = seeds.to(torch.int32)
     s = seeds.numel()
     if s == 0 or max_iter <= 0:
         raise ValueError("fast_reciprocal_nn_maps needs at least one seed and one round")
@@ -217,7 +228,7 @@ def fast_reciprocal_nn_maps(D1: torch.Tensor, D2: torch.Tensor, subsample: int =
         pws = torch.empty(int(L.m3_frnn_prune_ws_bytes(P, s, h1, w1, h2, w2)), dtype=torch.uint8, device=dev)
         _ffi.call("m3_frnn_blockstats", _ffi.ptr(pk1), _ffi.ptr(st1), P, h1, w1, f16, st)
         _ffi.call("m3_frnn_blockstats", _ffi.ptr(pk2), _ffi.ptr(st2), P, h2, w2, f16, st)
-        order = _seed_patch_order(len(ys), len(xs), dev)
+        order = _seed_patch_order(hs, ws, dev)
     for r in range(max_iter):
         if prune:
             _ffi.call("m3_frnn_round_pruned", _ffi.ptr(pk1), _ffi.ptr(pk2), _ffi.ptr(st1), _ffi.ptr(st2), _ffi.ptr(cur),
@@ -255,8 +266,8 @@ def match_fraction_scale(h: int, w: int) -> float:
     if not cfg.get("use_fast_nn", False):
         return 1.0
     sub = int(cfg.get("fast_nn_subsample", 8))
-    seeds = len(range(sub // 2, h, sub)) * len(range(sub // 2, w, sub))
-    return float(h * w) / float(max(1, seeds))
+    hs, ws, _ = _seed_grid(h, w, sub)
+    return float(h * w) / float(max(1, hs * ws))
 
 
 def match_fast_nn(X11, X21, D11, D21, idx_1_to_2_init=None):
@@ -318,9 +329,7 @@ def fast_reciprocal_nn(D1: torch.Tensor, D2: torch.Tensor, subsample: int = 8, m
     h1, w1, d = D1.shape
     f1, f2 = D1.reshape(1, -1, d).contiguous(), D2.reshape(1, -1, d).contiguous()
     dev = D1.device
-    ys = torch.arange(subsample // 2, h1, subsample, device=dev)
-    xs = torch.arange(subsample // 2, w1, subsample, device=dev)
-    xy1 = (ys[:, None] * w1 + xs[None, :]).reshape(-1)                      # active view-1 pixels
+    xy1 = _seed_grid(h1, w1, subsample, dev)[2]                             # active view-1 pixels
     out1, out2 = [], []
     for _ in range(max_iter):
         if xy1.numel() == 0:

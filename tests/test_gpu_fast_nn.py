@@ -36,19 +36,23 @@ def test_nn_search_vs_float64_oracle(dev, s, n, d, method):
     assert np.all(idx[dup & clear] == 0)                                     # never the duplicate at n // 2
 
 
-def test_nn_search_fp16_descriptors_are_exact_products(dev):
+@pytest.mark.parametrize("d", [16, 24, 32])
+def test_nn_search_fp16_descriptors_are_exact_products(dev, d):
     """Descriptors STORED as fp16 (BASELINE configs[4] 'fp16 features'): the MFMA multiplies them exactly and sums in
-    fp32, so against the float64 oracle on the SAME fp16 values only the fp32 summation bound applies."""
+    fp32, so against the float64 oracle on the SAME fp16 values only the fp32 summation bound applies (D * 2^-23: the
+    module's EPS for D <= 24, scaled by D / 24 above).  D = 16 and 32 are the other two fp16 instantiations of the pack
+    kernel."""
+    eps = EPS * max(d, 24) / 24
     rng = np.random.default_rng(11)
-    Q, DB = _unit(rng, 1000, 24).astype(np.float16), _unit(rng, 30000, 24).astype(np.float16)
+    Q, DB = _unit(rng, 1000, d).astype(np.float16), _unit(rng, 30000, d).astype(np.float16)
     DB[20000] = DB[7]
     idx, score = matching.nn_search(torch.from_numpy(Q)[None].to(dev), torch.from_numpy(DB)[None].to(dev), return_score=True)
     idx, score = idx[0].cpu().numpy(), score[0].cpu().numpy()
     ref, best, second = om.nn_search(Q.astype(np.float64), DB.astype(np.float64))
-    clear = best - second > 4 * EPS
+    clear = best - second > 4 * eps
     assert clear.mean() > 0.9 and np.array_equal(idx[clear], ref[clear])
     chosen = np.einsum("sd,sd->s", Q.astype(np.float64), DB[idx].astype(np.float64))
-    assert np.all(chosen >= best - 4 * EPS) and np.abs(score - chosen).max() < 4 * EPS
+    assert np.all(chosen >= best - 4 * eps) and np.abs(score - chosen).max() < 4 * eps
     assert np.all(idx[(ref == 7) & clear] == 7)
 
 
@@ -205,6 +209,65 @@ def test_block_bound_search_equals_brute_force_bit_for_bit(dev, case):
         _same_maps(fast, brute)
         if kind in ("smooth", "ragged"):
             assert int(brute["count"].min()) > 20
+
+
+@pytest.mark.parametrize("half", [False, True], ids=["f32", "f16"])
+@pytest.mark.parametrize("kind", ["random", "smooth"])
+def test_block_bound_search_with_more_than_one_query_block(dev, kind, half):
+    """More than 512 seeds: the active-set form of the brute-force kernel re-deals its workgroups over nb > 1 query blocks
+    and a query list spans blocks.  fast_reciprocal_nn_maps with and without block bounds and full rounds through the C
+    ABI (m3_frnn_round on every seed slot in every round) agree on every output.
+      * random: 2 maps of 96 x 128 unit descriptors without spatial coherence, subsample 3 -> S = 1376 (three query blocks,
+        the last of 352), 3 rounds.  The bounds prune nothing, so the pruned path takes its device-side fallback (the
+        gated brute-force kernel with a list).  The CPU oracle leaves 675 - 696 seeds per pair active after round 0 (two
+        query blocks, the second partial), 53 - 57 after round 1 and 1 - 2 after round 2.
+      * smooth: geometric_pair(96, 128), subsample 4 -> S = 768 (two query blocks in round 0), 4 rounds; the survivor
+        scoring does the work.  The CPU oracle converges 688 - 739 seeds per pair in round 0 and leaves 29 - 80."""
+    from mast3r_slam import _ffi
+    if kind == "random":
+        rng = np.random.default_rng(7)
+        D1 = rng.normal(size=(2, 96, 128, 24)).astype(np.float32); D2 = rng.normal(size=(2, 96, 128, 24)).astype(np.float32)
+        D1 /= np.linalg.norm(D1, axis=-1, keepdims=True); D2 /= np.linalg.norm(D2, axis=-1, keepdims=True)
+        sub, rounds, seeds = 3, 3, 1376
+    else:
+        sc = synthetic.geometric_pair(96, 128, seed=3, batch=2)
+        D1, D2 = sc["D21"], sc["D11"]
+        sub, rounds, seeds = 4, 4, 768
+    A, B = torch.from_numpy(np.ascontiguousarray(D1)).to(dev), torch.from_numpy(np.ascontiguousarray(D2)).to(dev)
+    if half:
+        A, B = A.half(), B.half()
+    fast = matching.fast_reciprocal_nn_maps(A, B, subsample=sub, max_iter=rounds, prune=True)
+    brute = matching.fast_reciprocal_nn_maps(A, B, subsample=sub, max_iter=rounds, prune=False)
+    assert fast["seeds"] == seeds
+    _same_maps(fast, brute)
+    # full rounds through the C ABI + a host-side sort / unique
+    P, h, w, d = A.shape
+    n, s, f16 = h * w, seeds, int(half)
+    L, st = _ffi.lib(), _ffi.stream_ptr()
+    pk1 = torch.empty(int(L.m3_frnn_pack_bytes(P, n, f16)), dtype=torch.uint8, device=dev)
+    pk2 = torch.empty_like(pk1)
+    _ffi.call("m3_frnn_pack", _ffi.ptr(A), _ffi.ptr(pk1), P, n, d, f16, st)
+    _ffi.call("m3_frnn_pack", _ffi.ptr(B), _ffi.ptr(pk2), P, n, d, f16, st)
+    ys, xs = torch.arange(sub // 2, h, sub, device=dev), torch.arange(sub // 2, w, sub, device=dev)
+    cur = (ys[:, None] * w + xs[None, :]).reshape(-1).to(torch.int32)[None].repeat(P, 1).contiguous()
+    active = torch.ones((P, s), dtype=torch.uint8, device=dev)
+    got1 = torch.empty((rounds, P, s), dtype=torch.int32, device=dev); got2 = torch.empty_like(got1)
+    xy2 = torch.empty((P, s), dtype=torch.int32, device=dev); keys = torch.zeros((P, s), dtype=torch.int64, device=dev)
+    left = []
+    for r in range(rounds):
+        _ffi.call("m3_frnn_round", _ffi.ptr(pk1), _ffi.ptr(pk2), _ffi.ptr(cur), _ffi.ptr(active), _ffi.ptr(got1[r]), _ffi.ptr(got2[r]),
+                  _ffi.ptr(xy2), _ffi.ptr(keys), P, s, n, n, f16, st)
+        left.append(active.sum(1).cpu().tolist())
+    print(kind, "f16" if half else "f32", "active after each round:", left, "pairs:", brute["count"].cpu().tolist())
+    if kind == "random":
+        assert min(left[0]) > 512 and 16 <= min(left[1]) and max(left[1]) < 512
+    else:
+        assert int(brute["count"].min()) > 600 and min(left[0]) >= 10
+    counts = brute["count"].cpu().tolist()
+    for p in range(P):
+        keep = got1[:, p].reshape(-1) >= 0
+        ref = torch.unique(torch.stack([got1[:, p].reshape(-1)[keep], got2[:, p].reshape(-1)[keep]], 1), dim=0)
+        assert counts[p] == ref.shape[0] and torch.equal(brute["pairs"][p, :counts[p]], ref)
 
 
 @pytest.mark.parametrize("half", [True, False], ids=["f16", "f32"])
