@@ -496,6 +496,48 @@ int m3_render_map(const float *const *X, const float *const *C, const void *cons
                   int bg_g, int bg_b, void *ws, int64_t ws_bytes, uint8_t *rgb, float *depth, int64_t *index,
                   void *stream);
 
+/* ------------------------------------------------------------ mesh rendering */
+
+/* Triangle rasteriser for the meshes.  Host side: mast3r_slam/render.py render_mesh.
+ *
+ * The mesh arrives as m3_mesh_scatter and the surface extraction write it: vertices float [V,3] (world), colors uint8
+ * [V,3], faces int32 [F,3] (rows of the vertex arrays).  The camera is as for m3_render_map: view_pose, 8 floats of T_WC
+ * in DEVICE memory, and a pinhole (fx, fy, cx, cy) of an Hv x Wv image.  S = 256 sub-pixel steps, guard band G = 16384.
+ *
+ *   vertex           c as m3_render_map's camera point; ok <=> near < c.z < far (strict, NaN fails);
+ *                    u = fx * (c.x / c.z) + cx, v likewise; in_guard <=> |u| <= G and |v| <= G;
+ *                    sx = (int)floorf(u * 256 + 0.5f), sy likewise.  Every operation is a separately rounded fp32 one
+ *   drawn face       its three indices lie in [0, V) (any other face is skipped and never dereferenced), its vertices are
+ *                    ok and in_guard, and A = (bx-ax)(cy-ay) - (by-ay)(cx-ax) != 0 (int64 on sx, sy).  cull = 1 also drops
+ *                    A > 0: with y down that is clockwise on the screen, so the counter-clockwise faces of m3_mesh_*
+ *                    seen from their keyframe (A < 0) stay.  There is NO clipping: a face with a vertex behind near,
+ *                    beyond far or outside the guard band is dropped whole
+ *   coverage         b and c are swapped when A < 0.  E_i = (qx-px)(Y-py) - (qy-py)(X-px) for the edge p -> q from vertex
+ *                    i+1 to vertex i+2 at the pixel centre (X, Y) = (256 x, 256 y), in int64.  Covered <=> for every i:
+ *                    E_i > 0, or E_i == 0 and the edge is top-left (dy < 0, or dy == 0 and dx > 0)
+ *   depth            l_i = (float)E_i / (float)A, iz_i = 1.0f / z_i, w = (l_0 iz_0 + l_1 iz_1) + l_2 iz_2, z = 1.0f / w
+ *   winner per pixel the smallest key (bits of z as uint32) << 32 | face index: nearest, ties to the smaller face index
+ *   colour           m_i = l_i * iz_i * z on the E_i of the winner, recomputed exactly; per channel
+ *                    floorf(((m_0 c_0 + m_1 c_1) + m_2 c_2) + 0.5f) clamped to 0 ... 255: smooth shading only
+ *   outputs          rgb uint8 [Hv,Wv,3] (else bg), depth float [Hv,Wv] (else +inf), index int64 [Hv,Wv] (the face index,
+ *                    else -1; may be NULL)
+ *
+ * m3_raster_launches(F) launches are queued (4: clear, project, raster, resolve; 2 for F = 0), whatever V and F are; there
+ * is no host synchronisation and no allocation, so the call can be captured into a graph.  The only atomics are 64-bit
+ * unsigned minima on the key buffer: the bytes of every output are the same on every call.  A face whose screen-clipped
+ * bounding box holds more than 64 pixels is walked by a whole wave in 8 x 8 blocks, any other by one lane; a mesh of fewer
+ * than 262 k faces shares the rows of blocks of its large faces among up to 64 slices of workgroups of the same launch.
+ * ws: m3_raster_ws_bytes(V, Hv, Wv) = V * 16 + Hv * Wv * 8 rounded up to 16 bytes (0 = unsupported: the view limits of
+ * m3_render_ws_bytes, 0 <= V <= 2^31 - 1), 16-byte aligned, contents ignored on entry: a 16-byte record per vertex and the
+ * dense key buffer.  0 <= F <= 2^31 - 1; V = 0 or F = 0 draws the background (vertices / colors, or faces / view_pose,
+ * may then be NULL); cull 0 or 1; fx, fy > 0; 0 <= near < far (far may be +inf); bg_* in 0 ... 255. */
+int64_t m3_raster_ws_bytes(int64_t V, int Hv, int Wv);
+int m3_raster_launches(int64_t F);
+int m3_raster_mesh(const float *vertices, const uint8_t *colors, const int32_t *faces, int64_t V, int64_t F,
+                   const float *view_pose, float fx, float fy, float cx, float cy, int Hv, int Wv, float near, float far,
+                   int cull, int bg_r, int bg_g, int bg_b, void *ws, int64_t ws_bytes, uint8_t *rgb, float *depth,
+                   int64_t *index, void *stream);
+
 /* ------------------------------------------------------- multi-view consistency */
 
 /* Geometric consistency of the keyframe map across keyframes.  Host side:

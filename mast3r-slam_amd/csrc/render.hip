@@ -12,20 +12,12 @@
 #include "map_points.h"
 #pragma clang fp contract(off)
 #include "view_dev.h"
+#include "zkey_dev.h"
 
 namespace {
 
-constexpr unsigned long long kNoKey = ~0ull;  // no source: a depth with these bits is a NaN and never a candidate
-// Key buffer to all ones, 16-byte stores.
-__global__ void __launch_bounds__(kThreads) k_render_clear(unsigned long long *__restrict__ keys, int64_t P) {
-    const int64_t i = ((int64_t)blockIdx.x * kThreads + threadIdx.x) * 2;
-    if (i + 2 <= P) *(ulonglong2 *)(keys + i) = ulonglong2{kNoKey, kNoKey};
-    else if (i < P) keys[i] = kNoKey;
-}
-
 // Grid as k_export_count.  A thread owns 4 consecutive points; X is only read when one of them passed the confidence
-// test.  Per footprint pixel: a plain load of the current key, and the atomic minimum only when the new key is smaller
-// (keys only ever decrease, so a stale value read here costs an atomic and never a result).
+// test.  Per footprint pixel: key_min (zkey_dev.h).
 template <int PS>
 __global__ void __launch_bounds__(kThreads) k_render_splat(const float *const *__restrict__ X,
                                                             const float *const *__restrict__ C,
@@ -62,9 +54,7 @@ __global__ void __launch_bounds__(kThreads) k_render_splat(const float *const *_
             for (int ox = -R; ox <= R; ++ox) {
                 const int xx = px + ox;
                 if (xx < 0 || xx >= Wv) continue;
-                unsigned long long *slot = keys + ((int64_t)yy * Wv + xx);
-                if (key < __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-                    __hip_atomic_fetch_min(slot, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                key_min(keys + ((int64_t)yy * Wv + xx), key);
             }
         }
     }
@@ -151,7 +141,7 @@ int m3_render_map(const float *const *X, const float *const *C, const void *cons
     hipStream_t st = (hipStream_t)stream;
     unsigned long long *keys = (unsigned long long *)ws;
     const int64_t P = (int64_t)Hv * Wv;
-    hipLaunchKernelGGL(k_render_clear, dim3(m3_cdiv(P, 2 * kThreads)), dim3(kThreads), 0, st, keys, P);
+    launch_key_clear(keys, P, st);
     if (K > 0) {
         const int tiles = m3_cdiv(N, kTile);
         const dim3 grid(K * tiles), block(kThreads);

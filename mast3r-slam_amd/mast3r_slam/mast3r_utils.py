@@ -17,7 +17,7 @@ the same bytes on the device.  The retrieval database (load_retriever :83-114,
 RetrievalDatabase :640-795, simple retrieval only) lives in mast3r_slam/retrieval.py and is re-exported here, as are
 the map, mesh and trajectory writers of mast3r_slam/export.py (collect_map, collect_mesh, save_ply, save_ply_mesh,
 save_trajectory; slam.py:320-415) and
-the headless map renderer of mast3r_slam/render.py (render_map, ViewRecorder and its camera helpers) and the focal
+the headless map renderer of mast3r_slam/render.py (render_map, render_mesh, ViewRecorder and its camera helpers) and the focal
 estimate of mast3r_slam/intrinsics.py (estimate_focal, estimate_intrinsics) and the multi-view consistency filter of
 mast3r_slam/consistency.py (multiview_support, consistent_keyframes) and the volumetric fusion of
 mast3r_slam/fusion.py (fuse_tsdf, extract_surface).
@@ -36,7 +36,8 @@ from .retrieval import RetrievalDatabase, load_retriever
 from .export import collect_map, collect_mesh, save_ply, save_ply_mesh, save_trajectory
 from .camera import CameraModel, load_calibration, undistort_device
 from .preprocess import adjust_intrinsics, resample_tables, resize_geometry, resize_img_device
-from .render import ViewRecorder, behind, default_intrinsics, depth_to_rgb, look_at, render_map, save_image
+from .render import (ViewRecorder, behind, default_intrinsics, depth_to_rgb, look_at, mesh_workspace_bytes, render_map,
+                     render_mesh, save_image)
 from .consistency import ConsistentFrame, consistent_keyframes, multiview_support, nearest_neighbours
 from .intrinsics import IntrinsicsEstimate, estimate_focal, estimate_intrinsics, intrinsics_from_rows
 from .fusion import TSDFVolume, extract_surface, fuse_tsdf
@@ -47,7 +48,8 @@ __all__ = [
     "mast3r_decode_symmetric_batch", "mast3r_match_asymmetric_batch", "load_retriever", "RetrievalDatabase",
     "collect_map", "collect_mesh", "save_ply", "save_ply_mesh", "save_trajectory",
     "resize_img_device", "resize_geometry", "resample_tables", "adjust_intrinsics",
-    "render_map", "default_intrinsics", "look_at", "behind", "depth_to_rgb", "save_image", "ViewRecorder",
+    "render_map", "render_mesh", "mesh_workspace_bytes", "default_intrinsics", "look_at", "behind", "depth_to_rgb", "save_image",
+    "ViewRecorder",
     "estimate_focal", "estimate_intrinsics", "intrinsics_from_rows", "IntrinsicsEstimate",
     "multiview_support", "consistent_keyframes", "nearest_neighbours", "ConsistentFrame",
     "fuse_tsdf", "extract_surface", "TSDFVolume",

@@ -13,6 +13,9 @@ display.  render_map draws the map as it stands on the device into an image from
 One call queues three launches whatever the number of keyframes, reads nothing back and allocates nothing when `out`
 and `workspace` are given; the view pose is read on the device, so a tracked pose can be used as it is and the call
 can be captured into a graph.  Two calls give identical bytes.  CPU tensors raise RuntimeError: there is no CPU path.
+
+render_mesh draws a triangle mesh (export.collect_mesh, fusion.extract_surface) the same way: solid surfaces instead of
+single points, four launches whatever the mesh size (csrc/raster.hip).
 """
 from __future__ import annotations
 
@@ -24,11 +27,13 @@ import numpy as np
 import torch
 
 from . import _ffi
-from .export import _MapTables, _check_workspace, _conf_gate, _map_tables
+from .export import _MapTables, _check_workspace, _conf_gate, _map_tables, collect_mesh
 
-__all__ = ["render_map", "default_intrinsics", "look_at", "behind", "depth_to_rgb", "save_image", "ViewRecorder"]
+__all__ = ["render_map", "render_mesh", "mesh_workspace_bytes", "default_intrinsics", "look_at", "behind", "depth_to_rgb",
+           "save_image", "ViewRecorder"]
 
 POINT_SIZES = (1, 3, 5, 7)
+CULL = {"none": 0, "back": 1}
 
 
 def default_intrinsics(size: Sequence[int], fov_deg: float = 60.0):
@@ -118,36 +123,23 @@ def workspace_bytes(size: Sequence[int]) -> int:
     return n
 
 
-def render_map(keyframes, T_WC, K, size, c_conf_threshold: Optional[float] = 1.5, point_size: int = 1,
-               near: float = 1e-3, far: float = math.inf, background=(0, 0, 0), return_index: bool = False, out=None,
-               workspace: Optional[torch.Tensor] = None):
-    """(rgb uint8 [H,W,3], depth float32 [H,W][, index int64 [H,W]]) of `keyframes` (as collect_map takes them) seen from
-    the Sim(3) pose T_WC ([1,8] or [8] float32 DEVICE tensor, read by the kernel) through the pinhole K = (fx, fy, cx,
-    cy) (or a 3 x 3 matrix; None: default_intrinsics(size)), size = (H, W).
-
-    depth is the camera-frame z of the winning point (+inf where nothing was drawn), index its source index k * N + n
-    (-1 where nothing was drawn).  `keyframes` may also be the result of map_tables(keyframes).  `out`: a tuple of tensors to write into instead of allocating; `workspace`: a uint8
-    device tensor of workspace_bytes(size).  An empty map gives the background image."""
+def _view_args(size, K, near, far, background):
+    """(H, W, (fx, fy, cx, cy), near, far, background) of a view, checked: ValueError for anything a renderer rejects."""
     if len(size) != 2 or int(size[0]) <= 0 or int(size[1]) <= 0:
         raise ValueError(f"size must be (H, W) with positive entries, got {size}")
     hv, wv = int(size[0]), int(size[1])
-    if point_size not in POINT_SIZES:
-        raise ValueError(f"point_size must be one of {POINT_SIZES}, got {point_size}")
-    fx, fy, cx, cy = _pinhole(K, (hv, wv))
+    pinhole = _pinhole(K, (hv, wv))
     near, far = float(near), float(far)
     if not (0.0 <= near < far):
         raise ValueError(f"need 0 <= near < far, got near={near}, far={far}")
     bg = tuple(int(v) for v in background)
     if len(bg) != 3 or any(v < 0 or v > 255 for v in bg):
         raise ValueError(f"background must be three values in 0 ... 255, got {background}")
-    ws_bytes = workspace_bytes((hv, wv))
-    m = keyframes if isinstance(keyframes, _MapTables) else _map_tables(keyframes)
-    view = _ffi.check(T_WC, torch.float32, "T_WC").reshape(-1)
-    if view.numel() != 8:
-        raise ValueError(f"T_WC must have 8 elements (t, q xyzw, s), got {tuple(T_WC.shape)}")
-    dev = view.device
-    if m is not None and m.device != dev:
-        raise ValueError(f"T_WC lives on {dev}, the map on {m.device}")
+    return hv, wv, pinhole, near, far, bg
+
+
+def _outputs(out, return_index: bool, hv: int, wv: int, dev):
+    """`out` checked, or freshly allocated: (rgb, depth[, index])."""
     if out is None:
         out = (torch.empty((hv, wv, 3), dtype=torch.uint8, device=dev), torch.empty((hv, wv), dtype=torch.float32, device=dev))
         if return_index:
@@ -158,6 +150,36 @@ def render_map(keyframes, T_WC, K, size, c_conf_threshold: Optional[float] = 1.5
     for t, dt, name, shape in zip(out, (torch.uint8, torch.float32, torch.int64), ("rgb", "depth", "index"), shapes):
         if _ffi.check(t, dt, f"out {name}", shape).data_ptr() != t.data_ptr():
             raise ValueError(f"out {name} must be contiguous")
+    return tuple(out)
+
+
+def _view_pose(T_WC) -> torch.Tensor:
+    view = _ffi.check(T_WC, torch.float32, "T_WC").reshape(-1)
+    if view.numel() != 8:
+        raise ValueError(f"T_WC must have 8 elements (t, q xyzw, s), got {tuple(T_WC.shape)}")
+    return view
+
+
+def render_map(keyframes, T_WC, K, size, c_conf_threshold: Optional[float] = 1.5, point_size: int = 1,
+               near: float = 1e-3, far: float = math.inf, background=(0, 0, 0), return_index: bool = False, out=None,
+               workspace: Optional[torch.Tensor] = None):
+    """(rgb uint8 [H,W,3], depth float32 [H,W][, index int64 [H,W]]) of `keyframes` (as collect_map takes them) seen from
+    the Sim(3) pose T_WC ([1,8] or [8] float32 DEVICE tensor, read by the kernel) through the pinhole K = (fx, fy, cx,
+    cy) (or a 3 x 3 matrix; None: default_intrinsics(size)), size = (H, W).
+
+    depth is the camera-frame z of the winning point (+inf where nothing was drawn), index its source index k * N + n
+    (-1 where nothing was drawn).  `keyframes` may also be the result of map_tables(keyframes).  `out`: a tuple of tensors to write into instead of allocating; `workspace`: a uint8
+    device tensor of workspace_bytes(size).  An empty map gives the background image."""
+    if point_size not in POINT_SIZES:
+        raise ValueError(f"point_size must be one of {POINT_SIZES}, got {point_size}")
+    hv, wv, (fx, fy, cx, cy), near, far, bg = _view_args(size, K, near, far, background)
+    ws_bytes = workspace_bytes((hv, wv))
+    m = keyframes if isinstance(keyframes, _MapTables) else _map_tables(keyframes)
+    view = _view_pose(T_WC)
+    dev = view.device
+    if m is not None and m.device != dev:
+        raise ValueError(f"T_WC lives on {dev}, the map on {m.device}")
+    out = _outputs(out, return_index, hv, wv, dev)
     if workspace is None:
         workspace = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
     _check_workspace(workspace, ws_bytes)
@@ -170,7 +192,69 @@ def render_map(keyframes, T_WC, K, size, c_conf_threshold: Optional[float] = 1.5
               use, thr, layout, _ffi.ptr(view), fx, fy, cx, cy, hv, wv, near, far, int(point_size), bg[0], bg[1], bg[2],
               _ffi.ptr(workspace), ws_bytes, _ffi.ptr(out[0]), _ffi.ptr(out[1]), _ffi.ptr(out[2]) if return_index else None,
               _ffi.stream_ptr())
-    return tuple(out)
+    return out
+
+
+def mesh_workspace_bytes(n_vertices: int, size: Sequence[int]) -> int:
+    """Bytes of the workspace render_mesh needs for a mesh of n_vertices and size = (H, W): a 16-byte record per vertex and
+    the dense key buffer of H * W * 8 bytes."""
+    n = int(_ffi.lib().m3_raster_ws_bytes(int(n_vertices), int(size[0]), int(size[1])))
+    if n <= 0:
+        raise ValueError(f"unsupported view size {tuple(size)} (each side 1 ... 16384) or vertex count {n_vertices} "
+                         "(at most 2^31 - 1)")
+    return n
+
+
+def render_mesh(vertices, colors=None, faces=None, T_WC=None, K=None, size=None, near: float = 1e-3, far: float = math.inf,
+                cull: str = "none", background=(0, 0, 0), return_index: bool = False, out=None,
+                workspace: Optional[torch.Tensor] = None):
+    """(rgb uint8 [H,W,3], depth float32 [H,W][, index int64 [H,W]]) of a triangle mesh - vertices float32 [V,3] in world
+    coordinates, colors uint8 [V,3], faces int32 [F,3], as export.collect_mesh, SLAM.mesh, fusion.extract_surface and
+    SLAM.fused_mesh return them - seen from the Sim(3) pose T_WC through the pinhole K, size = (H, W), all three as for
+    render_map.  The tuple those functions return may also be passed whole: render_mesh(mesh, T_WC, K, size).
+
+    A pixel whose centre a face covers (integer arithmetic on a grid of 256 steps per pixel, top-left rule: faces that
+    share an edge neither overlap nor leave a crack) gets the perspective-correct depth and the smoothly blended vertex
+    colours of the nearest such face, equal depths going to the smaller face index.  depth is +inf and index (the face
+    index) -1 where nothing was drawn.  cull "back" drops the faces that are clockwise on the screen (y down), which
+    keeps collect_mesh's faces seen from the side of their keyframe; "none" draws both windings.  Faces with an index
+    outside [0, V) are skipped.  `out` and `workspace` (mesh_workspace_bytes(V, size) bytes) as for render_map.
+
+    Known limitation: there is no clipping.  A face with a vertex at or behind `near`, at or beyond `far`, or more than
+    16384 pixels from the image origin is dropped whole, so a surface that passes close by the camera gets holes.
+    Smooth shading only; V and F at most 2^31 - 1."""
+    if isinstance(vertices, (tuple, list)):
+        if colors is not None:                                              # render_mesh(mesh, T_WC, K, size)
+            T_WC, K, size = colors, (faces if faces is not None else K), (T_WC if T_WC is not None else size)
+        if len(vertices) < 3:
+            raise ValueError("a mesh is (vertices, colors, faces[, index])")
+        vertices, colors, faces = vertices[:3]
+    if size is None or T_WC is None:
+        raise ValueError("render_mesh needs T_WC and size")
+    hv, wv, (fx, fy, cx, cy), near, far, bg = _view_args(size, K, near, far, background)
+    if cull not in CULL:
+        raise ValueError(f"cull must be one of {tuple(CULL)}, got {cull!r}")
+    for t, dt, name in ((vertices, torch.float32, "vertices"), (colors, torch.uint8, "colors"), (faces, torch.int32, "faces")):
+        if not isinstance(t, torch.Tensor) or t.dtype != dt or t.dim() != 2 or t.shape[1] != 3:
+            got = f"{t.dtype} {tuple(t.shape)}" if isinstance(t, torch.Tensor) else type(t).__name__
+            raise ValueError(f"{name} must be a {dt} [n,3] tensor, got {got}")
+    if colors.shape[0] != vertices.shape[0]:
+        raise ValueError(f"vertices has {vertices.shape[0]} rows, colors {colors.shape[0]}")
+    v, f = int(vertices.shape[0]), int(faces.shape[0])
+    view = _view_pose(T_WC)
+    dev = view.device
+    vertices, colors, faces = (_ffi.check(t, t.dtype, name) for t, name in ((vertices, "vertices"), (colors, "colors"), (faces, "faces")))
+    if any(t.device != dev for t in (vertices, colors, faces)):
+        raise ValueError(f"T_WC lives on {dev}, the mesh on {vertices.device}")
+    ws_bytes = mesh_workspace_bytes(v, (hv, wv))
+    out = _outputs(out, return_index, hv, wv, dev)
+    if workspace is None:
+        workspace = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+    _check_workspace(workspace, ws_bytes)
+    _ffi.call("m3_raster_mesh", _ffi.ptr(vertices) if v else None, _ffi.ptr(colors) if v else None, _ffi.ptr(faces) if f else None,
+              v, f, _ffi.ptr(view), fx, fy, cx, cy, hv, wv, near, far, CULL[cull], bg[0], bg[1], bg[2], _ffi.ptr(workspace),
+              ws_bytes, _ffi.ptr(out[0]), _ffi.ptr(out[1]), _ffi.ptr(out[2]) if return_index else None, _ffi.stream_ptr())
+    return out
 
 
 def depth_to_rgb(depth: torch.Tensor, near: Optional[float] = None, far: Optional[float] = None) -> torch.Tensor:
@@ -211,12 +295,24 @@ class ViewRecorder:
 
     camera: "follow" (behind(frame.T_WC, follow_distance, follow_height)), "frame" (the frame's own pose) or a fixed
     [1,8] pose.  K None: the frame's intrinsics moved to `size`, else default_intrinsics(size).  The output tensors
-    and the workspace are allocated once; per frame the host reads back the finished image and nothing else."""
+    and the workspace are allocated once; per frame the host reads back the finished image and nothing else.
+
+    surface "mesh" draws export.collect_mesh(keyframes, **mesh_kw) with render_mesh instead of the points with render_map
+    (render_kwargs are then render_mesh's).  The mesh is collected again for every recorded frame, which costs
+    collect_mesh's one host read of the vertex and face counts, and the workspace grows with the vertex count."""
 
     def __init__(self, directory, every: int = 1, camera="follow", size: Sequence[int] = (480, 640), K=None,
-                 follow_distance: float = 1.0, follow_height: float = 0.25, **render_kwargs) -> None:
+                 follow_distance: float = 1.0, follow_height: float = 0.25, surface: str = "points", mesh_kw=None,
+                 **render_kwargs) -> None:
         if int(every) < 1:
             raise ValueError(f"every must be >= 1, got {every}")
+        if surface == "fused":
+            raise ValueError("surface 'fused' is too costly per frame (a TSDF fusion of the whole map for every recorded "
+                             "frame): record 'points' or 'mesh', and draw the fused mesh once with SLAM.render_view")
+        if surface not in ("points", "mesh"):
+            raise ValueError(f"surface must be 'points' or 'mesh', got {surface!r}")
+        if mesh_kw and surface != "mesh":
+            raise ValueError("mesh_kw is for surface='mesh'")
         if isinstance(camera, str) and camera not in ("follow", "frame"):
             raise ValueError(f"camera must be 'follow', 'frame' or a pose, got {camera!r}")
         if "return_index" in render_kwargs or "out" in render_kwargs or "workspace" in render_kwargs:
@@ -226,6 +322,7 @@ class ViewRecorder:
         self.every, self.camera, self.size, self.K = int(every), camera, (int(size[0]), int(size[1])), K
         self.follow = (float(follow_distance), float(follow_height))
         self.render_kwargs = render_kwargs
+        self.surface, self.mesh_kw = surface, dict(mesh_kw or {})
         self.calls = 0
         self.paths: list[str] = []
         self.last_pose: Optional[torch.Tensor] = None
@@ -253,8 +350,16 @@ class ViewRecorder:
             self._out = (torch.empty((*self.size, 3), dtype=torch.uint8, device=dev),
                          torch.empty(self.size, dtype=torch.float32, device=dev))
             self._ws = torch.empty((workspace_bytes(self.size),), dtype=torch.uint8, device=dev)
-        rgb, _ = render_map(keyframes, pose, self.intrinsics(frame), self.size, out=self._out, workspace=self._ws,
-                            **self.render_kwargs)
+        if self.surface == "mesh":
+            mesh = collect_mesh(keyframes, **self.mesh_kw)[:3]
+            need = mesh_workspace_bytes(mesh[0].shape[0], self.size)
+            if self._ws.numel() < need:
+                self._ws = torch.empty((need,), dtype=torch.uint8, device=pose.device)
+            rgb, _ = render_mesh(*mesh, pose, self.intrinsics(frame), self.size, out=self._out, workspace=self._ws,
+                                 **self.render_kwargs)
+        else:
+            rgb, _ = render_map(keyframes, pose, self.intrinsics(frame), self.size, out=self._out, workspace=self._ws,
+                                **self.render_kwargs)
         path = os.path.join(self.directory, "view_%06d.png" % int(frame.frame_id))
         save_image(path, rgb)
         self.last_pose = pose.clone()

@@ -302,11 +302,19 @@ class SLAM:
 
     # ------------------------------------------------------------------ headless views (no counterpart: the reference
     # hands its callback to a desktop GUI)
-    def render_view(self, T_WC: Optional[torch.Tensor] = None, K=None, size=None, **kw):
+    def render_view(self, T_WC: Optional[torch.Tensor] = None, K=None, size=None, surface: str = "points", mesh_kw=None,
+                    **kw):
         """render.render_map over the keyframes: (rgb uint8 [H,W,3], depth float32 [H,W][, index]).  Defaults: the pose
         the last processed frame was given, the keyframes' own image size, and the keyframes' intrinsics moved to
         `size` (render.default_intrinsics without calibration).  K = "estimate": the pinhole of estimate_intrinsics()
-        moved to `size` (one host read of the per-keyframe focals)."""
+        moved to `size` (one host read of the per-keyframe focals).
+
+        surface "mesh" draws self.mesh(**mesh_kw) and "fused" self.fused_mesh(**mesh_kw) with render.render_mesh (solid
+        surfaces; `kw` are then render_mesh's, and index is the face index); "points" is render_map as above."""
+        if surface not in ("points", "mesh", "fused"):
+            raise ValueError(f"render_view: surface must be 'points', 'mesh' or 'fused', got {surface!r}")
+        if mesh_kw and surface == "points":
+            raise ValueError("render_view: mesh_kw is for surface='mesh' or 'fused'")
         frames = [kf for kf in self.keyframes._frames if kf.X_canon is not None]
         if T_WC is None:
             if not self.poses:
@@ -324,8 +332,12 @@ class SLAM:
                 raise ValueError(f"render_view: K must be intrinsics, None or 'estimate', got {K!r}")
             est = self.estimate_intrinsics()
             K = render.scaled_intrinsics(est.K, est.size, size)
-        return render.render_map(self.keyframes, T_WC, K, size, **kw)
+        if surface == "points":
+            return render.render_map(self.keyframes, T_WC, K, size, **kw)
+        mesh = (self.mesh if surface == "mesh" else self.fused_mesh)(**(mesh_kw or {}))
+        return render.render_mesh(*mesh[:3], T_WC, K, size, **kw)
 
-    def save_view(self, path, T_WC: Optional[torch.Tensor] = None, K=None, size=None, **kw) -> None:
+    def save_view(self, path, T_WC: Optional[torch.Tensor] = None, K=None, size=None, surface: str = "points",
+                  mesh_kw=None, **kw) -> None:
         """render_view written as a PNG."""
-        render.save_image(path, self.render_view(T_WC, K, size, **kw)[0])
+        render.save_image(path, self.render_view(T_WC, K, size, surface=surface, mesh_kw=mesh_kw, **kw)[0])
