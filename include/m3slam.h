@@ -675,6 +675,85 @@ int m3_tsdf_extract_scatter(const float *tsdf, const int32_t *weight, const uint
                             int64_t ws_bytes, int64_t V, int64_t F, float *vertices, uint8_t *colors, int32_t *faces,
                             void *stream);
 
+/* ------------------------------------------------------------ mesh components */
+
+/* Connected components of a triangle mesh, and the clean-up that keeps the large ones.  Host side:
+ * mast3r_slam/components.py.  The reference has no counterpart: this rule is the contract, and tests/components_twin.py
+ * restates it in numpy.
+ *
+ * The input is a mesh as collect_mesh / extract_surface return it:
+ *   - vertices float32 [V,3],
+ *   - colors uint8 [V,3],
+ *   - faces int32 [F,3], each entry a row of the vertex arrays.
+ *
+ * Connectivity.  Connectivity is by row, never by position.  Two vertices are connected when a valid face names both.
+ * Two vertices at the same coordinates but in different rows are not connected.
+ *
+ * Valid faces.  A face is valid when its three rows lie in [0, V).
+ *   - An invalid face connects nothing and is never kept.
+ *   - Invalid faces are counted.  The host raises ValueError when the count it reads back is non-zero.
+ *   - A face that names one row twice is valid.  It connects its rows and counts as a face.
+ *
+ * Labels.  label[v] (int32) is the smallest row in the component of v.  A vertex named by no valid face is its own
+ * component with 0 faces.
+ *
+ * Face counts.
+ *   - faces_of[c] is the number of valid faces whose first row lies in component c.
+ *   - largest is the maximum of faces_of.
+ *   - The winner is the component that attains largest.  On a tie the smaller label wins.
+ *
+ * Kept components.  A component is kept when all of these hold:
+ *   - faces_of >= max(1, min_faces).
+ *   - min_fraction == 0, or (double)faces_of >= (double)min_fraction * (double)largest.  Here min_fraction is an fp32
+ *     argument in [0, 1].  The test is one IEEE double multiply and one compare, exactly what the twin does in numpy
+ *     float64.
+ *   - largest_only == 0, or the component is the winner.
+ *
+ * Outputs.
+ *   - The kept vertices are the vertices of kept components.  They come out in ascending input row, with their colours
+ *     as passed.
+ *   - The kept faces are the valid faces of kept components.  They come out in ascending input face row, rewritten to
+ *     the new vertex rows.
+ *   - Optional: the input vertex row (int64 [V2]) and the input face row (int64 [F2]).
+ *
+ * Two calls give identical bytes.
+ *
+ * Left out.  Component area and any float criterion are out.  A float sum over atomics is not reproducible, and face
+ * counts are enough for both mesh sources.
+ *
+ * m3_mesh_components_label: six launches (parent[v] = v; one thread per face hooks the roots of its two edges, the larger
+ * under the smaller, with a compare-and-swap on parent - lock-free, nobody waits for another thread's store, and a
+ * stale load only makes the compare-and-swap fail; label[v] = root(v); valid faces per component with int32 atomicAdd;
+ * the winner with one 64-bit atomicMax of count << 32 | ~label; the header and faces_of_out).  F = 0 skips the two
+ * launches that have one thread per face.  labels_out int32 [V] and faces_of_out int32 [V] (the count of each vertex's
+ * component) may be NULL.  Afterwards ws int32 [4] = the components with at least one face, [5] = largest, [6] = the
+ * winner's label (-1 when there is no valid face), [7] = the invalid faces.
+ * m3_mesh_components_count, with the ws of a label call and the SAME V, F and faces: three launches (kept vertices and
+ * kept faces per tile of 256 rows, one exclusive scan of both).  Afterwards ws int32 [0] = V2 and [1] = F2: the host
+ * reads words 0 ... 7 in one copy.  largest and the winner are read from ws on the device.  V = 0 or F = 0: V2 = F2 = 0
+ * are written and nothing is launched.
+ * m3_mesh_components_scatter, with the same ws, mesh and V2, F2 as read back (both >= 1: the host launches nothing when
+ * F2 = 0): two launches (vertices, which also write the old row -> new row remap into ws; faces, which read it).  The
+ * filter is the one the count left in ws.  vertex_rows_out int64 [V2] and face_rows_out int64 [F2] may be NULL.
+ * m3_mesh_components_launches() = 11 = 6 + 3 + 2, whatever V, F and the content are.  No allocation and no host
+ * synchronisation: label and count can be captured into a graph.  The atomics are integer and commute, and output rows
+ * are tile offset + rank, never an atomic counter.
+ * ws: m3_mesh_components_ws_bytes(V, F) = 64 + pad(4 * ceil(V / 256)) + pad(4 * ceil(F / 256)) + 4 * pad(4 * V) bytes,
+ * pad rounding up to 16 (0 = unsupported: 0 <= V, F <= 2^31 - 1), 16-byte aligned, contents ignored on entry of label:
+ * int32 [16] header, the two offset tables, then parent, label, count and remap, int32 [V] each.
+ * M3_ERR_INVALID_ARG, before any HIP call, for NULL pointers (faces may be NULL when F = 0), negative sizes, min_fraction
+ * outside [0, 1] or NaN, largest_only other than 0 or 1, V2 outside 1 ... V, F2 outside 1 ... F, a misaligned ws or (label)
+ * a short one. */
+int64_t m3_mesh_components_ws_bytes(int64_t V, int64_t F);
+int m3_mesh_components_launches(void);
+int m3_mesh_components_label(const int32_t *faces, int64_t V, int64_t F, void *ws, int64_t ws_bytes, int32_t *labels_out,
+                             int32_t *faces_of_out, void *stream);
+int m3_mesh_components_count(void *ws, int64_t V, int64_t F, const int32_t *faces, int min_faces, float min_fraction,
+                             int largest_only, void *stream);
+int m3_mesh_components_scatter(const float *vertices, const uint8_t *colors, const int32_t *faces, int64_t V, int64_t F,
+                               void *ws, int64_t V2, int64_t F2, float *vertices_out, uint8_t *colors_out, int32_t *faces_out,
+                               int64_t *vertex_rows_out, int64_t *face_rows_out, void *stream);
+
 /* ---------------------------------------------------------- camera intrinsics */
 
 /* Focal length of every keyframe from its own pointmap.  Host side: mast3r_slam/intrinsics.py.

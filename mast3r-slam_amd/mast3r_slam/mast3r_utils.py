@@ -20,7 +20,8 @@ save_trajectory; slam.py:320-415) and
 the headless map renderer of mast3r_slam/render.py (render_map, render_mesh, ViewRecorder and its camera helpers) and the focal
 estimate of mast3r_slam/intrinsics.py (estimate_focal, estimate_intrinsics) and the multi-view consistency filter of
 mast3r_slam/consistency.py (multiview_support, consistent_keyframes) and the volumetric fusion of
-mast3r_slam/fusion.py (fuse_tsdf, extract_surface).
+mast3r_slam/fusion.py (fuse_tsdf, extract_surface) and the mesh clean-up of mast3r_slam/components.py (mesh_components,
+filter_components).
 """
 from __future__ import annotations
 
@@ -41,6 +42,7 @@ from .render import (ViewRecorder, behind, default_intrinsics, depth_to_rgb, loo
 from .consistency import ConsistentFrame, consistent_keyframes, multiview_support, nearest_neighbours
 from .intrinsics import IntrinsicsEstimate, estimate_focal, estimate_intrinsics, intrinsics_from_rows
 from .fusion import TSDFVolume, extract_surface, fuse_tsdf
+from .components import ComponentsInfo, filter_components, mesh_components
 
 __all__ = [
     "load_mast3r", "resize_img", "frame_to_numpy", "downsample", "mast3r_inference_mono", "mast3r_asymmetric_inference",
@@ -53,6 +55,7 @@ __all__ = [
     "estimate_focal", "estimate_intrinsics", "intrinsics_from_rows", "IntrinsicsEstimate",
     "multiview_support", "consistent_keyframes", "nearest_neighbours", "ConsistentFrame",
     "fuse_tsdf", "extract_surface", "TSDFVolume",
+    "mesh_components", "filter_components", "ComponentsInfo",
 ]
 
 
