@@ -232,6 +232,14 @@ int m3_track_normal_eq(const float *Xf, const float *Xk, const float *Qk, const 
                        const float *T_CkCf, double *out, double *ws, int N, float huber_k,
                        float sigma_ray, float sigma_dist, void *stream);
 
+/* The same build for the calibrated residual of m3_track_gn_calib_batch (one problem, N == H * W): the sums of
+ * one linearisation at T_CkCf, gated by valid & Xk.z > depth_eps & projection inside the image less pixel_border.
+ * K4 = HOST array (fx, fy, cx, cy).  out and ws as for m3_track_normal_eq. */
+int m3_track_normal_eq_calib(const float *Xf, const float *Xk, const float *Qk, const uint8_t *valid,
+                             const float *T_CkCf, double *out, double *ws, int N, int H, int W,
+                             const float *K4, float huber_k, float sigma_pixel, float sigma_depth,
+                             float pixel_border, float depth_eps, void *stream);
+
 /* Sim3.act over a point map (tracker.py:146 Xkk = T_CkCf.act(Xkf)): out = s R X + t. */
 int m3_sim3_act(const float *T, const float *X, float *out, int N, void *stream);
 

@@ -20,6 +20,7 @@
 // Calib: a model is its per-point function, its pixel lookup and whether it takes groups of four), gather4 + count_tail
 // the body of the three gather kernels (which differ in where a frame row comes from), track_solve<Model> the host
 // launch sequence of both solves.  The exception is the weighted-row loop inside the two per-point functions (see there).
+// The ray-distance model keeps its distance row out of that loop (see RayDist::point).
 #include "common.h"
 #include <cstdlib>
 #include "accum_dev.h"
@@ -259,18 +260,17 @@ struct RayDist {
         const V3<float> r = di * p;
         const float dk = __builtin_amdgcn_sqrtf(dot(xk, xk) + 1e-10f), dki = __builtin_amdgcn_rcpf(dk);
         const V3<float> rk = dki * xk;
-        const float res[4] = {rk.x - r.x, rk.y - r.y, rk.z - r.z, dk - d};
+        const float res[3] = {rk.x - r.x, rk.y - r.y, rk.z - r.z};
         const float di2 = di * di;
-        const V3<float> a[4] = {
+        const V3<float> a[3] = {
             {-di * (1.0f - di2 * p.x * p.x), di * di2 * p.x * p.y, di * di2 * p.x * p.z},
             {di * di2 * p.y * p.x, -di * (1.0f - di2 * p.y * p.y), di * di2 * p.y * p.z},
-            {di * di2 * p.z * p.x, di * di2 * p.z * p.y, -di * (1.0f - di2 * p.z * p.z)},
-            {-r.x, -r.y, -r.z}};
+            {di * di2 * p.z * p.x, di * di2 * p.z * p.y, -di * (1.0f - di2 * p.z * p.z)}};
         float Axx = 0.f, Axy = 0.f, Axz = 0.f, Ayy = 0.f, Ayz = 0.f, Azz = 0.f, cost = 0.f;
         V3<float> b{0.f, 0.f, 0.f};
 #pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const float si = (c < 3) ? si_ray : si_dist;
+        for (int c = 0; c < 3; ++c) {
+            const float si = si_ray;
             const float wr = fabsf(si * res[c]);
             const float hub = (wr < huber_k) ? 1.0f : huber_k * __builtin_amdgcn_rcpf(wr);
             const float w = si * si * hub;                         // (si * sqrt(hub))^2
@@ -282,6 +282,24 @@ struct RayDist {
             cost += 0.5f * wres * res[c];
         }
         accum_congruence(p, Axx, Axy, Axz, Ayy, Ayz, Azz, b, 1.0f, -1.0f, h);
+        // The distance row (a = -r) is added by its own entries, not through M(p): r is parallel to p, so its rotation
+        // columns p x a are zero identically and a . p = -d.  Through the congruence they came out as the float32 roundoff
+        // of a cancelling cross product times the row's weight - with the ray rows weighted down that noise exceeded the
+        // rotation block itself and the step failed on a negative pivot (tests/test_gpu_tracking_rows.py, the loop test).
+        {
+            const float rd = dk - d;
+            const float wr = fabsf(si_dist * rd);
+            const float hub = (wr < huber_k) ? 1.0f : huber_k * __builtin_amdgcn_rcpf(wr);
+            const float w = si_dist * si_dist * hub;
+            const V3<float> wv = w * r;
+            const float wd = w * d, wres = w * rd;
+            h[0] += wv.x * r.x; h[1] += wv.x * r.y; h[2] += wv.x * r.z; h[7] += wv.y * r.y; h[8] += wv.y * r.z; h[13] += wv.z * r.z;
+            h[6] += wd * r.x; h[12] += wd * r.y; h[17] += wd * r.z;     // H_t,s = w a (a . p) = w d r
+            h[27] += wd * d;                                             // H_s,s = w (a . p)^2
+            h[28] += wres * r.x; h[29] += wres * r.y; h[30] += wres * r.z;   // g = -J^T w res
+            h[34] += wres * d;
+            cost += 0.5f * wres * rd;
+        }
         h[35] += cost;
     }
 };
@@ -771,6 +789,25 @@ int m3_track_normal_eq(const float *Xf, const float *Xk, const float *Qk, const 
                        StepArgs{0, 0.f, 0.f, 1, kBlocks, nullptr, nullptr});
     hipLaunchKernelGGL(k_track_export, dim3(1), dim3(kThreads), 0, st, (const double *)ws, out, kBlocks);
     M3_CHECK_LAUNCH("m3_track_normal_eq");
+    return M3_OK;
+}
+
+int m3_track_normal_eq_calib(const float *Xf, const float *Xk, const float *Qk, const uint8_t *valid,
+                             const float *T_CkCf, double *out, double *ws, int N, int H, int W, const float *K4,
+                             float huber_k, float sigma_pixel, float sigma_depth, float pixel_border, float depth_eps,
+                             void *stream) {
+    M3_REQUIRE(Xf && Xk && Qk && valid && T_CkCf && out && ws && K4);
+    M3_REQUIRE(N > 0 && H > 0 && W > 0 && (int64_t)H * W == N);
+    M3_REQUIRE(sigma_pixel > 0.f && sigma_depth > 0.f && huber_k > 0.f);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_track_init, dim3(1), dim3(64), 0, st, (const float *)nullptr, (const float *)nullptr,
+                       T_CkCf, ws);
+    const Calib m{(float)(1.0 / (double)sigma_pixel), (float)(1.0 / (double)sigma_depth),
+                  TrackCalib{K4[0], K4[1], K4[2], K4[3], W, H, pixel_border, depth_eps}};
+    hipLaunchKernelGGL(k_track_accum<Calib>, dim3(kBlocks), dim3(kThreads), 0, st, Xf, Xk, Qk, valid, ws, N, huber_k, m,
+                       StepArgs{0, 0.f, 0.f, 1, kBlocks, nullptr, nullptr});
+    hipLaunchKernelGGL(k_track_export, dim3(1), dim3(kThreads), 0, st, (const double *)ws, out, kBlocks);
+    M3_CHECK_LAUNCH("m3_track_normal_eq_calib");
     return M3_OK;
 }
 

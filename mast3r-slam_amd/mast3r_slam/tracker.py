@@ -157,12 +157,10 @@ def opt_pose_calib_sim3(Xf, Xk, T_WCf, T_WCk, Qk, valid, K, img_size, cfg=None, 
         float(c["delta_norm"]), 1 if fixed_iters else 0))
 
 
-def normal_equations(Xf, Xk, T_CkCf, Qk, valid, cfg=None):
-    """The J^T W J / J^T W r reduction of tracker.py:239-244 at pose T_CkCf.
-    Returns (H [7,7] float64, g [7] float64, cost float64 scalar tensor)."""
-    c = dict(get_config()["tracking"])
-    c.update(cfg or {})
-    Xf = _ffi.check(Xf.reshape(-1, 3), torch.float32, "Xf")
+def _normal_eq(entry, Xf, Xk, T_CkCf, Qk, valid, n, tail):
+    """What the two normal_equations* calls share: checked inputs (n = points, -1 = taken from Xf), output and workspace,
+    the call of `entry` (`tail` = its arguments after N) and the 36 sums unpacked to (H, g, cost)."""
+    Xf = _ffi.check(Xf.reshape(n, 3), torch.float32, "Xf")
     n = Xf.shape[0]
     Xk = _ffi.check(Xk.reshape(-1, 3), torch.float32, "Xk", (n, 3))
     Qk = _ffi.check(Qk.reshape(-1), torch.float32, "Qk", (n,))
@@ -171,14 +169,37 @@ def normal_equations(Xf, Xk, T_CkCf, Qk, valid, cfg=None):
     dev = Xf.device
     out = torch.empty(36, dtype=torch.float64, device=dev)
     ws = _ws(dev)
-    _ffi.call("m3_track_normal_eq", _ffi.ptr(Xf), _ffi.ptr(Xk), _ffi.ptr(Qk), _ffi.ptr(v), _ffi.ptr(T),
-              _ffi.ptr(out), _ffi.ptr(ws), n, float(c["huber"]), float(c["sigma_ray"]), float(c["sigma_dist"]),
-              _ffi.stream_ptr())
+    _ffi.call(entry, _ffi.ptr(Xf), _ffi.ptr(Xk), _ffi.ptr(Qk), _ffi.ptr(v), _ffi.ptr(T), _ffi.ptr(out), _ffi.ptr(ws), n,
+              *tail, _ffi.stream_ptr())
     iu = torch.triu_indices(7, 7, device=dev)
     H = torch.zeros((7, 7), dtype=torch.float64, device=dev)
     H[iu[0], iu[1]] = out[:28]
     H = H + H.T - torch.diag(H.diagonal())
     return H, out[28:35].clone(), out[35].clone()
+
+
+def normal_equations(Xf, Xk, T_CkCf, Qk, valid, cfg=None):
+    """The J^T W J / J^T W r reduction of tracker.py:239-244 at pose T_CkCf.
+    Returns (H [7,7] float64, g [7] float64, cost float64 scalar tensor)."""
+    c = dict(get_config()["tracking"])
+    c.update(cfg or {})
+    return _normal_eq("m3_track_normal_eq", Xf, Xk, T_CkCf, Qk, valid, -1,
+                      (float(c["huber"]), float(c["sigma_ray"]), float(c["sigma_dist"])))
+
+
+def normal_equations_calib(Xf, Xk, T_CkCf, Qk, valid, K, img_size, cfg=None):
+    """normal_equations for the calibrated residual of opt_pose_calib_sim3 (tracker.py:326-406): one linearisation at
+    T_CkCf of the H * W points of img_size = (height, width), with that solve's gates and configuration keys."""
+    import ctypes
+    c = dict(get_config()["tracking"])
+    c.setdefault("sigma_pixel", 1.0); c.setdefault("sigma_depth", 10.0)
+    c.setdefault("pixel_border", 0); c.setdefault("depth_eps", 0.0)
+    c.update(cfg or {})
+    h, w = img_size
+    k4 = _k4(K)
+    return _normal_eq("m3_track_normal_eq_calib", Xf, Xk, T_CkCf, Qk, valid, h * w, (
+        h, w, ctypes.cast(k4, ctypes.c_void_p), float(c["huber"]), float(c["sigma_pixel"]), float(c["sigma_depth"]),
+        float(c["pixel_border"]), float(c["depth_eps"])))
 
 
 def count_unique(idx: torch.Tensor, valid: torch.Tensor, value_range: int) -> torch.Tensor:

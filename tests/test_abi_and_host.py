@@ -39,6 +39,8 @@ def test_every_declared_symbol_is_exported(built_lib):
     assert len(names) >= 18
     for n in names:
         assert hasattr(built_lib, n), f"{n} declared in include/ but not exported"
+    for n in ("m3_track_normal_eq", "m3_track_normal_eq_calib"):           # the one-linearisation entry of each tracking model
+        assert n in names
     assert len(set(RETIRED)) == 22
     for n in RETIRED:
         assert n not in names, f"{n} is retired but still declared in include/"
@@ -80,6 +82,15 @@ def test_null_arguments_are_rejected_without_a_gpu(built_lib):
     assert L.m3_refine_matches(None, None, None, None, 1, 4, 4, 24, 16, 3, 2, 0, None) == -1
     assert L.m3_track_gn_ray_dist(None, None, None, None, None, None, None, None, None, None, 16, 10, 1.345,
                                   0.003, 10.0, 1e-3, 1e-3, 0, None) == -1
+    K4 = (ctypes.c_float * 4)(64.0, 64.0, 32.0, 24.0)
+    one = ctypes.cast(K4, ctypes.c_void_p)          # any non-null address: validation fails before it is read
+    ne_calib = lambda **k: L.m3_track_normal_eq_calib(*[k.get(n, d) for n, d in (
+        ("Xf", one), ("Xk", one), ("Qk", one), ("valid", one), ("T", one), ("out", one), ("ws", one), ("N", 48 * 64), ("H", 48),
+        ("W", 64), ("K4", one), ("huber", 1.345), ("sigma_pixel", 1.0), ("sigma_depth", 10.0), ("border", 0.0), ("eps", 0.0),
+        ("stream", None))])
+    for bad in (dict(Xf=None), dict(K4=None), dict(out=None), dict(N=48 * 64 + 1), dict(H=0), dict(W=-64), dict(sigma_pixel=0.0),
+                dict(sigma_depth=-1.0), dict(huber=0.0)):
+        assert ne_calib(**bad) == -1, bad
     with pytest.raises(RuntimeError, match="invalid argument"):
         _ffi.call("m3_prep_iter_proj", None, None, None, None, None, None, 1, 4, 4, None)
 
