@@ -762,6 +762,66 @@ int m3_mesh_components_scatter(const float *vertices, const uint8_t *colors, con
                                void *ws, int64_t V2, int64_t F2, float *vertices_out, uint8_t *colors_out, int32_t *faces_out,
                                int64_t *vertex_rows_out, int64_t *face_rows_out, void *stream);
 
+/* --------------------------------------------------------------- mesh normals */
+
+/* Per-vertex normals of a triangle mesh, and vertex colours lit with them.  Host side:
+ * mast3r_slam/normals.py.  The reference has no counterpart: this rule is the contract, and tests/normals_twin.py
+ * restates it in numpy.  The rule is Open3D's - unit face normals, equal weights - with the sum made reproducible by
+ * doing it in integers.  Every fp32 and float64 operation below is rounded on its own (no fused multiply-add).
+ *
+ * Face f = (i0, i1, i2) with vertices a, b, c (rows i0, i1, i2 of vertices float32 [V,3]):
+ *   e1 = b - a, e2 = c - a                                            (fp32)
+ *   n  = (e1.y * e2.z - e1.z * e2.y, e1.z * e2.x - e1.x * e2.z, e1.x * e2.y - e1.y * e2.x)
+ *   len2 = (n.x * n.x + n.y * n.y) + n.z * n.z
+ * A face contributes nothing when
+ *   - an index lies outside [0, V) (nothing is dereferenced for such a face), or
+ *   - len2 is not finite or len2 < 2^-80: a repeated index, zero area, a NaN or infinite vertex.  With this threshold
+ *     no result depends on how subnormal numbers are treated.
+ * Every other face contributes u = n / sqrtf(len2) as q_k = (int64) rintf(u_k * 16777216.0f) (round to nearest even;
+ * the scaling by 2^24 is exact).  q is added to three int64 sums of each of the face's three vertices.  Integer adds
+ * commute, so the sums depend neither on the order of the faces nor on the order of the threads.
+ *
+ * Vertex v with sums (x, y, z):
+ *   - all three 0 (no face names it, only degenerate faces do, or the contributions cancel exactly): normal (0, 0, 0);
+ *   - otherwise x, y, z are converted to float64, L = sqrt((x * x + y * y) + z * z), normal_k = (float)(s_k / L).
+ * The conversions to float64 are exact while fewer than 2^29 faces share one vertex (|sum| < 2^29 * 2^24 = 2^53).
+ *
+ * m3_mesh_normals: three queued operations whatever V and F are (clear the sums; one thread per face, 64-bit integer
+ * atomic adds in global memory; one thread per vertex).  normals float32 [V,3].  V = 0 or F = 0 is valid; with F = 0 all
+ * normals are 0.  No allocation, nothing read back: the call can be captured into a graph, and two calls give identical
+ * bytes.  m3_mesh_normals_launches() = 3.
+ * ws: m3_mesh_normals_ws_bytes(V) = max(16, 24 * V rounded up to 16) bytes (0 = unsupported: 0 <= V <= 2^31 - 1),
+ * 16-byte aligned, contents ignored on entry: int64 [3][V], a plane per component.
+ *
+ * m3_mesh_shade: one launch, one thread per vertex, fp32.  out uint8 [V,3] from vertices float32 [V,3], normals float32
+ * [V,3] and colors uint8 [V,3] (NULL: the constant albedo_r, albedo_g, albedo_b, each 0 ... 255).  c_k is the colour
+ * channel as a float, n the normal, p the vertex.
+ *   mode 0 (lambert):
+ *     l = eye - p with eye = view_pose[0 ... 2] read on the device (light 0, the headlight; view_pose is a Sim(3) pose
+ *         t, q xyzw, s as the rasteriser takes it), or the constant (lx, ly, lz) (light 1: the world direction from the
+ *         surface towards the light)
+ *     d = ((n.x * l.x + n.y * l.y) + n.z * l.z) / sqrtf((l.x * l.x + l.y * l.y) + l.z * l.z)
+ *     d = fabsf(d) when two_sided
+ *     d = d > 0 ? fminf(d, 1) : 0                                      (a NaN gives 0)
+ *     I = ambient + (1 - ambient) * d                                  (1 - ambient is rounded first)
+ *     out_k = clamp(floorf(c_k * I + 0.5f), 0, 255)
+ *     A zero normal gets the ambient term alone.
+ *   mode 1 (normals): out_k = clamp(floorf((n_k * 0.5f + 0.5f) * 255.f + 0.5f), 0, 255), a NaN giving 0: world-space
+ *     normals as colours, (0, 0, 0) -> 128.  vertices, colors, view_pose and the light are not read.
+ * clamp(x, 0, 255) = fminf(fmaxf(x, 0), 255).
+ *
+ * M3_ERR_INVALID_ARG, before any HIP call: NULL vertices / faces / normals / out where V (for faces: F) > 0, a NULL,
+ * misaligned or short ws, pointers not aligned to 4 bytes, V or F outside 0 ... 2^31 - 1, ambient outside [0, 1] or
+ * NaN, mode other than 0 or 1, light other than 0 or 1, two_sided other than 0 or 1, an albedo outside 0 ... 255; in mode 0
+ * a NULL view_pose with light 0, and a zero or non-finite (lx, ly, lz) with light 1. */
+int64_t m3_mesh_normals_ws_bytes(int64_t V);
+int m3_mesh_normals_launches(void);
+int m3_mesh_normals(const float *vertices, const int32_t *faces, int64_t V, int64_t F, void *ws, int64_t ws_bytes,
+                    float *normals, void *stream);
+int m3_mesh_shade(const float *vertices, const float *normals, const uint8_t *colors, int64_t V, const float *view_pose,
+                  int light, float lx, float ly, float lz, float ambient, int two_sided, int mode, int albedo_r,
+                  int albedo_g, int albedo_b, uint8_t *out, void *stream);
+
 /* ---------------------------------------------------------- camera intrinsics */
 
 /* Focal length of every keyframe from its own pointmap.  Host side: mast3r_slam/intrinsics.py.

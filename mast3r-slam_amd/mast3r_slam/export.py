@@ -31,10 +31,12 @@ import torch
 
 from . import _ffi
 
-__all__ = ["collect_map", "collect_mesh", "save_ply", "save_ply_mesh", "save_trajectory"]
+__all__ = ["collect_map", "collect_mesh", "save_ply", "save_ply_mesh", "save_ply_mesh_normals", "save_trajectory"]
 
 IMG_F32_CHW, IMG_U8_HWC = 0, 1                                         # include/m3slam.h
 _PLY_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")])
+_PLY_NORMALS_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4"),
+                               ("red", "u1"), ("green", "u1"), ("blue", "u1")])
 _PLY_FACE_DTYPE = np.dtype([("n", "u1"), ("v", "<i4", (3,))])            # property list uchar int vertex_indices
 
 last_voxel_stats: dict = {}           # table slots / occupied voxels of the most recent voxel pass (tools/bench_map_export.py)
@@ -302,6 +304,44 @@ def save_ply_mesh(path, vertices, colors, faces, binary: bool = True):
             tri.tofile(fh)
         elif f:
             np.savetxt(fh, t, fmt="3 %d %d %d")
+    return v, f
+
+
+def save_ply_mesh_normals(path, vertices, colors, faces, normals, binary: bool = True):
+    """save_ply_mesh with per-vertex normals (normals.vertex_normals): the vertex properties are float x y z nx ny nz,
+    uchar red green blue - the order MeshLab, Open3D and CloudCompare write - followed by the face element as
+    save_ply_mesh writes it.  binary: two structured arrays in `binary_little_endian 1.0`; else ASCII lines (%.6f), for
+    small meshes.  ValueError when the row counts differ or a face index is outside [0, V).  Returns (V, F)."""
+    p = _host(vertices, np.float32).reshape(-1, 3)
+    c = _host(colors, np.uint8).reshape(-1, 3)
+    t = _host(faces, np.int32).reshape(-1, 3)
+    n = _host(normals, np.float32).reshape(-1, 3)
+    if p.shape[0] != c.shape[0] or p.shape[0] != n.shape[0]:
+        raise ValueError(f"{p.shape[0]} vertices but {c.shape[0]} colours and {n.shape[0]} normals")
+    v, f = p.shape[0], t.shape[0]
+    if f and (int(t.min()) < 0 or int(t.max()) >= v):
+        raise ValueError(f"face indices span [{int(t.min())}, {int(t.max())}], the mesh has {v} vertices")
+    with open(os.fspath(path), "wb") as fh:
+        fh.write(("ply\nformat {} 1.0\nelement vertex {}\nproperty float x\nproperty float y\nproperty float z\n"
+                  "property float nx\nproperty float ny\nproperty float nz\n"
+                  "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+                  "element face {}\nproperty list uchar int vertex_indices\nend_header\n"
+                  ).format("binary_little_endian" if binary else "ascii", v, f).encode("ascii"))
+        if binary:
+            body = np.empty(v, dtype=_PLY_NORMALS_DTYPE)
+            for k, name in enumerate("xyz"):
+                body[name], body["n" + name] = p[:, k], n[:, k]
+            body["red"], body["green"], body["blue"] = c[:, 0], c[:, 1], c[:, 2]
+            body.tofile(fh)
+            tri = np.empty(f, dtype=_PLY_FACE_DTYPE)
+            tri["n"], tri["v"] = 3, t
+            tri.tofile(fh)
+        else:
+            if v:
+                np.savetxt(fh, np.concatenate([p.astype(np.float64), n.astype(np.float64), c.astype(np.float64)], axis=1),
+                           fmt="%.6f %.6f %.6f %.6f %.6f %.6f %d %d %d")
+            if f:
+                np.savetxt(fh, t, fmt="3 %d %d %d")
     return v, f
 
 

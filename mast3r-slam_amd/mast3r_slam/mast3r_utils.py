@@ -21,7 +21,8 @@ the headless map renderer of mast3r_slam/render.py (render_map, render_mesh, Vie
 estimate of mast3r_slam/intrinsics.py (estimate_focal, estimate_intrinsics) and the multi-view consistency filter of
 mast3r_slam/consistency.py (multiview_support, consistent_keyframes) and the volumetric fusion of
 mast3r_slam/fusion.py (fuse_tsdf, extract_surface) and the mesh clean-up of mast3r_slam/components.py (mesh_components,
-filter_components).
+filter_components) and the vertex normals and lit vertex colours of mast3r_slam/normals.py (vertex_normals, shade_vertices;
+save_ply_mesh_normals writes them).
 """
 from __future__ import annotations
 
@@ -34,7 +35,7 @@ from .config import get_config
 from .model import Mast3rFull
 from . import matching
 from .retrieval import RetrievalDatabase, load_retriever
-from .export import collect_map, collect_mesh, save_ply, save_ply_mesh, save_trajectory
+from .export import collect_map, collect_mesh, save_ply, save_ply_mesh, save_ply_mesh_normals, save_trajectory
 from .camera import CameraModel, load_calibration, undistort_device
 from .preprocess import adjust_intrinsics, resample_tables, resize_geometry, resize_img_device
 from .render import (ViewRecorder, behind, default_intrinsics, depth_to_rgb, look_at, mesh_workspace_bytes, render_map,
@@ -43,6 +44,7 @@ from .consistency import ConsistentFrame, consistent_keyframes, multiview_suppor
 from .intrinsics import IntrinsicsEstimate, estimate_focal, estimate_intrinsics, intrinsics_from_rows
 from .fusion import TSDFVolume, extract_surface, fuse_tsdf
 from .components import ComponentsInfo, filter_components, mesh_components
+from .normals import shade_vertices, vertex_normals
 
 __all__ = [
     "load_mast3r", "resize_img", "frame_to_numpy", "downsample", "mast3r_inference_mono", "mast3r_asymmetric_inference",
@@ -56,6 +58,7 @@ __all__ = [
     "multiview_support", "consistent_keyframes", "nearest_neighbours", "ConsistentFrame",
     "fuse_tsdf", "extract_surface", "TSDFVolume",
     "mesh_components", "filter_components", "ComponentsInfo",
+    "vertex_normals", "shade_vertices", "save_ply_mesh_normals",
 ]
 
 

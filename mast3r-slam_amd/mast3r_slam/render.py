@@ -34,6 +34,7 @@ __all__ = ["render_map", "render_mesh", "mesh_workspace_bytes", "default_intrins
 
 POINT_SIZES = (1, 3, 5, 7)
 CULL = {"none": 0, "back": 1}
+SHADING = (None, "headlight", "normals")
 
 
 def default_intrinsics(size: Sequence[int], fov_deg: float = 60.0):
@@ -207,7 +208,8 @@ def mesh_workspace_bytes(n_vertices: int, size: Sequence[int]) -> int:
 
 def render_mesh(vertices, colors=None, faces=None, T_WC=None, K=None, size=None, near: float = 1e-3, far: float = math.inf,
                 cull: str = "none", background=(0, 0, 0), return_index: bool = False, out=None,
-                workspace: Optional[torch.Tensor] = None):
+                workspace: Optional[torch.Tensor] = None, shading: Optional[str] = None, normals: Optional[torch.Tensor] = None,
+                shade_kw=None):
     """(rgb uint8 [H,W,3], depth float32 [H,W][, index int64 [H,W]]) of a triangle mesh - vertices float32 [V,3] in world
     coordinates, colors uint8 [V,3], faces int32 [F,3], as export.collect_mesh, SLAM.mesh, fusion.extract_surface and
     SLAM.fused_mesh return them - seen from the Sim(3) pose T_WC through the pinhole K, size = (H, W), all three as for
@@ -222,7 +224,14 @@ def render_mesh(vertices, colors=None, faces=None, T_WC=None, K=None, size=None,
 
     Known limitation: there is no clipping.  A face with a vertex at or behind `near`, at or beyond `far`, or more than
     16384 pixels from the image origin is dropped whole, so a surface that passes close by the camera gets holes.
-    Smooth shading only; V and F at most 2^31 - 1."""
+    Smooth shading only; V and F at most 2^31 - 1.
+
+    shading None draws the vertex colours as they are.  "headlight" draws them lit by a point light at the eye of T_WC
+    and "normals" draws the world-space vertex normals as colours: normals.shade_vertices(vertices, normals, colors,
+    T_WC, **shade_kw) into a temporary, which is rasterised in the place of `colors` (shade_kw: shade_vertices' light,
+    ambient, two_sided and albedo; colors=None there draws the constant albedo, shape without the photographs).
+    `normals` (float32 [V,3]) are normals.vertex_normals(vertices, faces) unless given: 3 + 1 + 4 launches, nothing
+    read back, and the temporaries are the only allocations."""
     if isinstance(vertices, (tuple, list)):
         if colors is not None:                                              # render_mesh(mesh, T_WC, K, size)
             T_WC, K, size = colors, (faces if faces is not None else K), (T_WC if T_WC is not None else size)
@@ -234,6 +243,12 @@ def render_mesh(vertices, colors=None, faces=None, T_WC=None, K=None, size=None,
     hv, wv, (fx, fy, cx, cy), near, far, bg = _view_args(size, K, near, far, background)
     if cull not in CULL:
         raise ValueError(f"cull must be one of {tuple(CULL)}, got {cull!r}")
+    if shading not in SHADING:
+        raise ValueError(f"shading must be one of {SHADING}, got {shading!r}")
+    if shading is None and (normals is not None or shade_kw):
+        raise ValueError("normals and shade_kw are for shading='headlight' or 'normals'")
+    if not set(shade_kw or {}) <= {"light", "ambient", "two_sided", "albedo", "colors"}:
+        raise ValueError(f"shade_kw holds shade_vertices' light, ambient, two_sided, albedo and colors, got {sorted(shade_kw)}")
     for t, dt, name in ((vertices, torch.float32, "vertices"), (colors, torch.uint8, "colors"), (faces, torch.int32, "faces")):
         if not isinstance(t, torch.Tensor) or t.dtype != dt or t.dim() != 2 or t.shape[1] != 3:
             got = f"{t.dtype} {tuple(t.shape)}" if isinstance(t, torch.Tensor) else type(t).__name__
@@ -248,6 +263,13 @@ def render_mesh(vertices, colors=None, faces=None, T_WC=None, K=None, size=None,
         raise ValueError(f"T_WC lives on {dev}, the mesh on {vertices.device}")
     ws_bytes = mesh_workspace_bytes(v, (hv, wv))
     out = _outputs(out, return_index, hv, wv, dev)
+    if shading is not None:
+        from . import normals as _normals                                    # normals imports export, as this module does
+        if normals is None:
+            normals = _normals.vertex_normals(vertices, faces)
+        kw = dict(colors=colors, T_WC=view, mode="normals" if shading == "normals" else "lambert")
+        kw.update(shade_kw or {})
+        colors = _normals.shade_vertices(vertices, normals, **kw)
     if workspace is None:
         workspace = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
     _check_workspace(workspace, ws_bytes)
@@ -298,8 +320,9 @@ class ViewRecorder:
     and the workspace are allocated once; per frame the host reads back the finished image and nothing else.
 
     surface "mesh" draws export.collect_mesh(keyframes, **mesh_kw) with render_mesh instead of the points with render_map
-    (render_kwargs are then render_mesh's).  The mesh is collected again for every recorded frame, which costs
-    collect_mesh's one host read of the vertex and face counts, and the workspace grows with the vertex count."""
+    (render_kwargs are then render_mesh's; shading="headlight" records lit views).  The mesh is collected again for every
+    recorded frame, which costs collect_mesh's one host read of the vertex and face counts, and the workspace grows with
+    the vertex count."""
 
     def __init__(self, directory, every: int = 1, camera="follow", size: Sequence[int] = (480, 640), K=None,
                  follow_distance: float = 1.0, follow_height: float = 0.25, surface: str = "points", mesh_kw=None,
@@ -317,6 +340,8 @@ class ViewRecorder:
             raise ValueError(f"camera must be 'follow', 'frame' or a pose, got {camera!r}")
         if "return_index" in render_kwargs or "out" in render_kwargs or "workspace" in render_kwargs:
             raise ValueError("the recorder owns its outputs: return_index / out / workspace cannot be passed")
+        if surface == "points" and any(render_kwargs.get(k) is not None for k in ("shading", "normals", "shade_kw")):
+            raise ValueError("shading is for surface='mesh': points carry no normals")
         self.directory = os.fspath(directory)
         os.makedirs(self.directory, exist_ok=True)
         self.every, self.camera, self.size, self.K = int(every), camera, (int(size[0]), int(size[1])), K

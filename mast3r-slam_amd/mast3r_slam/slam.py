@@ -310,11 +310,14 @@ class SLAM:
         moved to `size` (one host read of the per-keyframe focals).
 
         surface "mesh" draws self.mesh(**mesh_kw) and "fused" self.fused_mesh(**mesh_kw) with render.render_mesh (solid
-        surfaces; `kw` are then render_mesh's, and index is the face index); "points" is render_map as above."""
+        surfaces; `kw` are then render_mesh's, and index is the face index; shading="headlight" lights the surface from
+        the eye, normals.py); "points" is render_map as above."""
         if surface not in ("points", "mesh", "fused"):
             raise ValueError(f"render_view: surface must be 'points', 'mesh' or 'fused', got {surface!r}")
         if mesh_kw and surface == "points":
             raise ValueError("render_view: mesh_kw is for surface='mesh' or 'fused'")
+        if surface == "points" and any(kw.get(k) is not None for k in ("shading", "normals", "shade_kw")):
+            raise ValueError("render_view: shading is for surface='mesh' or 'fused': points carry no normals")
         frames = [kf for kf in self.keyframes._frames if kf.X_canon is not None]
         if T_WC is None:
             if not self.poses:
