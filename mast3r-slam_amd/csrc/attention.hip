@@ -9,7 +9,7 @@
 //     O^T = V^T . P^T    (MFMA A = V^T fragment, B = P fragment)  -> lane holds 16 d of its q
 // so the row max / row sum need only in-lane work plus two xor-shuffles, the rescale factor is
 // lane-local, and P goes from the S accumulators to the next MFMA's B operand with a bf16 pack
-// and no LDS round trip.  K and V tiles are staged global -> LDS by global_load_lds (double
+// and no LDS round trip.  K and V tiles are staged global -> LDS by LDS-DMA buffer loads (double
 // buffered); K fragments are ds_read_b128 from an XOR-swizzled image, V^T fragments come from
 // the row-major V image through ds_read_b64_tr_b16 (hardware transpose), conflict-free with a
 // chunk-pair swizzle.
@@ -22,7 +22,6 @@ namespace {
 using m3gemm::bf16x8;
 using m3gemm::f32x4;
 using m3gemm::bf16_t;
-using m3gemm::glds16;
 using m3gemm::pack16;
 using m3gemm::mfma16;
 using m3gemm::DT_BF16;
@@ -78,6 +77,11 @@ struct AttnArgs {
 #define M3_ATTN_EXP 0       // experiments (timing-only builds, wrong results): 4 = no exp2 (p = s), 5 = no exp2 and constant P (no packing)
 #endif
 constexpr float kDefer = 8.0f;
+// a * b - c with the product rounded before the subtraction
+__device__ __forceinline__ float mul_then_sub(float a, float b, float c) {
+#pragma clang fp contract(off)
+    return a * b - c;
+}
 // PVDT: 16-bit type of V in memory and of the probabilities P, i.e. of the O^T = V^T . P^T product.  PVDT = DT except in
 // the mixed mode of the fp16 trunk (DT = fp16, PVDT = bf16, M3_DT_F16_PVBF16): q and k - whose rounding is what an
 // 8-bit mantissa costs on peaked softmax rows (logits of 30-80: DESIGN.md section 4) - keep fp16's 11 bits, while P and V
@@ -114,26 +118,60 @@ k_attn(const AttnArgs a) {
     }
 
     // staging: thread t moves 16-byte slot t (row = t/8, chunk' = t%8) of each 4 KiB half tile
+    // The key loop is bound by VALU issue, so a tile's staging costs it no vector arithmetic: the tile's first row is a
+    // scalar base (one buffer descriptor per stream, rebuilt per tile on the scalar unit), a lane keeps ONE byte offset per
+    // stream for the whole kernel (row srow, its swizzled chunk), the second half tile is a scalar offset of 32 rows, and the
+    // LDS side (stage, half, wave) is scalar as well.  Only the last tile of a Tk that is no multiple of 64 clamps rows
+    // (per lane): a wave-uniform branch.
     const int srow = tid >> 3, sc = tid & 7;
     const int kch = sc ^ ((srow >> 1) & 7);                 // K image: chunk ^ ((row>>1)&7)
     const int vch = sc ^ (((srow >> 1) & 3) << 1);          // V image: chunk-pair ^ ((row>>1)&3)
-    auto stage = [&](int t, int buf) {
-        unsigned char *kb = lds + buf * 2 * kTileBytes, *vb = kb + kTileBytes;
+    const int nt = (a.Tk + KT - 1) / KT;
+    const unsigned row_bytes = (unsigned)a.kv_row_stride * 2u;
+    const unsigned k_lane = (unsigned)srow * row_bytes + kch * 16, v_lane = (unsigned)srow * row_bytes + vch * 16;
+    unsigned char *const lds_wave = lds + __builtin_amdgcn_readfirstlane(wave) * 1024;
+    auto stage = [&](int t, int stage_off) {                // stage_off: byte offset of the stage, wave-uniform
+        unsigned char *kb = lds_wave + stage_off, *vb = kb + kTileBytes;
+        const auto kr = m3gemm::stream_rsrc(Kp + (size_t)t * KT * a.kv_row_stride);
+        const auto vr = m3gemm::stream_rsrc(Vp + (size_t)t * KT * a.kv_row_stride);
+        if (t == nt - 1 && (a.Tk & (KT - 1))) {
+            asm volatile("; key tail: rows past Tk are staged from the last row" ::: "memory");
+            const int last = a.Tk - 1 - t * KT;
+            int sr = tid >> 3;
+            asm volatile("" : "+v"(sr));                    // computed here: nothing of this block lives across the loop
 #pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            int kr = t * KT + i * 32 + srow;
-            kr = kr < a.Tk ? kr : a.Tk - 1;
-            const size_t row = (size_t)kr * a.kv_row_stride;
-            glds16(Kp + row + kch * 8, kb + i * 4096 + wave * 1024);
-            glds16(Vp + row + vch * 8, vb + i * 4096 + wave * 1024);
+            for (int i = 0; i < 2; ++i) {
+                const int r = i * 32 + sr;
+                const unsigned row = (unsigned)(r < last ? r : last) * row_bytes;
+                m3gemm::blds16(kr, row + kch * 16, 0, kb + i * 4096);
+                m3gemm::blds16(vr, row + vch * 16, 0, vb + i * 4096);
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                m3gemm::blds16(kr, k_lane, i * 32 * row_bytes, kb + i * 4096);
+                m3gemm::blds16(vr, v_lane, i * 32 * row_bytes, vb + i * 4096);
+            }
         }
     };
 
     f32x4 o[QT][4];
     float m_run[QT], l_run[QT];
     bool ovf = false;                                             // MODE 2: sticky "a row sum left the safe range"
-    const int nt = (a.Tk + KT - 1) / KT;
     const int tq = lq >> 2, tp = lq & 3;
+    // Fragment addresses inside a stage: one per-lane byte offset per K k-step and per V^T d-tile (the swizzles are XORs, so
+    // these do not differ by constants); the key tile / k-step and the half are constants of the read instruction, and a
+    // tile adds its stage to each offset once.
+    //   K:   row r = kt*16 + lq, chunk (ks*4 + g) ^ ((r >> 1) & 7), and (r >> 1) & 7 = lq >> 1 for every kt
+    //   V^T: row (2kk + half)*16 + g*4 + tq, chunk (dt*2 + (tp >> 1)) ^ (((row >> 1) & 3) << 1), and (row >> 1) & 3 is that of g*4 + tq
+    int k_frag[2], v_frag[4];
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) k_frag[ks] = lq * 128 + ((ks * 4 + g) ^ (lq >> 1)) * 16;
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) {
+        const int row = g * 4 + tq;
+        v_frag[dt] = row * 128 + ((dt * 2 + (tp >> 1)) ^ (((row >> 1) & 3) << 1)) * 16 + (tp & 1) * 8;
+    }
 
     auto run = [&](auto mode_tag) {
         constexpr int MD = decltype(mode_tag)::value;
@@ -148,31 +186,44 @@ k_attn(const AttnArgs a) {
 #pragma unroll
             for (int dt = 0; dt < 4; ++dt) o[qt][dt] = f32x4{0.f, 0.f, 0.f, 0.f};
         }
-        stage(0, 0);
-        for (int t = 0; t < nt; ++t) {
-            const int buf = t & 1;
+        // S^T accumulator initialiser of the prescaled loops, {-m_ref x4} per query tile (log2 units): m_ref moves only after
+        // tile 0 and in the rare rescale blocks, so the splat is kept in registers and rebuilt there, not on every tile; it
+        // is also the only home of m_ref (m_run serves MODE 0 alone)
+        f32x4 c0v[QT];
+#pragma unroll
+        for (int qt = 0; qt < QT; ++qt) c0v[qt] = f32x4{0.f, 0.f, 0.f, 0.f};
+        auto reference = [&](int qt) { return -c0v[qt][0]; };
+        auto new_reference = [&](int qt, float m_ref) {
+            const float c0 = -m_ref;
+            c0v[qt] = f32x4{c0, c0, c0, c0};
+        };
+        // One key tile; FIRST (tile 0 of the prescaled loops) is a compile-time fact of the call site.
+        constexpr int kStage = 2 * kTileBytes;
+        auto tile = [&](const int t, auto first_c) {
+            constexpr bool FIRST = decltype(first_c)::value;
+            const int flip = (M3_ATTN_ABL & 4) ? 0 : (t & 1) * kStage;      // byte offset of tile t's stage
             // ONE barrier per tile: it publishes tile t (every wave waited for its own share) and, because a wave
             // reaches it only after its last fragment read of tile t-1, it also frees that tile's stage - which is
             // where tile t+1 is staged right behind it, with the whole of tile t's arithmetic to land.
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             m3gemm::lds_barrier();
-            if (t + 1 < nt && !(M3_ATTN_ABL & 4)) stage(t + 1, buf ^ 1);
-            const unsigned char *Ks = lds + ((M3_ATTN_ABL & 4) ? 0 : buf) * 2 * kTileBytes, *Vs = Ks + kTileBytes;
+            if (t + 1 < nt && !(M3_ATTN_ABL & 4)) stage(t + 1, flip ^ kStage);
+            const unsigned char *Ks = lds + flip, *Vs = Ks + kTileBytes;
 
-            if constexpr (MD == 2) {
+            if constexpr (MD == 2 && !FIRST) {
                 // range keeper for the row sums of the tiles so far (tested here, a tile late, so that the test does
                 // not wait for the matrix core); per query, identical in its 4 lanes
                 bool big = false;
 #pragma unroll
                 for (int qt = 0; qt < QT; ++qt) big |= l_acc[qt][0] > 0x1p60f;
-                if (t > 0 && __any(big)) {
+                if (__any(big)) {
                     asm volatile("; rare path" ::: "memory");
 #pragma unroll
                     for (int qt = 0; qt < QT; ++qt) {
                         const bool hit = l_acc[qt][0] > 0x1p60f;
                         ovf |= !(l_acc[qt][0] <= 0x1p100f);          // sticky: o may have overflowed where l has not
                         const float alpha = hit ? 0x1p-64f : 1.0f;
-                        m_run[qt] += hit ? 64.0f : 0.0f;
+                        new_reference(qt, reference(qt) + (hit ? 64.0f : 0.0f));
 #pragma unroll
                         for (int r = 0; r < 4; ++r) l_acc[qt][r] *= alpha;
 #pragma unroll
@@ -185,21 +236,23 @@ k_attn(const AttnArgs a) {
 
             // ---- S^T = K . Q^T : s[qt][kt] holds keys kt*16 + g*4 + r of query lq ------------------
             f32x4 s[QT][4];
+            if constexpr (MD >= 1 && !FIRST) {
+                // one register home for the initialiser on both sides of the rare blocks (without this the register
+                // allocator keeps a second copy and moves eight registers per tile)
 #pragma unroll
-            for (int qt = 0; qt < QT; ++qt) {
-                const float c0 = (MD >= 1 && t > 0) ? -m_run[qt] : 0.f;          // prescaled: m_run holds m_ref (log2 units)
-#pragma unroll
-                for (int kt = 0; kt < 4; ++kt) s[qt][kt] = f32x4{c0, c0, c0, c0};
+                for (int qt = 0; qt < QT; ++qt) asm("" : "+v"(c0v[qt]));
             }
+#pragma unroll
+            for (int qt = 0; qt < QT; ++qt)
+#pragma unroll
+                for (int kt = 0; kt < 4; ++kt) s[qt][kt] = c0v[qt];             // zero in tile 0 and in MODE 0
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
                 for (int kt = 0; kt < 4; ++kt) {
-                    const int r = kt * 16 + lq;
-                    const int c = (ks * 4 + g) ^ ((r >> 1) & 7);
                     bf16x8 kf;
-                    if ((M3_ATTN_ABL & 1) && t > 0) { kf = qf[0][ks]; asm volatile("" : "+v"(kf)); }
-                    else kf = *reinterpret_cast<const bf16x8 *>(Ks + r * 128 + c * 16);
+                    if ((M3_ATTN_ABL & 1) && !FIRST && t > 0) { kf = qf[0][ks]; asm volatile("" : "+v"(kf)); }
+                    else kf = *reinterpret_cast<const bf16x8 *>(Ks + kt * 2048 + k_frag[ks]);
 #pragma unroll
                     for (int qt = 0; qt < QT; ++qt)
                         s[qt][kt] = mfma16<DT>(kf, qf[qt][ks], s[qt][kt]);
@@ -243,9 +296,9 @@ k_attn(const AttnArgs a) {
             if constexpr (MD == 2) {
 #pragma unroll
                 for (int qt = 0; qt < QT; ++qt) {
-                    if (t == 0) {                                            // the first tile's true maximum is the reference
+                    if constexpr (FIRST) {                                   // the first tile's true maximum is the reference
                         const float mx = tile_max(qt);
-                        m_run[qt] = mx;
+                        new_reference(qt, mx);
 #pragma unroll
                         for (int kt = 0; kt < 4; ++kt)
 #pragma unroll
@@ -269,8 +322,8 @@ k_attn(const AttnArgs a) {
 #pragma unroll
                 for (int qt = 0; qt < QT; ++qt) {
                     const float mx = tile_max(qt);
-                    if (t == 0) {                                            // first tile: the true maximum becomes the reference
-                        m_run[qt] = mx;
+                    if (FIRST) {                                             // first tile: the true maximum becomes the reference
+                        new_reference(qt, mx);
 #pragma unroll
                         for (int kt = 0; kt < 4; ++kt)
 #pragma unroll
@@ -279,7 +332,7 @@ k_attn(const AttnArgs a) {
                         asm volatile("; rare path: keep it a branch (if-converted, its 32 subtracts + selects ran on every tile)" ::: "memory");
                         const float delta = fmaxf(mx, 0.f);
                         const float alpha = __builtin_amdgcn_exp2f(-delta);
-                        m_run[qt] += delta;
+                        new_reference(qt, reference(qt) + delta);
                         l_run[qt] *= alpha;
 #pragma unroll
                         for (int dt = 0; dt < 4; ++dt)
@@ -320,7 +373,13 @@ k_attn(const AttnArgs a) {
                     for (int kt = 0; kt < 4; ++kt)
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
-                            const float p = __builtin_amdgcn_exp2f(s[qt][kt][r] * a.scale_log2e - mb);
+                            // The rounding of the exponent is spelled out, not left to contraction: fused everywhere but in
+                            // the tile's last score, whose product is rounded on its own.  That is what every build so far
+                            // computed (the vectoriser paired that product with mb's, which kept it from fusing) and what
+                            // other shapes of this loop would otherwise change in the last bit.
+                            const float e = (kt == 3 && r == 3) ? mul_then_sub(s[qt][kt][r], a.scale_log2e, mb)
+                                                                : __builtin_fmaf(s[qt][kt][r], a.scale_log2e, -mb);
+                            const float p = __builtin_amdgcn_exp2f(e);
                             s[qt][kt][r] = p;
                             rs += p;
                         }
@@ -342,13 +401,11 @@ k_attn(const AttnArgs a) {
 #pragma unroll
                 for (int dt = 0; dt < 4; ++dt) {
                     union { bf16x4 h[2]; bf16x8 v; } vf;
-                    if ((M3_ATTN_ABL & 2) && t > 0) { vf.v = qf[0][kk]; asm volatile("" : "+v"(vf.v)); }
+                    if ((M3_ATTN_ABL & 2) && !FIRST && t > 0) { vf.v = qf[0][kk]; asm volatile("" : "+v"(vf.v)); }
                     else
 #pragma unroll
                     for (int half = 0; half < 2; ++half) {
-                        const int row = (2 * kk + half) * 16 + g * 4 + tq;
-                        const int ch = (dt * 2 + (tp >> 1)) ^ (((row >> 1) & 3) << 1);
-                        const unsigned char *p = Vs + row * 128 + ch * 16 + (tp & 1) * 8;
+                        const unsigned char *p = Vs + (2 * kk + half) * 2048 + v_frag[dt];
                         vf.h[half] = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
                             (__attribute__((address_space(3))) bf16x4 *)p);
                     }
@@ -361,7 +418,12 @@ k_attn(const AttnArgs a) {
                     for (int qt = 0; qt < QT; ++qt) l_acc[qt] = mfma16<PVDT>(ones, pf[qt][kk], l_acc[qt]);
                 }
             }
-        }
+        };
+        stage(0, 0);
+        // the prescaled loops set their reference in tile 0 and test nothing before it: a body of its own; MODE 0 treats
+        // every tile alike and keeps one loop
+        if constexpr (MD >= 1) tile(0, std::true_type{});
+        for (int t = (MD >= 1 ? 1 : 0); t < nt; ++t) tile(t, std::false_type{});
         m3gemm::lds_barrier();                      // the stages are reused right after the loop (flag word / recomputation)
         if constexpr (MD == 2 && M3_ATTN_EXP != 1) {
 #pragma unroll
@@ -464,6 +526,7 @@ static int attention_launch(const void *Q, const void *K, const void *V, void *O
     // dtype 2 = M3_DT_F16_PVBF16 (prescaled entry only): q, k, O fp16; V holds bf16, P is bf16
     M3_REQUIRE((dtype == DT_BF16 || dtype == DT_F16 || (dtype == 2 && pre)) && ((int64_t)Tq / 64 + 1) * heads * nbatch < (1ll << 31));
     M3_REQUIRE(q_row_stride % 8 == 0 && kv_row_stride % 8 == 0 && o_row_stride % 4 == 0);
+    M3_REQUIRE(kv_row_stride >= 0 && kv_row_stride < (1 << 23));      // staging: 64 rows of K / V within a 32-bit byte offset
     M3_REQUIRE(kv_batch_shift >= 0);
     AttnArgs a;
     a.Q = (const bf16_t *)Q; a.K = (const bf16_t *)K; a.V = (const bf16_t *)V; a.O = (bf16_t *)O;

@@ -85,6 +85,17 @@ __device__ __forceinline__ void glds16(const void *g, void *lds_wave_base) {
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) unsigned *)g,
                                      (__attribute__((address_space(3))) unsigned *)lds_wave_base, 16, 0, 0);
 }
+// The same LDS-DMA through a buffer descriptor: the address is (descriptor base, scalar) + wave_off (scalar) + lane_off (one
+// 32-bit VGPR), so a stream that advances by a wave-uniform stride keeps ONE per-lane offset for the whole kernel and its
+// advance is scalar arithmetic - no 64-bit pointer per piece on the VALU.  Build the descriptor and lds_wave_base from
+// wave-uniform values the compiler can prove uniform (kernel arguments, blockIdx, readfirstlane) or it wraps every load in a
+// readfirstlane loop.  No range check (the record count is the maximum): offsets must stay below 2^31.
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t stream_rsrc(const void *base) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), 0, 0x7ffffff0, 0x00020000);
+}
+__device__ __forceinline__ void blds16(__amdgpu_buffer_rsrc_t r, unsigned lane_off, unsigned wave_off, void *lds_wave_base) {
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void *)lds_wave_base, 16, lane_off, wave_off, 0, 0);
+}
 
 // Workgroup barrier that LDS traffic cannot cross.  For LLVM `__builtin_amdgcn_s_barrier()` touches no memory, so
 // the scheduler is free to move ds_reads - and the s_waitcnt that retires them - across it: in the round-1 build the
