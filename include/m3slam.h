@@ -822,6 +822,86 @@ int m3_mesh_shade(const float *vertices, const float *normals, const uint8_t *co
                   int light, float lx, float ly, float lz, float ambient, int two_sided, int mode, int albedo_r,
                   int albedo_g, int albedo_b, uint8_t *out, void *stream);
 
+/* ------------------------------------------------------------- mesh simplify */
+
+/* Mesh simplification by vertex clustering.  Host side: mast3r_slam/simplify.py.  The rule is
+ * Open3D's simplify_vertex_clustering with the average made exact: one output vertex per occupied voxel, faces
+ * rewritten, collapsed and repeated faces removed.  This text is the contract, and tests/simplify_twin.py restates it
+ * in numpy; device and twin agree byte for byte.  Every float64 operation below is rounded on its own (no fused
+ * multiply-add).
+ *
+ * Inputs: vertices float32 [V,3], colors uint8 [V,3], faces int32 [F,3] (each entry a row of the vertex arrays), and
+ * voxel, the fp32 argument voxel_size (finite, > 0) converted to float64.  0 <= V, F <= 2^31 - 1.
+ *
+ * Cell of a vertex.  Per axis, for the coordinate x:
+ *   t    = (double)x / voxel                                          (one float64 divide)
+ *   cell = floor(t)
+ *   q    = llrint((t - cell) * 2^24)                                  (round to nearest even; 0 ... 2^24)
+ * A vertex is out of range when on any axis x is not finite or |cell| >= 2^20 (the limit of the point-cloud voxel
+ * table).  An out-of-range vertex joins no cluster.  Such vertices are counted; they are not an error.
+ *
+ * Clusters.  The in-range vertices with the same cell triple form a cluster.
+ *   - Its leader is the smallest input row in it.
+ *   - Clusters are output in ascending leader row: in the order of first appearance in the input.
+ *   - Every cluster is output, whether or not a kept face names it.
+ *
+ * Position and colour of a cluster of n vertices.
+ *   - n = 1: the vertex's own bits and colour.  So a voxel finer than the mesh returns the vertex and colour arrays
+ *     byte for byte.
+ *   - n > 1, per axis: S = the integer sum of the members' q (below 2^55).
+ *       mean = (double)S / ((double)n * 2^24)
+ *       out  = (float)(((double)cell + mean) * voxel)
+ *   - n > 1, per channel: C = the integer sum of the members' values; out = (2 C + n) / (2 n) in integer arithmetic,
+ *     the rounded mean.
+ *
+ * Faces.
+ *   - A face that names a row outside [0, V) is invalid.  Invalid faces are counted and never kept; the host raises
+ *     ValueError when the count it reads back is non-zero.
+ *   - Every other face is mapped to the three clusters of its rows.  It is dropped when one of its rows is out of
+ *     range, and when two of its three clusters are the same.
+ *   - The key of a remaining face is its triple of cluster output rows, rotated so that the smallest comes first.  A
+ *     rotation keeps the orientation: two faces over the same three clusters with opposite winding have different
+ *     keys.
+ *   - Of the faces with the same key only the one with the smallest input row is kept.
+ *   - Kept faces come out in ascending input row, written as their key.
+ *
+ * Outputs: vertices float32 [V2,3], colors uint8 [V2,3], faces int32 [F2,3]; optionally cluster_of int64 [V] (the
+ * output row of every input vertex, -1 when it is out of range) and face_rows int64 [F2] (the input row of every kept
+ * face).  Two calls give identical bytes, and so do two orders of the threads.
+ *
+ * Left out: quadric placement and any error-driven decimation, a target face count, normal-aware clustering, and
+ * carrying vertex normals through (m3_mesh_normals recomputes them).
+ *
+ * m3_mesh_simplify_count: six launches (clear the tables and the header with a kernel; one thread per vertex claims
+ * the slot of its cell in an open-addressing table with a 64-bit compare-and-swap, lowers the slot's leader row with
+ * atomicMin and adds q, the colour and 1 to the slot's integer sums; one thread per vertex reads its leader, leaders
+ * per tile of 256 rows; one thread per face claims the slot of its key in a second table that holds a face row per
+ * slot - an occupied slot is compared by rebuilding the occupant's key, and an equal key lowers the row with
+ * atomicMin; winning faces per tile; one exclusive scan of both counts).  Afterwards ws int32 [0] = V2, [1] = F2,
+ * [2] = the out-of-range vertices, [3] = the invalid faces: the host reads them in one copy.  vertices and colors may
+ * be NULL when V = 0, faces when F = 0.
+ * m3_mesh_simplify_scatter, with the same ws, mesh and V2, F2 as read back: two launches (leaders write their cluster
+ * and leave their output row in ws; winning faces are written as their key, and cluster_of for every input vertex).
+ * voxel_size is the one the count left in ws.  vertices_out and colors_out may be NULL when V2 = 0, faces_out when
+ * F2 = 0; cluster_of_out and face_rows_out may be NULL.
+ * m3_mesh_simplify_launches() = 8 = 6 + 2, whatever V, F and the content are.  No allocation and no host
+ * synchronisation: count and scatter can each be captured into a graph.  The atomics are integer and commute, and
+ * output rows are tile offset + rank, never an atomic counter.
+ * ws: m3_mesh_simplify_ws_bytes(V, F) = 64 + pad(4 * max(1, ceil(V / 256))) + pad(4 * max(1, ceil(F / 256)))
+ * + 3 * pad(4 * V) + pad(4 * F) + 64 * SV + 4 * SF bytes, pad rounding up to 16, SV and SF the smallest powers of two
+ * that are >= 1024 and >= 2 V, 2 F (0 = unsupported: 0 <= V, F <= 2^31 - 1), 16-byte aligned, contents ignored on entry
+ * of count.
+ * M3_ERR_INVALID_ARG, before any HIP call, for NULL pointers where a size is non-zero, negative sizes, a voxel_size that
+ * is not finite and > 0, V2 outside 0 ... V, F2 outside 0 ... F, pointers not aligned to their element, a misaligned
+ * or short ws. */
+int64_t m3_mesh_simplify_ws_bytes(int64_t V, int64_t F);
+int m3_mesh_simplify_launches(void);
+int m3_mesh_simplify_count(const float *vertices, const uint8_t *colors, const int32_t *faces, int64_t V, int64_t F,
+                           float voxel_size, void *ws, int64_t ws_bytes, void *stream);
+int m3_mesh_simplify_scatter(const float *vertices, const uint8_t *colors, const int32_t *faces, int64_t V, int64_t F,
+                             void *ws, int64_t ws_bytes, int64_t V2, int64_t F2, float *vertices_out, uint8_t *colors_out,
+                             int32_t *faces_out, int64_t *cluster_of_out, int64_t *face_rows_out, void *stream);
+
 /* ---------------------------------------------------------- camera intrinsics */
 
 /* Focal length of every keyframe from its own pointmap.  Host side: mast3r_slam/intrinsics.py.

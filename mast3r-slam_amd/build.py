@@ -49,6 +49,8 @@ PER_FILE = {
     # face normal, its quantisation, the float64 finish and the shading are separately rounded operations
     # (tests/normals_twin.py restates them)
     "mesh_normals.hip": ["-ffp-contract=off"],
+    # cell, quantisation and the float64 finish of a cluster mean are separately rounded operations (tests/simplify_twin.py)
+    "mesh_simplify.hip": ["-ffp-contract=off"],
 }
 
 
