@@ -99,29 +99,50 @@ k_conv_tail(const TailArgs ain) {
     const int oy0 = ty * TH, ox0 = tx * TW;
     const bf16_t *img = a.X + (size_t)b * a.IH * a.IW * CIN;
 
-    // weights of (tap, input half) -> stage buf: 128 rows x 8 chunks' = 1024 slots, 2 per thread
-    auto stage_w = [&](int tap, int half, int buf) {
-        unsigned char *base = wst + buf * kWStage;
+    // weights of (tap, input half) -> stage buf: 128 rows x 8 chunks' = 1024 slots, 2 per thread.  Staged through a buffer
+    // descriptor on this workgroup's weight rows (blds16, gemm_common.h): a lane keeps its two row / swizzled-chunk byte
+    // offsets for the whole kernel, (tap, half) is the load's scalar offset and the LDS target is scalar - the tap loop
+    // carries no 64-bit address arithmetic.  Same addresses as a.Wc + (row * 9 + tap) * CIN + (half * 8 + chunk) * 8.
+    const auto w_rsrc = stream_rsrc(a.Wc);
+    const int wave_u = __builtin_amdgcn_readfirstlane(wave);
+    unsigned char *const lds_wave = lds + wave_u * 1024;
+    unsigned w_lane[2];
 #pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int slot = i * kThreads + tid;
-            const int row = slot >> 3, cp = slot & 7;
-            const int c = half * 8 + (cp ^ ((row >> 1) & 7));
-            glds16(a.Wc + ((size_t)row * 9 + tap) * CIN + c * 8, base + i * (kThreads * 16) + wave * 1024);
-        }
+    for (int i = 0; i < 2; ++i) {
+        const int slot = i * kThreads + tid;
+        const int row = slot >> 3, cp = slot & 7;
+        w_lane[i] = (unsigned)row * (9 * CIN * 2) + ((cp ^ ((row >> 1) & 7)) << 4);
+    }
+    auto stage_w = [&](int tap, int half, int buf) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+            blds16(w_rsrc, w_lane[i], (unsigned)(tap * CIN + half * 64) * 2u,
+                   lds_wave + kHaloBytes + buf * kWStage + i * (kThreads * 16));
     };
     // x2 bilinear (align_corners): the 18 x 34 halo of the H x W image blends an (at most) 11 x 19 input patch
     const float sy = UPS && a.H > 1 ? (float)(a.IH - 1) / (float)(a.H - 1) : 0.f;
     const float sx = UPS && a.W > 1 ? (float)(a.IW - 1) / (float)(a.W - 1) : 0.f;
     const int py0 = (int)((float)max(oy0 - 1, 0) * sy), px0 = (int)((float)max(ox0 - 1, 0) * sx);
-    auto stage_patch = [&](int half) {          // 209 pixels x 8 chunks = 1672 slots -> 27 wave-instructions (padded)
-        for (int wi = wave; wi < (PH * PW * 8 + 63) / 64; wi += kThreads / 64) {
-            int slot = wi * 64 + lane;
+    // 209 pixels x 8 chunks = 1672 slots -> 27 wave-instructions (padded), up to 4 per wave.  The pixel a lane fetches does
+    // not depend on the slice: its byte offset inside the image is computed once, the slice is the load's scalar offset
+    constexpr int kPatchIss = (PH * PW * 8 + 63) / 64, kPatchPerWave = (kPatchIss + 7) / 8;
+    const auto x_rsrc = stream_rsrc(img);
+    unsigned p_lane[UPS ? kPatchPerWave : 1];
+    if (UPS) {
+#pragma unroll
+        for (int j = 0; j < kPatchPerWave; ++j) {
+            int slot = (wave + 8 * j) * 64 + lane;
             slot = slot < PH * PW * 8 ? slot : PH * PW * 8 - 1;
             const int pp = slot >> 3, c = slot & 7;
             const int y = min(py0 + pp / PW, a.IH - 1), x = min(px0 + pp % PW, a.IW - 1);
-            glds16(img + ((size_t)y * a.IW + x) * CIN + (half * 8 + c) * 8, patch + wi * 1024);
+            p_lane[j] = (unsigned)((y * a.IW + x) * CIN + c * 8) * 2u;
         }
+    }
+    auto stage_patch = [&](int half) {
+#pragma unroll
+        for (int j = 0; j < kPatchPerWave; ++j)
+            if (wave_u + 8 * j < kPatchIss)
+                blds16(x_rsrc, p_lane[j], (unsigned)half * 128u, lds_wave + kHaloBytes + 2 * kWStage + j * 8192);
     };
     auto stage_halo_direct = [&](int half) {    // 612 pixels x 8 chunks' = 4896 slots = 76.5 wave-instructions
         for (int wi = wave; wi < (kHaloPix * 8 + 63) / 64; wi += kThreads / 64) {
@@ -484,6 +505,8 @@ static int dpt_tail_launch(const void *X, const void *Wc, const float *bias, con
     M3_REQUIRE(groups == 1 || ((!tail || (W42 && b42)) && (bias == nullptr) == (bias2 == nullptr)));
     M3_REQUIRE((dtype == DT_BF16 || dtype == DT_F16) && (!upsample || (H % 2 == 0 && W % 2 == 0)));
     M3_REQUIRE((int64_t)groups * B * H * W < (1ll << 31));
+    // patch staging addresses an input image through 32-bit byte offsets from its first pixel (stream_rsrc: below 2^31)
+    M3_REQUIRE(!upsample || (int64_t)(H / 2) * (W / 2) * cin * 2 < (1ll << 31) - 16);
     M3_REQUIRE(reinterpret_cast<uintptr_t>(X) % 16 == 0 && reinterpret_cast<uintptr_t>(Wc) % 16 == 0 &&
                reinterpret_cast<uintptr_t>(Y) % 16 == 0 && reinterpret_cast<uintptr_t>(R) % 16 == 0);
     TailArgs a;

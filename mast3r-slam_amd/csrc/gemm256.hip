@@ -55,24 +55,33 @@ k_gemm256(const GemmArgs gin) {
     const int tm = first_m + in_band % gsz, tn = in_band / gsz;
     const int m0 = tm * BM, n0 = tn * BN;
 
-    // staging: thread t moves 16-byte slot t of each 8 KiB issue (64 rows x 128 B); 4 issues per operand
+    // staging: thread t moves 16-byte slot t of each 8 KiB issue (64 rows x 128 B); 4 issues per operand.
+    // Dense launches stage through one buffer descriptor per operand, based at the tile's first row (wave-uniform): a lane
+    // keeps ONE 32-bit tile-relative byte offset per issue for the whole kernel, the K advance is the load's scalar offset
+    // and the LDS target is scalar too (blds16, gemm_common.h) - the K loop carries no address arithmetic on the VALU.
+    // Same rows, same clamp, same addresses as per-lane pointers.  The conv form keeps pointers: a lane switches to the
+    // zero page for taps outside the image.
     const int srow = tid >> 3, sch = (tid & 7) ^ ((srow >> 1) & 7);
-    const bf16_t *a_src[4];
     const bf16_t *w_src[WISS];
+    unsigned a_lane[4], w_lane[WISS];
     int a_oy[4], a_ox[4];
     const bf16_t *a_img[4];
+    const auto a_rsrc = stream_rsrc(g.A + (MODE == 0 ? (size_t)m0 * g.K : 0));
+    const auto w_rsrc = stream_rsrc(g.W + (MODE == 0 ? (size_t)n0 * g.K : 0));
+    unsigned char *const lds_wave = lds + __builtin_amdgcn_readfirstlane(wave) * 1024;
 #pragma unroll
     for (int i = 0; i < WISS; ++i) {
         int n = n0 + i * 64 + srow;
         n = n < g.N ? n : g.N - 1;
-        w_src[i] = g.W + (size_t)n * g.K + sch * 8;
+        if (MODE == 0) w_lane[i] = (unsigned)(n - n0) * (unsigned)g.K * 2u + sch * 16;
+        else w_src[i] = g.W + (size_t)n * g.K + sch * 8;
     }
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         int m = m0 + i * 64 + srow;
         m = m < g.M ? m : g.M - 1;
         if (MODE == 0) {
-            a_src[i] = g.A + (size_t)m * g.K + sch * 8;
+            a_lane[i] = (unsigned)(m - m0) * (unsigned)g.K * 2u + sch * 16;
         } else {
             const int pix = g.OH * g.OW;
             const int b = m / pix, rem = m - b * pix;
@@ -94,23 +103,25 @@ k_gemm256(const GemmArgs gin) {
         }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const void *src;
             if (MODE == 0) {
-                src = a_src[i] + (size_t)kt * BK;
+                blds16(a_rsrc, a_lane[i], (unsigned)kt * (BK * 2), lds_wave + buf * kStageBytes + i * 8192);
             } else {
                 const int iy = a_oy[i] + ky, ix = a_ox[i] + kx;
                 const bool in = (iy >= 0) && (iy < g.H) && (ix >= 0) && (ix < g.Wd);
-                src = in ? (const void *)(a_img[i] + ((size_t)iy * g.Wd + ix) * g.Cin + c0) : (const void *)g.zero16;
+                const void *src = in ? (const void *)(a_img[i] + ((size_t)iy * g.Wd + ix) * g.Cin + c0) : (const void *)g.zero16;
+                glds16(src, base + i * 8192 + wave * 1024);
             }
-            glds16(src, base + i * 8192 + wave * 1024);
         }
     };
     auto stage_w = [&](int kt, int buf) {
         unsigned char *base = lds + buf * kStageBytes;
-        const size_t koff = MODE == 1 ? conv_k_offset(kt, g.Cin) : (size_t)kt * BK;
 #pragma unroll
-        for (int i = 0; i < WISS; ++i)
-            glds16(w_src[i] + koff, base + BM * BK * 2 + i * 8192 + wave * 1024);
+        for (int i = 0; i < WISS; ++i) {
+            if (MODE == 0)
+                blds16(w_rsrc, w_lane[i], (unsigned)kt * (BK * 2), lds_wave + buf * kStageBytes + BM * BK * 2 + i * 8192);
+            else
+                glds16(w_src[i] + conv_k_offset(kt, g.Cin), base + BM * BK * 2 + i * 8192 + wave * 1024);
+        }
     };
     auto stage = [&](int kt, int buf) { stage_a(kt, buf); stage_w(kt, buf); };
 
@@ -242,6 +253,8 @@ template <int MODE, int BN, int DT>
 int launch256(const GemmArgs &a, int epi, hipStream_t st) {
     constexpr int kLdsBytes = 2 * (BM + BN) * BK * 2 + BM * 8;    // 128 KiB / 112 KiB of stages + the LayerNorm-fold row table
     const int tiles = m3_cdiv(a.M, BM) * m3_cdiv(a.N, BN);
+    // dense staging: 32-bit byte offsets from the tile's first row (256 rows of K, plus the K advance) stay below 2^31
+    if (MODE == 0) M3_REQUIRE((long long)(BM + 1) * a.K * 2 < (1ll << 31) - 16);
     dim3 grid(tiles, a.groups > 1 ? a.groups : 1), blk(kThreads);
 #define M3_L(E)                                                                                              \
     case E: {                                                                                                \
