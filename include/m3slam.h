@@ -902,6 +902,88 @@ int m3_mesh_simplify_scatter(const float *vertices, const uint8_t *colors, const
                              void *ws, int64_t ws_bytes, int64_t V2, int64_t F2, float *vertices_out, uint8_t *colors_out,
                              int32_t *faces_out, int64_t *cluster_of_out, int64_t *face_rows_out, void *stream);
 
+/* --------------------------------------------------------------- mesh smooth */
+
+/* Edge topology of a triangle mesh, and Laplacian / Taubin smoothing on it.  Host side:
+ * mast3r_slam/smooth.py.  The filters are Open3D's filter_smooth_laplacian and filter_smooth_taubin (uniform weights)
+ * with the order of every sum fixed.  This text is the contract, and tests/smooth_twin.py restates it in numpy; device
+ * and twin agree byte for byte.  Every float64 operation below is rounded on its own (no fused multiply-add).
+ *
+ * Inputs: vertices float32 [V,3], faces int32 [F,3] (each entry a row of the vertex array).
+ * 0 <= V <= 2^31 - 1 and 0 <= F <= (2^31 - 1) / 6: the adjacency holds at most 6 F entries, indexed in int32.
+ *
+ * Edges.
+ *   - Face f with rows (a, b, c) contributes the undirected pairs {a,b}, {b,c}, {c,a}.
+ *   - A pair with two equal rows is no edge.
+ *   - A face that names a row outside [0, V) is invalid: it contributes nothing and is counted.
+ *   - An edge is the pair (lo, hi), lo < hi, by row and never by position.
+ *   - faces_of(edge) is the number of face corners that contribute it.  A repeated face counts every time, and
+ *     either winding counts.
+ *   - Boundary edge: faces_of == 1.  Non-manifold edge: faces_of > 2.
+ *   - A boundary vertex lies on at least one boundary edge.
+ *
+ * Adjacency.
+ *   - row(v) is the other ends of the unique edges at v, in ascending order; degree[v] is its length.
+ *   - This is a CSR: off int32 [V + 1], nbr int32 [2 E], E the number of edges.
+ *   - It is canonical: it depends on the set of edges, not on the order of the faces or of the threads.
+ *
+ * One pass with weight w.  w is an fp32 argument converted to float64.  Every vertex is computed from the positions
+ * before the pass; p_v is the position of v before the pass.
+ *   - If v is pinned, or a coordinate of p_v is not finite, the output is p_v bit for bit.
+ *   - Otherwise walk row(v) in ascending order.  For every neighbour j whose three coordinates are finite (tested on
+ *     the positions before this pass): s += (double)p_j per axis, n += 1.  s starts at 0.0.
+ *   - If n == 0, the output is p_v bit for bit.
+ *   - Otherwise, per axis: m = s / (double)n, out = (float)((double)p_v + w * (m - (double)p_v)).
+ *
+ * Methods.
+ *   - laplacian (method 0): `iterations` passes with lam.
+ *   - taubin (method 1): `iterations` times (a pass with lam, then a pass with mu).
+ *   - 0 < lam <= 1; mu is any finite value (Open3D's defaults are lam = 0.5, mu = -0.53).  iterations >= 0;
+ *     iterations = 0 returns the input's bytes.
+ *   - Pinned: the boundary vertices when fix_boundary, united with the rows where the caller's mask is non-zero.  The
+ *     pinned set is the same for every pass.
+ *
+ * Left out: cotangent and other geometric weights, smoothing of colours or normals (m3_mesh_normals recomputes
+ * them), feature-preserving or bilateral filters, hole filling.
+ *
+ * m3_mesh_topology_build: seven launches (clear the table, the degrees and the header with a kernel; one thread per
+ * face claims, for each of its three pairs, the slot of the key lo << 31 | hi in an open-addressing table with a
+ * 64-bit compare-and-swap and a probe loop bounded by the table size, adds 1 to the slot's face count, and - only the
+ * thread whose compare-and-swap claimed the slot - adds 1 to degree[lo] and degree[hi]; the exclusive scan of the
+ * degrees in three: sums per tile of 256 rows, one scan of the tiles, tile offset + rank; one thread per face again -
+ * the corner that claimed a slot writes each end into the other's row at a cursor taken with an integer add, marked
+ * when the slot's count is 1, and adds to the header's counts; every row is sorted ascending - a thread per row up to 32 entries, the lanes of a wave together
+ * for a longer one - and the boundary flag of its vertex is the or of its marks).  Afterwards ws int32 [0] = 2 E,
+ * [1] = the boundary edges, [2] = the non-manifold edges, [3] = the invalid faces: the host reads them in one 16-byte
+ * copy.  faces may be NULL when F = 0.
+ * m3_mesh_smooth_launches() = 7: the launches of m3_mesh_topology_build, whatever V, F and the content are.
+ * m3_mesh_topology_read: one launch; degree_out int32 [V], boundary_out uint8 [V] (0 or 1) from a built ws.
+ * m3_mesh_topology_edges, with E as read back: three launches (neighbours above v per tile of 256 rows; one scan;
+ * scatter at tile offset + rank).  edges_out int32 [E,2] in lexicographic (lo, hi) order, edge_faces_out int32 [E] =
+ * faces_of, looked up in the table.
+ * m3_mesh_smooth_passes, on a ws built from the same V and faces: one launch per pass (iterations, or 2 * iterations
+ * for taubin), one thread per vertex; iterations = 0 is one copy launch.  Between passes the positions live in ws as
+ * 16 bytes per vertex (x, y, z and a word that holds the finite and the pinned flag); the first pass reads vertices,
+ * the last writes out, and vertices is never written.  pinned: uint8 [V] or NULL.  out must not be vertices.
+ * No entry point allocates or synchronises with the host: each can be captured into a graph.  The atomics are integer
+ * and commute (compare-and-swap to claim, add); no thread waits for another.  Which slot an edge lands in and
+ * where in its row a neighbour first lands depend on the arrival order; nothing after the sort does.
+ * ws: m3_mesh_smooth_ws_bytes(V, F) = 64 + pad(4 * ceil((V + 1) / 256)) + pad(4 * (V + 2)) + 12 * S + pad(V)
+ * + pad(12 * F) + 2 * pad(24 * F) + 32 * V bytes, pad rounding up to 16, S the smallest power of two that is >= 1024 and >= 6 F (the
+ * table stays at most half full) (0 = unsupported V or F), 16-byte aligned, contents ignored on entry of build.
+ * M3_ERR_INVALID_ARG, before any HIP call, for NULL pointers where a size is non-zero, sizes out of range, a
+ * misaligned or (build, passes) short ws, pointers not aligned to 4 bytes, E outside 0 ... 3 F, fix_boundary other
+ * than 0 or 1, method other than 0 or 1, iterations < 0, lam outside (0, 1] or NaN, a mu that is not finite, and
+ * out == vertices. */
+int64_t m3_mesh_smooth_ws_bytes(int64_t V, int64_t F);
+int m3_mesh_smooth_launches(void);
+int m3_mesh_topology_build(const int32_t *faces, int64_t V, int64_t F, void *ws, int64_t ws_bytes, void *stream);
+int m3_mesh_topology_read(const void *ws, int64_t V, int64_t F, int32_t *degree_out, uint8_t *boundary_out, void *stream);
+int m3_mesh_topology_edges(void *ws, int64_t V, int64_t F, int64_t E, int32_t *edges_out, int32_t *edge_faces_out,
+                           void *stream);
+int m3_mesh_smooth_passes(const float *vertices, int64_t V, int64_t F, void *ws, int64_t ws_bytes, const uint8_t *pinned,
+                          int fix_boundary, int method, int iterations, float lam, float mu, float *out, void *stream);
+
 /* ---------------------------------------------------------- camera intrinsics */
 
 /* Focal length of every keyframe from its own pointmap.  Host side: mast3r_slam/intrinsics.py.

@@ -22,7 +22,8 @@ estimate of mast3r_slam/intrinsics.py (estimate_focal, estimate_intrinsics) and 
 mast3r_slam/consistency.py (multiview_support, consistent_keyframes) and the volumetric fusion of
 mast3r_slam/fusion.py (fuse_tsdf, extract_surface) and the mesh clean-up of mast3r_slam/components.py (mesh_components,
 filter_components) and the vertex normals and lit vertex colours of mast3r_slam/normals.py (vertex_normals, shade_vertices;
-save_ply_mesh_normals writes them) and the vertex clustering of mast3r_slam/simplify.py (simplify_mesh, simplify_counts).
+save_ply_mesh_normals writes them) and the vertex clustering of mast3r_slam/simplify.py (simplify_mesh, simplify_counts)
+and the edge topology and smoothing of mast3r_slam/smooth.py (mesh_topology, smooth_mesh).
 """
 from __future__ import annotations
 
@@ -46,6 +47,7 @@ from .fusion import TSDFVolume, extract_surface, fuse_tsdf
 from .components import ComponentsInfo, filter_components, mesh_components
 from .normals import shade_vertices, vertex_normals
 from .simplify import SimplifyInfo, simplify_counts, simplify_mesh
+from .smooth import MeshTopology, mesh_topology, smooth_mesh
 
 __all__ = [
     "load_mast3r", "resize_img", "frame_to_numpy", "downsample", "mast3r_inference_mono", "mast3r_asymmetric_inference",
@@ -61,6 +63,7 @@ __all__ = [
     "mesh_components", "filter_components", "ComponentsInfo",
     "vertex_normals", "shade_vertices", "save_ply_mesh_normals",
     "simplify_mesh", "simplify_counts", "SimplifyInfo",
+    "smooth_mesh", "mesh_topology", "MeshTopology",
 ]
 
 
