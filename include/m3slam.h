@@ -984,6 +984,88 @@ int m3_mesh_topology_edges(void *ws, int64_t V, int64_t F, int64_t E, int32_t *e
 int m3_mesh_smooth_passes(const float *vertices, int64_t V, int64_t F, void *ws, int64_t ws_bytes, const uint8_t *pinned,
                           int fix_boundary, int method, int iterations, float lam, float mu, float *out, void *stream);
 
+/* ---------------------------------------------------------------- point cloud */
+
+/* Fixed-radius neighbourhoods of a point cloud, and the two passes on top of them: normals and the radius outlier
+ * filter.  Host side: mast3r_slam/cloud.py.  This text is the contract, and tests/cloud_twin.py
+ * restates it in numpy; counts and moments of device and twin agree byte for byte.  Every float64 operation below is
+ * rounded on its own (no fused multiply-add).
+ *
+ * Inputs: points float32 [M,3], 0 <= M <= 2^30; radius, a float32 value r > 0; scale = 2^20 / (double)r, a double the
+ * host computes (the device does not divide for it; an entry point refuses a scale with scale * r > 2^21).
+ *
+ * Finite points.  A point is finite when its three coordinates are.  A point that is not finite has no neighbours and
+ * is nobody's neighbour.
+ *
+ * Range.  The cell of a finite point is floor((double)p / h) per axis, h = (double)r * (1 + 2^-10) (exact in float64),
+ * the quotient an IEEE float64 division.  A point with a cell coordinate c, |c| >= 2^20, on some axis is out of range:
+ * it is counted in the header of ws, and is treated as a point that is not finite.  The caller is expected to refuse
+ * the cloud then (the Python layer raises ValueError).
+ *
+ * Neighbour set N(i) of a finite point i: every finite j, i itself included, with
+ *     d = (double)p_j - (double)p_i per axis,  d2 = (dx dx + dy dy) + dz dz,  d2 <= (double)r * (double)r.
+ * The boundary is inclusive, and duplicate points are neighbours of each other.
+ *
+ * Outputs per point.
+ *   - count[i] = |N(i)|, int32; 0 for a point that is not finite.
+ *   - moments[i], int64 [9], over N(i), from q = rint(d * scale) per axis (round half to even) as integers:
+ *     sum qx, sum qy, sum qz, sum qx qx, sum qx qy, sum qx qz, sum qy qy, sum qy qz, sum qz qz; zeros where count = 0.
+ * Every sum is an integer sum, so the result depends neither on the order of the threads nor on the order of the input
+ * rows.  |q| <= 2^20 + 1, so no sum overflows below about 2^22 neighbours of one point; that bound is not enforced.
+ *
+ * Normals from count and moments, one point at a time, in float64.  n = count, S1 the first three moments, S2 the
+ * symmetric matrix of the last six.
+ *   - C = S2 / n - (S1 / n)(S1 / n)^T; the device forms n S2 - S1 S1^T exactly in 128-bit integers and rounds that.
+ *   - The normal is a unit eigenvector of the smallest eigenvalue of C (cyclic Jacobi, a fixed number of sweeps, only
+ *     + - * / sqrt), rounded to float32; eigenvalues l0 <= l1 <= l2.
+ *   - count < min_points (min_points >= 1), trace(C) == 0 or a point that is not finite: normal (0,0,0), variation 0.
+ *   - toward given: the normal is negated when sum_a n_a * ((double)c_a - (double)p_a) < 0, c the viewpoint of the
+ *     point (toward + i * toward_stride); a zero or NaN sum leaves it.  toward NULL: the component of largest
+ *     magnitude is made positive, a tie going to the lower axis.
+ *   - variation = l0 / (l0 + l1 + l2) as float32 (0 on a plane, 1/3 for an isotropic blob).
+ *
+ * Radius filter: keep(i) <=> count[i] - 1 >= min_neighbors, min_neighbors >= 0 - the other points within r; a point
+ * that is not finite has count 0 and is never kept.  Kept rows come in input order.
+ *
+ * Left out: k-nearest-neighbour queries, the statistical outlier filter, normal propagation for clouds without
+ * viewpoints, per-point radii.
+ *
+ * m3_cloud_neighbors: m3_cloud_launches() = 7 launches whatever M and the content are (clear header, table and cell
+ * counts with a kernel; one thread per point claims the slot of its cell's key - 3 x 21 bits, as the voxel pass of
+ * m3_map_voxel_count packs them - with a 64-bit compare-and-swap and takes its rank in the cell with an integer add,
+ * or writes its zero outputs when it has no cell; the exclusive scan of the cell counts in three - sums per tile of
+ * 256 slots, one scan of the tiles, tile offset + rank; one thread per point writes (x, y, z, i) as 16 bytes at its
+ * cell's start + its rank; one thread per entry of that cell-sorted list walks the 27 cells around its own with ten
+ * accumulators in registers).  moments may be NULL: counts only.  Afterwards ws int32 [0] = the points out of range,
+ * [1] = the points that have a cell.  The 27-cell walk is complete: see the header comment of csrc/cloud.hip.
+ * m3_cloud_normals: one launch, one thread per point, no workspace.  toward float32 [3] (toward_stride 0) or [M,3]
+ * (toward_stride 3) or NULL; variation float32 [M] or NULL.
+ * m3_cloud_radius_count: two launches (kept rows per tile of 1024, one scan); ws int32 [2] = the kept rows M2, and
+ * words [0], [1] stay as m3_cloud_neighbors left them, so that the host reads all in one 16-byte copy.
+ * m3_cloud_radius_scatter with M2 as read back: one launch; points_out float32 [M2,3]; colors / colors_out uint8
+ * [M,3] / [M2,3] or both NULL; index int64 [M] or NULL, index_out int64 [M2] or NULL (= index[i], or i without index);
+ * rows_out int64 [M2] or NULL (= i).
+ * No entry point allocates or synchronises with the host: each can be captured into a graph.  The atomics are integer
+ * and commute (compare-and-swap to claim, add); no thread waits for another.  Which slot a cell lands in and the order
+ * inside a cell depend on the arrival order; nothing that is output does.
+ * ws: m3_cloud_ws_bytes(M) = 64 + pad(4 * ceil((S + 1) / 256)) + pad(4 * (S + 1)) + 8 * S + 3 * pad(4 * M) + 16 * M
+ * bytes, pad rounding up to 16, S the smallest power of two that is >= 1024 and >= 2 M (the table stays at most half
+ * full) (0 = M outside 0 ... 2^30), 16-byte aligned, contents ignored on entry of m3_cloud_neighbors.
+ * M3_ERR_INVALID_ARG, before any HIP call, for NULL pointers where M is non-zero, M out of range, a misaligned or
+ * short ws, pointers not aligned to their element, a radius that is not finite and > 0, a scale that is not finite
+ * and > 0 or has scale * r > 2^21, toward_stride other than 0 or 3, min_points < 1, min_neighbors < 0, M2 outside
+ * 0 ... M, colors without colors_out or the reverse, and index without index_out. */
+int64_t m3_cloud_ws_bytes(int64_t M);
+int m3_cloud_launches(void);
+int m3_cloud_neighbors(const float *points, int64_t M, float radius, double scale, int32_t *count, int64_t *moments,
+                       void *ws, int64_t ws_bytes, void *stream);
+int m3_cloud_normals(const float *points, int64_t M, const int32_t *count, const int64_t *moments, const float *toward,
+                     int toward_stride, int min_points, float *normals, float *variation, void *stream);
+int m3_cloud_radius_count(const int32_t *count, int64_t M, int min_neighbors, void *ws, int64_t ws_bytes, void *stream);
+int m3_cloud_radius_scatter(const float *points, const uint8_t *colors, const int64_t *index, const int32_t *count,
+                            int64_t M, int min_neighbors, const void *ws, int64_t ws_bytes, int64_t M2, float *points_out,
+                            uint8_t *colors_out, int64_t *index_out, int64_t *rows_out, void *stream);
+
 /* ---------------------------------------------------------- camera intrinsics */
 
 /* Focal length of every keyframe from its own pointmap.  Host side: mast3r_slam/intrinsics.py.

@@ -1,0 +1,522 @@
+// Fixed-radius neighbourhoods of a point cloud on a uniform grid, and the two passes on top of them: normals from the
+// neighbourhood moments and the radius outlier filter (mast3r_slam/cloud.py).
+// The rule is stated once, in include/m3slam.h; tests/cloud_twin.py restates it in numpy.
+//
+// index:  clear -> one thread per point (claim the slot of its cell's key, take a rank in the cell; a point without a
+//         cell writes its zero outputs here) -> cell counts per tile of 256 slots -> scan of the tiles -> cell starts =
+//         tile offset + rank -> one thread per point writes (x, y, z, i) at its cell's start + its rank -> one thread
+//         per entry of that list walks the 27 cells around its own (the hot path).
+// Seven launches whatever the cloud holds.  The only atomics are integer ones whose results commute: CAS to claim a
+// slot, add for the rank and the header.  Which slot a cell lands in and where in its cell a point lands depend on the
+// arrival order; count and moments are integer sums over a set, so nothing that is output does.  No thread waits for
+// another.
+//
+// Why 27 cells are enough.  The cell of p is floor(fl(p / h)) per axis, h = r (1 + 2^-10): r has 24 significant bits
+// and 1 + 2^-10 eleven, so h is exact in float64.  Let j be a neighbour of i: d2 <= r r, where r r is exact and d2 is
+// rounded three times, each operand a non-negative float64.  So dx dx <= r r (1 + 2^-52)^3 and |dx| <= r (1 + 2^-51)
+// for the rounded difference dx, and |p_j - p_i| <= r (1 + 2^-50) for the exact one.  The exact quotients then differ by
+// at most (1 + 2^-50) / (1 + 2^-10) < 1 - 2^-11.  A point with a cell has |fl(p / h)| < 2^20 + 1, so the division
+// moves each quotient by at most 2^-32: the computed quotients differ by less than 1 - 2^-11 + 2^-31 < 1, and their
+// floors by at most 1 - on every axis, near a power of two or not.  A float32 floorf(p / r) has no such margin: two
+// points exactly r apart can land two cells apart.
+//
+// The queries run in the order of the cell-sorted list: the lanes of a wave that share a cell walk the same 27 ranges,
+// so their 16-byte loads are one address per wave, and the range of a cell is contiguous.  The cells themselves lie in
+// table order, which is hash order: neighbouring cells are not neighbours in memory (DESIGN.md 7o has what that costs).
+//
+// ws: int32 [16] header | tile int32 [ceil((S + 1) / 256)] | start int32 [S + 1] | keys uint64 [S] | slot uint32 [M] |
+// rank int32 [M] | sslot uint32 [M] | sorted 16 bytes [M]; S = the power of two >= max(1024, 2 M).  Header words:
+// [0] points out of range, [1] points that have a cell (the total of the scan), [2] rows the radius filter keeps; the
+// others are 0.  The radius filter keeps its tile offsets in the tile array.
+//
+// Compiled with -ffp-contract=off: every float64 operation of the rule is rounded on its own.
+#include "common.h"
+#include "compact_dev.h"
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int kBuildLaunches = 7;
+constexpr int kClHdrWords = 16;
+constexpr int kOutOfRange = 0, kInCells = 1, kKept = 2;
+constexpr int64_t kMaxM = 1ll << 30;                  // S <= 2^31: slots fit uint32, list positions int32
+constexpr unsigned long long kEmptyKey = ~0ull;       // a packed cell key uses 63 bits
+constexpr uint32_t kNoSlot = ~0u;
+constexpr double kCellLim = 1048576.0;                // 2^20: 21 bits per axis after the offset
+constexpr int kCellBias = 1 << 20, kCellMask = (1 << 21) - 1;
+constexpr int kSweeps = 10;                           // cyclic Jacobi on 3 x 3: converged after five or six
+
+struct ClWs {
+    int64_t S, ntile;
+    int64_t tile, start, keys, slot, rank, sslot, sorted, bytes;                // byte offsets into ws
+};
+
+inline int64_t pad16(int64_t b) { return (b + 15) / 16 * 16; }
+
+inline bool cl_layout(int64_t M, ClWs &m) {
+    if (M < 0 || M > kMaxM) return false;
+    m.S = 1024;
+    while (m.S < 2 * M) m.S *= 2;                        // at most M cells: never more than half full
+    m.ntile = (m.S + 1 + kThreads - 1) / kThreads;
+    m.tile = kClHdrWords * 4;
+    m.start = m.tile + pad16(4 * m.ntile);
+    m.keys = m.start + pad16(4 * (m.S + 1));             // the clear kernel fills [0, keys) with 0 and [keys, slot) with ff
+    m.slot = m.keys + 8 * m.S;
+    m.rank = m.slot + pad16(4 * M);
+    m.sslot = m.rank + pad16(4 * M);
+    m.sorted = m.sslot + pad16(4 * M);
+    m.bytes = m.sorted + 16 * M;
+    return true;
+}
+
+struct alignas(16) Ent {                      // an entry of the cell-sorted list
+    float x, y, z;
+    int32_t i;                                // the point's row
+};
+
+struct ClPtr {
+    int32_t *hdr, *tile, *start, *rank;
+    unsigned long long *keys;
+    uint32_t *slot, *sslot;
+    Ent *sorted;
+};
+
+inline ClPtr cl_ptr(void *ws, const ClWs &m) {
+    char *p = (char *)ws;
+    ClPtr q;
+    q.hdr = (int32_t *)p;
+    q.tile = (int32_t *)(p + m.tile);
+    q.start = (int32_t *)(p + m.start);
+    q.keys = (unsigned long long *)(p + m.keys);
+    q.slot = (uint32_t *)(p + m.slot);
+    q.rank = (int32_t *)(p + m.rank);
+    q.sslot = (uint32_t *)(p + m.sslot);
+    q.sorted = (Ent *)(p + m.sorted);
+    return q;
+}
+
+inline dim3 grid_of(int64_t rows) { return dim3((unsigned)(rows ? (rows + kThreads - 1) / kThreads : 1)); }
+
+__device__ __forceinline__ int64_t row_of() { return (int64_t)blockIdx.x * kThreads + threadIdx.x; }
+
+__device__ __forceinline__ unsigned long long mix64(unsigned long long x) {
+    x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ull;
+    x ^= x >> 27; x *= 0x94d049bb133111ebull;
+    return x ^ (x >> 31);
+}
+
+// Biased cell coordinates, each in [1, 2^21 - 1], packed as k_voxel_insert packs its voxels.
+__device__ __forceinline__ unsigned long long cell_key(int bx, int by, int bz) {
+    return ((unsigned long long)bx << 42) | ((unsigned long long)by << 21) | (unsigned long long)bz;
+}
+
+__device__ __forceinline__ bool finite3(float x, float y, float z) { return isfinite(x) && isfinite(y) && isfinite(z); }
+
+// Header, tiles, cell counts and keys are cleared by a kernel, 16 bytes per thread: a captured memset left its words
+// uncleared on replay.  int4 [0, a) = 0, [a, n) = ff ..
+__global__ void __launch_bounds__(kThreads) k_cl_clear(int4 *__restrict__ ws, int64_t a, int64_t n) {
+    const int64_t i = row_of();
+    if (i >= n) return;
+    const int w = i < a ? 0 : -1;
+    ws[i] = int4{w, w, w, w};
+}
+
+// One point per thread: claim or find the slot of its cell and take the next rank in it.  A point that is not finite
+// or out of range gets no slot and its outputs - zeros - here, since the query pass never sees it.
+__global__ void __launch_bounds__(kThreads) k_cl_insert(const float *__restrict__ points, int64_t M, double h,
+                                                         unsigned long long *__restrict__ keys, int32_t *__restrict__ cnt,
+                                                         int64_t S, uint32_t *__restrict__ slot, int32_t *__restrict__ rank,
+                                                         int32_t *__restrict__ count, int64_t *__restrict__ moments,
+                                                         int32_t *__restrict__ hdr) {
+    const int64_t i = row_of();
+    bool far = false;
+    if (i < M) {
+        const float x = points[3 * i], y = points[3 * i + 1], z = points[3 * i + 2];
+        uint32_t mine = kNoSlot;
+        int32_t r = 0;
+        if (finite3(x, y, z)) {
+            const double cx = floor((double)x / h), cy = floor((double)y / h), cz = floor((double)z / h);
+            far = !(fabs(cx) < kCellLim && fabs(cy) < kCellLim && fabs(cz) < kCellLim);
+            if (!far) {
+                const unsigned long long key = cell_key((int)cx + kCellBias, (int)cy + kCellBias, (int)cz + kCellBias);
+                const unsigned long long mask = (unsigned long long)(S - 1);
+                unsigned long long s = mix64(key) & mask;
+                for (int64_t probe = 0; probe < S; ++probe) {                   // the table is at most half full: this ends
+                    unsigned long long cur = __hip_atomic_load(keys + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    if (cur == kEmptyKey) {
+                        cur = atomicCAS(keys + s, kEmptyKey, key);
+                        if (cur == kEmptyKey) cur = key;
+                    }
+                    if (cur == key) {
+                        mine = (uint32_t)s;
+                        r = atomicAdd(cnt + s, 1);
+                        break;
+                    }
+                    s = (s + 1) & mask;
+                }
+            }
+        }
+        slot[i] = mine;
+        rank[i] = r;
+        if (mine == kNoSlot) {
+            count[i] = 0;
+            if (moments) {
+#pragma unroll
+                for (int k = 0; k < 9; ++k) moments[9 * i + k] = 0;
+            }
+        }
+    }
+    const unsigned long long b = __ballot(far);
+    if (b && (threadIdx.x & 63) == 0) atomicAdd(hdr + kOutOfRange, (int)__popcll(b));      // M <= 2^30: no overflow
+}
+
+// Exclusive prefix of x over the workgroup in thread order, and the workgroup's total.
+__device__ __forceinline__ int block_exclusive(int x, int &total) {
+    __shared__ int wtot[kThreads / M3_WAVE];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    int incl = x;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int t = __shfl_up(incl, o, 64);
+        if (lane >= o) incl += t;
+    }
+    if (lane == 63) wtot[w] = incl;
+    __syncthreads();
+    int base = 0;
+    total = 0;
+#pragma unroll
+    for (int i = 0; i < kThreads / M3_WAVE; ++i) {
+        base += i < w ? wtot[i] : 0;
+        total += wtot[i];
+    }
+    return base + incl - x;
+}
+
+// The cell counts of a tile of 256 slots, added up.  cnt has n = S + 1 entries; the last is 0 and becomes the total.
+__global__ void __launch_bounds__(kThreads) k_cl_tile_counts(const int32_t *__restrict__ cnt, int64_t n,
+                                                              int32_t *__restrict__ tile) {
+    const int64_t i = row_of();
+    int total;
+    block_exclusive(i < n ? cnt[i] : 0, total);
+    if (threadIdx.x == 0) tile[blockIdx.x] = total;
+}
+
+// Counts to cell starts, in place: the tile's offset + the rank inside the tile.  Cell s is [start[s], start[s + 1]).
+__global__ void __launch_bounds__(kThreads) k_cl_starts(int32_t *__restrict__ cnt, int64_t n, const int32_t *__restrict__ tile) {
+    const int64_t i = row_of();
+    int total;
+    const int start = tile[blockIdx.x] + block_exclusive(i < n ? cnt[i] : 0, total);
+    if (i < n) cnt[i] = start;
+}
+
+// One point per thread again: its entry goes to its cell's start + its rank.
+__global__ void __launch_bounds__(kThreads) k_cl_fill(const float *__restrict__ points, int64_t M,
+                                                       const uint32_t *__restrict__ slot, const int32_t *__restrict__ rank,
+                                                       const int32_t *__restrict__ start, int64_t S, Ent *__restrict__ sorted,
+                                                       uint32_t *__restrict__ sslot) {
+    const int64_t i = row_of();
+    if (i >= M) return;
+    const uint32_t s = slot[i];
+    if (s == kNoSlot || (int64_t)s >= S) return;
+    const int64_t at = (int64_t)start[s] + rank[i];
+    if (at < 0 || at >= M) return;                                              // never, for a ws from the same points
+    sorted[at] = Ent{points[3 * i], points[3 * i + 1], points[3 * i + 2], (int32_t)i};
+    sslot[at] = s;
+}
+
+// One entry of the cell-sorted list per thread: the 27 cells around its own, each looked up in the table and walked
+// from start to end, one 16-byte load per candidate.  n_in = hdr[kInCells] entries exist.
+template <bool MOMENTS>
+__global__ void __launch_bounds__(kThreads) k_cl_query(const Ent *__restrict__ sorted, const uint32_t *__restrict__ sslot,
+                                                        const int32_t *__restrict__ start,
+                                                        const unsigned long long *__restrict__ keys, int64_t S, int64_t M,
+                                                        const int32_t *__restrict__ hdr, double r2, double scale,
+                                                        int32_t *__restrict__ count, int64_t *__restrict__ moments) {
+    const int64_t t = row_of();
+    const int64_t n_in = hdr[kInCells] < M ? hdr[kInCells] : M;
+    if (t >= n_in) return;
+    const Ent me = sorted[t];
+    const uint32_t s0 = sslot[t];
+    if ((int64_t)s0 >= S || me.i < 0 || me.i >= M) return;                      // never, for a ws from the same points
+    const unsigned long long key = keys[s0], mask = (unsigned long long)(S - 1);
+    const int bx = (int)(key >> 42) & kCellMask, by = (int)(key >> 21) & kCellMask, bz = (int)key & kCellMask;
+    const double px = (double)me.x, py = (double)me.y, pz = (double)me.z;
+    int n = 0;
+    int64_t a0 = 0, a1 = 0, a2 = 0, a3 = 0, a4 = 0, a5 = 0, a6 = 0, a7 = 0, a8 = 0;
+#pragma unroll 1
+    for (int c = 0; c < 27; ++c) {
+        const int ox = c % 3 - 1, oy = (c / 3) % 3 - 1, oz = c / 9 - 1;
+        const int nx = bx + ox, ny = by + oy, nz = bz + oz;
+        if (nx < 1 || nx > kCellMask || ny < 1 || ny > kCellMask || nz < 1 || nz > kCellMask) continue;   // holds no point
+        int64_t b = 0, e = 0;
+        const unsigned long long want = cell_key(nx, ny, nz);
+        unsigned long long s = c == 13 ? (unsigned long long)s0 : mix64(want) & mask;
+        for (int64_t probe = 0; probe < S; ++probe) {
+            const unsigned long long cur = keys[s];
+            if (cur == want) {
+                b = start[s];
+                e = start[s + 1];
+                break;
+            }
+            if (cur == kEmptyKey) break;
+            s = (s + 1) & mask;
+        }
+        if (b < 0 || e < b || e > n_in) b = e = 0;                              // never, for a ws from the same points
+        for (int64_t k = b; k < e; ++k) {
+            const Ent q = sorted[k];
+            const double dx = (double)q.x - px, dy = (double)q.y - py, dz = (double)q.z - pz;
+            const double d2 = (dx * dx + dy * dy) + dz * dz;
+            const bool in = d2 <= r2;
+            n += in ? 1 : 0;
+            if (MOMENTS) {
+                // |q| <= 2^21 + 1 by the entry point's test of scale * r: the products are 32 x 32 -> 64 bits
+                const int qx = (int)rint(in ? dx * scale : 0.0), qy = (int)rint(in ? dy * scale : 0.0),
+                          qz = (int)rint(in ? dz * scale : 0.0);
+                a0 += qx;
+                a1 += qy;
+                a2 += qz;
+                a3 += (int64_t)qx * qx;
+                a4 += (int64_t)qx * qy;
+                a5 += (int64_t)qx * qz;
+                a6 += (int64_t)qy * qy;
+                a7 += (int64_t)qy * qz;
+                a8 += (int64_t)qz * qz;
+            }
+        }
+    }
+    count[me.i] = n;
+    if (MOMENTS) {
+        int64_t *row = moments + 9 * (int64_t)me.i;
+        row[0] = a0; row[1] = a1; row[2] = a2; row[3] = a3; row[4] = a4; row[5] = a5; row[6] = a6; row[7] = a7; row[8] = a8;
+    }
+}
+
+// ---- normals ---------------------------------------------------------------------------------------------------------
+// |v| < 2^127, rounded twice at most: the high and the low word of |v| are converted and added.
+__device__ __forceinline__ double to_double(__int128 v) {
+    const bool neg = v < 0;
+    const unsigned __int128 a = neg ? (unsigned __int128)0 - (unsigned __int128)v : (unsigned __int128)v;
+    const double d = (double)(unsigned long long)(a >> 64) * 18446744073709551616.0 + (double)(unsigned long long)a;
+    return neg ? -d : d;
+}
+
+// One Jacobi rotation in the (P, Q) plane of the symmetric A, accumulated into the columns of V; R is the third axis.
+template <int P, int Q, int R>
+__device__ __forceinline__ void rotate(double (&A)[3][3], double (&V)[3][3]) {
+    const double apq = A[P][Q];
+    if (apq == 0.0) return;
+    const double theta = (A[Q][Q] - A[P][P]) / (2.0 * apq);
+    const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));     // theta^2 = inf: t = 0
+    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+    A[P][P] -= t * apq;
+    A[Q][Q] += t * apq;
+    A[P][Q] = A[Q][P] = 0.0;
+    const double arp = A[R][P], arq = A[R][Q];
+    A[R][P] = A[P][R] = c * arp - s * arq;
+    A[R][Q] = A[Q][R] = s * arp + c * arq;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const double vp = V[k][P], vq = V[k][Q];
+        V[k][P] = c * vp - s * vq;
+        V[k][Q] = s * vp + c * vq;
+    }
+}
+
+// One point per thread: n S2 - S1 S1^T exactly, its eigenvector of the smallest eigenvalue, the orientation.
+__global__ void __launch_bounds__(kThreads) k_cl_normals(const float *__restrict__ points, int64_t M,
+                                                          const int32_t *__restrict__ count, const int64_t *__restrict__ moments,
+                                                          const float *__restrict__ toward, int toward_stride, int min_points,
+                                                          float *__restrict__ normals, float *__restrict__ variation) {
+    const int64_t i = row_of();
+    if (i >= M) return;
+    float out[3] = {0.f, 0.f, 0.f}, var = 0.f;
+    const int n = count[i];
+    const float px = points[3 * i], py = points[3 * i + 1], pz = points[3 * i + 2];
+    if (n >= min_points && n >= 1 && finite3(px, py, pz)) {
+        int64_t m[9];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) m[k] = moments[9 * i + k];
+        const __int128 nn = n;
+        const __int128 d00 = nn * m[3] - (__int128)m[0] * m[0], d01 = nn * m[4] - (__int128)m[0] * m[1],
+                       d02 = nn * m[5] - (__int128)m[0] * m[2], d11 = nn * m[6] - (__int128)m[1] * m[1],
+                       d12 = nn * m[7] - (__int128)m[1] * m[2], d22 = nn * m[8] - (__int128)m[2] * m[2];
+        if (d00 + d11 + d22 != 0) {
+            double A[3][3] = {{to_double(d00), to_double(d01), to_double(d02)},
+                              {to_double(d01), to_double(d11), to_double(d12)},
+                              {to_double(d02), to_double(d12), to_double(d22)}};
+            double V[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
+#pragma unroll 1
+            for (int sweep = 0; sweep < kSweeps; ++sweep) {
+                rotate<0, 1, 2>(A, V);
+                rotate<0, 2, 1>(A, V);
+                rotate<1, 2, 0>(A, V);
+            }
+            const double l[3] = {A[0][0], A[1][1], A[2][2]};
+            const int k = l[1] < l[0] ? (l[2] < l[1] ? 2 : 1) : (l[2] < l[0] ? 2 : 0);    // the smallest; a tie: the lower
+            double u[3];
+#pragma unroll
+            for (int a = 0; a < 3; ++a) u[a] = k == 0 ? V[a][0] : k == 1 ? V[a][1] : V[a][2];
+            const double len = sqrt((u[0] * u[0] + u[1] * u[1]) + u[2] * u[2]);
+            const double l0 = k == 0 ? l[0] : k == 1 ? l[1] : l[2], sum = (l[0] + l[1]) + l[2];
+            if (len > 0.0 && sum > 0.0) {
+#pragma unroll
+                for (int a = 0; a < 3; ++a) out[a] = (float)(u[a] / len);
+                var = (float)((l0 > 0.0 ? l0 : 0.0) / sum);
+                bool flip;
+                if (toward) {
+                    const float *c = toward + (int64_t)toward_stride * i;
+                    const double dot = ((double)out[0] * ((double)c[0] - (double)px) + (double)out[1] * ((double)c[1] - (double)py)) +
+                                       (double)out[2] * ((double)c[2] - (double)pz);
+                    flip = dot < 0.0;
+                } else {
+                    const float ax = fabsf(out[0]), ay = fabsf(out[1]), az = fabsf(out[2]);
+                    const float lead = ax >= ay && ax >= az ? out[0] : ay >= az ? out[1] : out[2];
+                    flip = lead < 0.f;
+                }
+                if (flip) {
+#pragma unroll
+                    for (int a = 0; a < 3; ++a) out[a] = -out[a];
+                }
+            }
+        }
+    }
+    normals[3 * i] = out[0];
+    normals[3 * i + 1] = out[1];
+    normals[3 * i + 2] = out[2];
+    if (variation) variation[i] = var;
+}
+
+// ---- radius filter ---------------------------------------------------------------------------------------------------
+// Bits of the thread's four consecutive rows that have more than min_neighbors points in their set: themselves and
+// min_neighbors others at least.
+__device__ __forceinline__ unsigned kept_rows(const int32_t *__restrict__ count, int64_t i0, int64_t M, int min_neighbors) {
+    unsigned keep = 0;
+#pragma unroll
+    for (int j = 0; j < kPts; ++j) {
+        if (i0 + j < M && count[i0 + j] > min_neighbors) keep |= 1u << j;
+    }
+    return keep;
+}
+
+__global__ void __launch_bounds__(kThreads) k_cl_keep_count(const int32_t *__restrict__ count, int64_t M, int min_neighbors,
+                                                             int32_t *__restrict__ cnt) {
+    const unsigned keep = kept_rows(count, (int64_t)blockIdx.x * kTile + threadIdx.x * kPts, M, min_neighbors);
+    int total;
+    block_prefix(keep, total);
+    if (threadIdx.x == 0) cnt[blockIdx.x] = total;
+}
+
+__global__ void __launch_bounds__(kThreads) k_cl_keep_scatter(const float *__restrict__ points,
+                                                               const unsigned char *__restrict__ colors,
+                                                               const int64_t *__restrict__ index,
+                                                               const int32_t *__restrict__ count, int64_t M, int min_neighbors,
+                                                               const int32_t *__restrict__ offs, int64_t M2,
+                                                               float *__restrict__ points_out,
+                                                               unsigned char *__restrict__ colors_out,
+                                                               int64_t *__restrict__ index_out, int64_t *__restrict__ rows_out) {
+    const int64_t i0 = (int64_t)blockIdx.x * kTile + threadIdx.x * kPts;
+    const unsigned keep = kept_rows(count, i0, M, min_neighbors);
+    int total;
+    int64_t o = (int64_t)offs[blockIdx.x] + block_prefix(keep, total);
+#pragma unroll
+    for (int j = 0; j < kPts; ++j) {
+        if (!((keep >> j) & 1u) || o < 0 || o >= M2) continue;                  // o < M2 always holds for a ws from the same count
+        const int64_t i = i0 + j;
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            points_out[3 * o + d] = points[3 * i + d];
+            if (colors_out) colors_out[3 * o + d] = colors[3 * i + d];
+        }
+        if (index_out) index_out[o] = index ? index[i] : i;
+        if (rows_out) rows_out[o] = i;
+        ++o;
+    }
+}
+
+inline bool ws_ok(const void *ws) { return ws && ((uintptr_t)ws & 15) == 0; }
+inline bool aligned(const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
+inline int64_t keep_tiles(int64_t M) { return M ? (M + kTile - 1) / kTile : 1; }
+
+}  // namespace
+
+extern "C" {
+
+int64_t m3_cloud_ws_bytes(int64_t M) {
+    ClWs m;
+    return cl_layout(M, m) ? m.bytes : 0;
+}
+
+int m3_cloud_launches(void) { return kBuildLaunches; }
+
+int m3_cloud_neighbors(const float *points, int64_t M, float radius, double scale, int32_t *count, int64_t *moments,
+                       void *ws, int64_t ws_bytes, void *stream) {
+    ClWs m;
+    M3_REQUIRE(cl_layout(M, m) && ws_ok(ws) && ws_bytes >= m.bytes);
+    M3_REQUIRE(((points && count) || M == 0) && aligned(points, 4) && aligned(count, 4) && aligned(moments, 8));
+    M3_REQUIRE(radius > 0.f && radius < INFINITY);                                                   // NaN fails
+    M3_REQUIRE(scale > 0.0 && scale < (double)INFINITY && scale * (double)radius <= 2097152.0);
+    hipStream_t st = (hipStream_t)stream;
+    const ClPtr p = cl_ptr(ws, m);
+    const dim3 block(kThreads);
+    const dim3 tiles((unsigned)m.ntile);
+    const double r = (double)radius, h = r * (1.0 + 0x1p-10);
+    hipLaunchKernelGGL(k_cl_clear, grid_of(m.slot / 16), block, 0, st, (int4 *)ws, m.keys / 16, m.slot / 16);
+    // M = 0: no thread has a row.  The launches are kept so that their number is fixed.
+    hipLaunchKernelGGL(k_cl_insert, grid_of(M), block, 0, st, points, M, h, p.keys, p.start, m.S, p.slot, p.rank, count,
+                       moments, p.hdr);
+    hipLaunchKernelGGL(k_cl_tile_counts, tiles, block, 0, st, p.start, m.S + 1, p.tile);
+    launch_scan(st, p.hdr + kInCells, ScanJob{p.tile, m.ntile});
+    hipLaunchKernelGGL(k_cl_starts, tiles, block, 0, st, p.start, m.S + 1, p.tile);
+    hipLaunchKernelGGL(k_cl_fill, grid_of(M), block, 0, st, points, M, p.slot, p.rank, p.start, m.S, p.sorted, p.sslot);
+    if (moments)
+        hipLaunchKernelGGL(k_cl_query<true>, grid_of(M), block, 0, st, p.sorted, p.sslot, p.start, p.keys, m.S, M, p.hdr,
+                           r * r, scale, count, moments);
+    else
+        hipLaunchKernelGGL(k_cl_query<false>, grid_of(M), block, 0, st, p.sorted, p.sslot, p.start, p.keys, m.S, M, p.hdr,
+                           r * r, scale, count, moments);
+    M3_CHECK_LAUNCH("m3_cloud_neighbors");
+    return M3_OK;
+}
+
+int m3_cloud_normals(const float *points, int64_t M, const int32_t *count, const int64_t *moments, const float *toward,
+                     int toward_stride, int min_points, float *normals, float *variation, void *stream) {
+    M3_REQUIRE(M >= 0 && M <= kMaxM && ((points && count && moments && normals) || M == 0));
+    M3_REQUIRE(aligned(points, 4) && aligned(count, 4) && aligned(moments, 8) && aligned(toward, 4) && aligned(normals, 4) &&
+               aligned(variation, 4));
+    M3_REQUIRE((toward_stride == 0 || toward_stride == 3) && min_points >= 1);
+    hipLaunchKernelGGL(k_cl_normals, grid_of(M), dim3(kThreads), 0, (hipStream_t)stream, points, M, count, moments, toward,
+                       toward_stride, min_points, normals, variation);
+    M3_CHECK_LAUNCH("m3_cloud_normals");
+    return M3_OK;
+}
+
+int m3_cloud_radius_count(const int32_t *count, int64_t M, int min_neighbors, void *ws, int64_t ws_bytes, void *stream) {
+    ClWs m;
+    M3_REQUIRE(cl_layout(M, m) && ws_ok(ws) && ws_bytes >= m.bytes);
+    M3_REQUIRE((count || M == 0) && aligned(count, 4) && min_neighbors >= 0);
+    hipStream_t st = (hipStream_t)stream;
+    const ClPtr p = cl_ptr(ws, m);
+    const int64_t tiles = keep_tiles(M);                                        // <= ntile: the offsets fit the tile array
+    hipLaunchKernelGGL(k_cl_keep_count, dim3((unsigned)tiles), dim3(kThreads), 0, st, count, M, min_neighbors, p.tile);
+    launch_scan(st, p.hdr + kKept, ScanJob{p.tile, tiles});
+    M3_CHECK_LAUNCH("m3_cloud_radius_count");
+    return M3_OK;
+}
+
+int m3_cloud_radius_scatter(const float *points, const uint8_t *colors, const int64_t *index, const int32_t *count,
+                            int64_t M, int min_neighbors, const void *ws, int64_t ws_bytes, int64_t M2, float *points_out,
+                            uint8_t *colors_out, int64_t *index_out, int64_t *rows_out, void *stream) {
+    ClWs m;
+    M3_REQUIRE(cl_layout(M, m) && ws_ok(ws) && ws_bytes >= m.bytes);
+    M3_REQUIRE(M2 >= 0 && M2 <= M && ((points && count) || M == 0) && (points_out || M2 == 0) && min_neighbors >= 0);
+    M3_REQUIRE((colors != nullptr) == (colors_out != nullptr) && (!index || index_out));
+    M3_REQUIRE(aligned(points, 4) && aligned(count, 4) && aligned(points_out, 4) && aligned(index, 8) && aligned(index_out, 8) &&
+               aligned(rows_out, 8));
+    const ClPtr p = cl_ptr(const_cast<void *>(ws), m);
+    hipLaunchKernelGGL(k_cl_keep_scatter, dim3((unsigned)keep_tiles(M)), dim3(kThreads), 0, (hipStream_t)stream, points, colors,
+                       index, count, M, min_neighbors, p.tile, M2, points_out, colors_out, index_out, rows_out);
+    M3_CHECK_LAUNCH("m3_cloud_radius_scatter");
+    return M3_OK;
+}
+
+}  // extern "C"

@@ -31,7 +31,8 @@ import torch
 
 from . import _ffi
 
-__all__ = ["collect_map", "collect_mesh", "save_ply", "save_ply_mesh", "save_ply_mesh_normals", "save_trajectory"]
+__all__ = ["collect_map", "collect_mesh", "save_ply", "save_ply_mesh", "save_ply_mesh_normals", "save_ply_normals",
+           "save_trajectory"]
 
 IMG_F32_CHW, IMG_U8_HWC = 0, 1                                         # include/m3slam.h
 _PLY_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")])
@@ -343,6 +344,34 @@ def save_ply_mesh_normals(path, vertices, colors, faces, normals, binary: bool =
             if f:
                 np.savetxt(fh, t, fmt="3 %d %d %d")
     return v, f
+
+
+def save_ply_normals(path, points, colors, normals, binary: bool = True) -> int:
+    """save_ply with per-point normals (cloud.cloud_normals): the vertex properties are float x y z nx ny nz, uchar red
+    green blue, as save_ply_mesh_normals writes them, and there is no face element - what a Poisson reconstruction or a
+    surfel viewer reads.  binary: one structured array in `binary_little_endian 1.0`; else ASCII lines (%.6f), for
+    small clouds.  ValueError when the row counts differ.  Returns M."""
+    p = _host(points, np.float32).reshape(-1, 3)
+    c = _host(colors, np.uint8).reshape(-1, 3)
+    n = _host(normals, np.float32).reshape(-1, 3)
+    if p.shape[0] != c.shape[0] or p.shape[0] != n.shape[0]:
+        raise ValueError(f"{p.shape[0]} points but {c.shape[0]} colours and {n.shape[0]} normals")
+    m = p.shape[0]
+    with open(os.fspath(path), "wb") as fh:
+        fh.write(("ply\nformat {} 1.0\nelement vertex {}\nproperty float x\nproperty float y\nproperty float z\n"
+                  "property float nx\nproperty float ny\nproperty float nz\n"
+                  "property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n"
+                  ).format("binary_little_endian" if binary else "ascii", m).encode("ascii"))
+        if binary:
+            body = np.empty(m, dtype=_PLY_NORMALS_DTYPE)
+            for k, name in enumerate("xyz"):
+                body[name], body["n" + name] = p[:, k], n[:, k]
+            body["red"], body["green"], body["blue"] = c[:, 0], c[:, 1], c[:, 2]
+            body.tofile(fh)
+        elif m:
+            np.savetxt(fh, np.concatenate([p.astype(np.float64), n.astype(np.float64), c.astype(np.float64)], axis=1),
+                       fmt="%.6f %.6f %.6f %.6f %.6f %.6f %d %d %d")
+    return m
 
 
 def _sim3_rows(poses: np.ndarray) -> np.ndarray:

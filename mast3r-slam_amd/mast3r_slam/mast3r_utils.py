@@ -23,7 +23,9 @@ mast3r_slam/consistency.py (multiview_support, consistent_keyframes) and the vol
 mast3r_slam/fusion.py (fuse_tsdf, extract_surface) and the mesh clean-up of mast3r_slam/components.py (mesh_components,
 filter_components) and the vertex normals and lit vertex colours of mast3r_slam/normals.py (vertex_normals, shade_vertices;
 save_ply_mesh_normals writes them) and the vertex clustering of mast3r_slam/simplify.py (simplify_mesh, simplify_counts)
-and the edge topology and smoothing of mast3r_slam/smooth.py (mesh_topology, smooth_mesh).
+and the edge topology and smoothing of mast3r_slam/smooth.py (mesh_topology, smooth_mesh) and the point-cloud
+neighbourhoods of mast3r_slam/cloud.py (cloud_neighbors, cloud_normals, source_viewpoints, remove_radius_outliers;
+save_ply_normals writes a cloud with normals).
 """
 from __future__ import annotations
 
@@ -36,7 +38,8 @@ from .config import get_config
 from .model import Mast3rFull
 from . import matching
 from .retrieval import RetrievalDatabase, load_retriever
-from .export import collect_map, collect_mesh, save_ply, save_ply_mesh, save_ply_mesh_normals, save_trajectory
+from .export import (collect_map, collect_mesh, save_ply, save_ply_mesh, save_ply_mesh_normals, save_ply_normals,
+                     save_trajectory)
 from .camera import CameraModel, load_calibration, undistort_device
 from .preprocess import adjust_intrinsics, resample_tables, resize_geometry, resize_img_device
 from .render import (ViewRecorder, behind, default_intrinsics, depth_to_rgb, look_at, mesh_workspace_bytes, render_map,
@@ -48,6 +51,7 @@ from .components import ComponentsInfo, filter_components, mesh_components
 from .normals import shade_vertices, vertex_normals
 from .simplify import SimplifyInfo, simplify_counts, simplify_mesh
 from .smooth import MeshTopology, mesh_topology, smooth_mesh
+from .cloud import CloudNeighbors, cloud_neighbors, cloud_normals, remove_radius_outliers, source_viewpoints
 
 __all__ = [
     "load_mast3r", "resize_img", "frame_to_numpy", "downsample", "mast3r_inference_mono", "mast3r_asymmetric_inference",
@@ -64,6 +68,7 @@ __all__ = [
     "vertex_normals", "shade_vertices", "save_ply_mesh_normals",
     "simplify_mesh", "simplify_counts", "SimplifyInfo",
     "smooth_mesh", "mesh_topology", "MeshTopology",
+    "cloud_neighbors", "cloud_normals", "source_viewpoints", "remove_radius_outliers", "CloudNeighbors", "save_ply_normals",
 ]
 
 
