@@ -1027,8 +1027,8 @@ int m3_mesh_smooth_passes(const float *vertices, int64_t V, int64_t F, void *ws,
  * Radius filter: keep(i) <=> count[i] - 1 >= min_neighbors, min_neighbors >= 0 - the other points within r; a point
  * that is not finite has count 0 and is never kept.  Kept rows come in input order.
  *
- * Left out: k-nearest-neighbour queries, the statistical outlier filter, normal propagation for clouds without
- * viewpoints, per-point radii.
+ * k-nearest-neighbour queries and the statistical outlier filter: the m3_knn_* entry points below.  Left out: normal
+ * propagation for clouds without viewpoints, per-point radii.
  *
  * m3_cloud_neighbors: m3_cloud_launches() = 7 launches whatever M and the content are (clear header, table and cell
  * counts with a kernel; one thread per point claims the slot of its cell's key - 3 x 21 bits, as the voxel pass of
@@ -1065,6 +1065,85 @@ int m3_cloud_radius_count(const int32_t *count, int64_t M, int min_neighbors, vo
 int m3_cloud_radius_scatter(const float *points, const uint8_t *colors, const int64_t *index, const int32_t *count,
                             int64_t M, int min_neighbors, const void *ws, int64_t ws_bytes, int64_t M2, float *points_out,
                             uint8_t *colors_out, int64_t *index_out, int64_t *rows_out, void *stream);
+
+/* k nearest neighbours within a radius on the same index, and the two passes on top of them: the statistical outlier
+ * filter and normals over the k nearest.  Host side: mast3r_slam/cloud.py.  This text is the
+ * contract, and tests/knn_twin.py restates it in numpy - brute force over all pairs, no cells; index, dist2, found, q and
+ * the kept rows of device and twin agree byte for byte.  Every float64 operation is rounded on its own.
+ *
+ * The search is hybrid: the k nearest among the points within r.  The grid is the one above (cells of edge h =
+ * r (1 + 2^-10)), so the 27 cells around a query hold every candidate; an unbounded k-NN would need ring expansion with
+ * no bound on the work for an isolated point and is left out.
+ *
+ * Queries.  Self mode (queries NULL, Q = M): the queries are the points; row i is not its own neighbour, other rows at
+ * the same position are, at distance 0.  Cross mode: queries float32 [Q,3], nothing is excluded.
+ *
+ * Candidates of a query q: every point j that is finite and in range (it has a cell, as above) with
+ *     d = (double)p_j - (double)q per axis,  d2 = (dx dx + dy dy) + dz dz,  d2 <= (double)r * (double)r
+ * - the membership test of m3_cloud_neighbors, so that in self mode the candidates of i are N(i) without i.  A query
+ * that is not finite, or whose own cell coordinate floor((double)q / h) reaches +-2^20 on some axis (out of range), has
+ * no candidates; the queries that are finite but out of range are counted in header word [3] (cross mode only: in self
+ * mode they are the points of word [0]).
+ *
+ * Order.  Candidates are ordered by one unsigned 64-bit key, ascending:
+ *     key = (bits(d2) & ~(2^30 - 1)) | j
+ * bits(d2) the IEEE pattern of the non-negative float64 d2, its low 30 bits replaced by the row j (M <= 2^30).  That is:
+ * by squared distance to its 22 leading explicit mantissa bits, ties to the lower row.  TWO CANDIDATES WHOSE d2 DIFFER
+ * ONLY IN THE 30 DROPPED BITS (a relative difference below 2^-22) ARE ORDERED BY ROW, NOT BY DISTANCE.  No float32
+ * conversion and no denormal takes part in the ordering; one compare decides each pair.
+ *
+ * Outputs per query, 1 <= k <= 64:
+ *   - found int32 = min(k, number of candidates);
+ *   - index int32 [Q,k]: the rows of the `found` smallest keys in ascending key order, then -1;
+ *   - dist2 float32 [Q,k]: (float)d2 of those rows (d2 as above, rounded once to float32), then +inf.
+ * All of it is a function of the point set and the query alone: two calls give identical bytes, and permuting the
+ * point rows permutes the rows named in index and changes nothing else unless two keys tie in their distance bits.
+ *
+ * Moments over the k nearest (m3_knn_moments): the neighbourhood of i is i and its `found` nearest others; count =
+ * found + 1 and the nine sums of q = rint(d * scale) as for m3_cloud_neighbors; count 0 and zeros for a point that is
+ * not finite or out of range.  m3_cloud_normals consumes them unchanged.  Where no point has more than k others within
+ * r, count and moments are those of m3_cloud_neighbors byte for byte.
+ *
+ * Statistical filter, in integers.  A row is complete when found == k.  For a complete row i
+ *     D_e = rint(d2_e * factor), factor = 2^32 / ((double)r * (double)r) computed once by the host in float64 (d2 the
+ *     float64 value recomputed as above, not dist2), s_e = floor(sqrt(D_e)) exactly (an integer check corrects the
+ *     floating square root), q_i = sum of s_e over the k neighbours <= 64 * 2^16 = 2^22: the mean distance to the k
+ *     nearest in units of r / (k 2^16).
+ * Rows that are not complete - points that are not finite among them - have q = -1.  The device adds up n = the
+ * complete rows, S1 = sum q and S2 = sum q^2 over them, S2 as two words, S2 = S2lo + 2^32 S2hi with S2lo the sum of
+ * q^2 mod 2^32 and S2hi the sum of floor(q^2 / 2^32).  The host forms, in float64 from exact integers,
+ *     mu = S1 / n,  var = (n S2 - S1^2) / (n (n - 1)) (0 for n < 2),  T = mu + std_ratio * sqrt(var),
+ * and a row is kept <=> it is complete and q_i <= floor(T) (the device gets min(floor(T), 2^31 - 1) as `threshold`).
+ * Kept rows come in input order.  Against Open3D's remove_statistical_outlier: a point with fewer than k others within
+ * r is dropped and takes no part in mu and var, and distances are these integers; where every point is complete the
+ * selection is Open3D's up to arithmetic.
+ *
+ * m3_knn_query: m3_knn_launches() = 7 launches whatever the cloud holds - the six that build the index, exactly those of
+ * m3_cloud_neighbors, then one query kernel: one query per thread (self mode in the order of the cell-sorted list),
+ * the k best keys in LDS, [k][threads] 64-bit words, 256 threads per workgroup for k <= 16, 128 for k <= 32, 64 above.
+ * Afterwards ws int32 [0], [1] are as after m3_cloud_neighbors and [3] = the queries out of range.
+ * m3_knn_moments: one launch, no workspace.  m3_knn_mean_distance: one launch; q int32 [M]; it ADDS to the header of a
+ * ws that m3_knn_query has just filled (the index build cleared it): int32 [4] = n, uint64 at bytes 24, 32, 40 = S1,
+ * S2lo, S2hi.  The host reads the 64-byte header once.  m3_knn_stat_count / m3_knn_stat_scatter: as
+ * m3_cloud_radius_count / m3_cloud_radius_scatter with the predicate 0 <= q <= threshold; ws int32 [2] = M2.
+ * No entry point allocates or synchronises with the host: each can be captured into a graph.  Every range and row read
+ * from ws or index is bounds-checked: a stale ws gives wrong numbers, not a fault.
+ * M3_ERR_INVALID_ARG, before any HIP call, as for the entry points above, and for k outside 1 ... 64, Q outside
+ * 0 ... 2^30, queries NULL with Q != M, a factor that is not finite and > 0, threshold < 0.
+ *
+ * Left out: unbounded k-NN, normal propagation over a minimum spanning tree, per-point radii, cross queries sorted
+ * through an index of their own. */
+int m3_knn_launches(void);
+int m3_knn_query(const float *points, int64_t M, float radius, const float *queries, int64_t Q, int k, int32_t *index,
+                 float *dist2, int32_t *found, void *ws, int64_t ws_bytes, void *stream);
+int m3_knn_moments(const float *points, int64_t M, float radius, double scale, const int32_t *index, const int32_t *found,
+                   int k, int32_t *count, int64_t *moments, void *stream);
+int m3_knn_mean_distance(const float *points, int64_t M, double factor, const int32_t *index, const int32_t *found, int k,
+                         int32_t *q, void *ws, int64_t ws_bytes, void *stream);
+int m3_knn_stat_count(const int32_t *q, int64_t M, int threshold, void *ws, int64_t ws_bytes, void *stream);
+int m3_knn_stat_scatter(const float *points, const uint8_t *colors, const int64_t *index, const int32_t *q, int64_t M,
+                        int threshold, const void *ws, int64_t ws_bytes, int64_t M2, float *points_out, uint8_t *colors_out,
+                        int64_t *index_out, int64_t *rows_out, void *stream);
 
 /* ---------------------------------------------------------- camera intrinsics */
 

@@ -26,8 +26,12 @@
 //
 // ws: int32 [16] header | tile int32 [ceil((S + 1) / 256)] | start int32 [S + 1] | keys uint64 [S] | slot uint32 [M] |
 // rank int32 [M] | sslot uint32 [M] | sorted 16 bytes [M]; S = the power of two >= max(1024, 2 M).  Header words:
-// [0] points out of range, [1] points that have a cell (the total of the scan), [2] rows the radius filter keeps; the
-// others are 0.  The radius filter keeps its tile offsets in the tile array.
+// [0] points out of range, [1] points that have a cell (the total of the scan), [2] rows a filter keeps, [3] k-NN
+// queries out of range, [4] complete rows of the statistical filter, bytes 24 ... 47 its three 64-bit sums; the others
+// are 0.  The filters keep their tile offsets in the tile array.
+//
+// On the same index: the k nearest within the radius - the six build launches and one query
+// kernel of its own - and on top of them the statistical outlier filter and the moments over the k nearest.
 //
 // Compiled with -ffp-contract=off: every float64 operation of the rule is rounded on its own.
 #include "common.h"
@@ -112,6 +116,16 @@ __device__ __forceinline__ unsigned long long cell_key(int bx, int by, int bz) {
 
 __device__ __forceinline__ bool finite3(float x, float y, float z) { return isfinite(x) && isfinite(y) && isfinite(z); }
 
+// Biased cell coordinates of a finite point or query; false when one of them reaches +-2^20: out of range.
+__device__ __forceinline__ bool cell_of(float x, float y, float z, double h, int &bx, int &by, int &bz) {
+    const double cx = floor((double)x / h), cy = floor((double)y / h), cz = floor((double)z / h);
+    if (!(fabs(cx) < kCellLim && fabs(cy) < kCellLim && fabs(cz) < kCellLim)) return false;
+    bx = (int)cx + kCellBias;
+    by = (int)cy + kCellBias;
+    bz = (int)cz + kCellBias;
+    return true;
+}
+
 // Header, tiles, cell counts and keys are cleared by a kernel, 16 bytes per thread: a captured memset left its words
 // uncleared on replay.  int4 [0, a) = 0, [a, n) = ff ..
 __global__ void __launch_bounds__(kThreads) k_cl_clear(int4 *__restrict__ ws, int64_t a, int64_t n) {
@@ -135,10 +149,10 @@ __global__ void __launch_bounds__(kThreads) k_cl_insert(const float *__restrict_
         uint32_t mine = kNoSlot;
         int32_t r = 0;
         if (finite3(x, y, z)) {
-            const double cx = floor((double)x / h), cy = floor((double)y / h), cz = floor((double)z / h);
-            far = !(fabs(cx) < kCellLim && fabs(cy) < kCellLim && fabs(cz) < kCellLim);
+            int bx, by, bz;
+            far = !cell_of(x, y, z, h, bx, by, bz);
             if (!far) {
-                const unsigned long long key = cell_key((int)cx + kCellBias, (int)cy + kCellBias, (int)cz + kCellBias);
+                const unsigned long long key = cell_key(bx, by, bz);
                 const unsigned long long mask = (unsigned long long)(S - 1);
                 unsigned long long s = mix64(key) & mask;
                 for (int64_t probe = 0; probe < S; ++probe) {                   // the table is at most half full: this ends
@@ -159,7 +173,7 @@ __global__ void __launch_bounds__(kThreads) k_cl_insert(const float *__restrict_
         slot[i] = mine;
         rank[i] = r;
         if (mine == kNoSlot) {
-            count[i] = 0;
+            if (count) count[i] = 0;                                            // NULL: the index alone is built (k-NN)
             if (moments) {
 #pragma unroll
                 for (int k = 0; k < 9; ++k) moments[9 * i + k] = 0;
@@ -386,21 +400,22 @@ __global__ void __launch_bounds__(kThreads) k_cl_normals(const float *__restrict
     if (variation) variation[i] = var;
 }
 
-// ---- radius filter ---------------------------------------------------------------------------------------------------
-// Bits of the thread's four consecutive rows that have more than min_neighbors points in their set: themselves and
-// min_neighbors others at least.
-__device__ __forceinline__ unsigned kept_rows(const int32_t *__restrict__ count, int64_t i0, int64_t M, int min_neighbors) {
+// ---- the filters' ordered compaction ---------------------------------------------------------------------------------
+// Bits of the thread's four consecutive rows whose value v has lo < v <= hi.  The radius filter: v = count, lo =
+// min_neighbors (the point itself and min_neighbors others at least), hi = INT32_MAX.  The statistical filter: v = q,
+// lo = -1 (a complete row), hi = floor(T).
+__device__ __forceinline__ unsigned kept_rows(const int32_t *__restrict__ v, int64_t i0, int64_t M, int lo, int hi) {
     unsigned keep = 0;
 #pragma unroll
     for (int j = 0; j < kPts; ++j) {
-        if (i0 + j < M && count[i0 + j] > min_neighbors) keep |= 1u << j;
+        if (i0 + j < M && v[i0 + j] > lo && v[i0 + j] <= hi) keep |= 1u << j;
     }
     return keep;
 }
 
-__global__ void __launch_bounds__(kThreads) k_cl_keep_count(const int32_t *__restrict__ count, int64_t M, int min_neighbors,
+__global__ void __launch_bounds__(kThreads) k_cl_keep_count(const int32_t *__restrict__ count, int64_t M, int lo, int hi,
                                                              int32_t *__restrict__ cnt) {
-    const unsigned keep = kept_rows(count, (int64_t)blockIdx.x * kTile + threadIdx.x * kPts, M, min_neighbors);
+    const unsigned keep = kept_rows(count, (int64_t)blockIdx.x * kTile + threadIdx.x * kPts, M, lo, hi);
     int total;
     block_prefix(keep, total);
     if (threadIdx.x == 0) cnt[blockIdx.x] = total;
@@ -409,13 +424,13 @@ __global__ void __launch_bounds__(kThreads) k_cl_keep_count(const int32_t *__res
 __global__ void __launch_bounds__(kThreads) k_cl_keep_scatter(const float *__restrict__ points,
                                                                const unsigned char *__restrict__ colors,
                                                                const int64_t *__restrict__ index,
-                                                               const int32_t *__restrict__ count, int64_t M, int min_neighbors,
+                                                               const int32_t *__restrict__ count, int64_t M, int lo, int hi,
                                                                const int32_t *__restrict__ offs, int64_t M2,
                                                                float *__restrict__ points_out,
                                                                unsigned char *__restrict__ colors_out,
                                                                int64_t *__restrict__ index_out, int64_t *__restrict__ rows_out) {
     const int64_t i0 = (int64_t)blockIdx.x * kTile + threadIdx.x * kPts;
-    const unsigned keep = kept_rows(count, i0, M, min_neighbors);
+    const unsigned keep = kept_rows(count, i0, M, lo, hi);
     int total;
     int64_t o = (int64_t)offs[blockIdx.x] + block_prefix(keep, total);
 #pragma unroll
@@ -433,9 +448,298 @@ __global__ void __launch_bounds__(kThreads) k_cl_keep_scatter(const float *__res
     }
 }
 
+// ---- k nearest within the radius -------------------------------------------------------------------------------------
+// One query per thread.  Self mode (CROSS false): thread t takes entry t of the cell-sorted list, as k_cl_query does,
+// so the lanes that share a cell walk the same ranges; as row t it also writes the empty outputs of a point without a
+// cell, which is in no list.  Cross mode: thread t takes query row t, and its lanes diverge over the cells.
+//
+// The k best keys live in LDS, column layout [k][THREADS] of 64-bit words: entry e of lane l is word e * THREADS + l,
+// so a wave's access to one entry is 512 contiguous bytes and no lane ever touches another's column - no barrier.  The
+// worst key of the list and its position stay in registers: a candidate costs d2, the radius test and one 64-bit
+// compare; only one that enters pays the scan of k words for the new worst.  The list is sorted once at the end
+// (insertion sort in LDS) and written out with d2 recomputed from the stored rows.
+// THREADS falls as k grows - 256 up to k = 16, 128 up to 32, 64 up to 64 - so that a workgroup never holds more than
+// 8 k THREADS <= 32 KB of the CU's 160 KB and five workgroups fit whatever k is (the launch passes exactly 8 k THREADS).
+constexpr int kKnnMaxK = 64;
+constexpr unsigned long long kRowMask = (1ull << 30) - 1;                       // the low 30 bits of a key: the row
+constexpr int kQueriesFar = 3, kComplete = 4;                                   // header words (int32)
+constexpr int kSumQ = 3, kSumQQLo = 4, kSumQQHi = 5;                            // header words (uint64): bytes 24 ... 47
+
+__device__ __forceinline__ unsigned long long knn_key(double d2, int32_t j) {
+    return ((unsigned long long)__double_as_longlong(d2) & ~kRowMask) | ((unsigned long long)(uint32_t)j & kRowMask);
+}
+
+__device__ __forceinline__ void knn_empty(int64_t row, int k, int32_t *__restrict__ index, float *__restrict__ dist2,
+                                          int32_t *__restrict__ found, int from = 0) {
+    for (int e = from; e < k; ++e) {
+        index[row * k + e] = -1;
+        dist2[row * k + e] = INFINITY;
+    }
+    if (from == 0) found[row] = 0;
+}
+
+template <int THREADS, bool CROSS>
+__global__ void __launch_bounds__(THREADS) k_knn_query(const float *__restrict__ points, const float *__restrict__ queries,
+                                                        int64_t Q, const Ent *__restrict__ sorted,
+                                                        const uint32_t *__restrict__ sslot, const uint32_t *__restrict__ slot,
+                                                        const int32_t *__restrict__ start,
+                                                        const unsigned long long *__restrict__ keys, int64_t S, int64_t M,
+                                                        int32_t *__restrict__ hdr, double h, double r2, int k,
+                                                        int32_t *__restrict__ index, float *__restrict__ dist2,
+                                                        int32_t *__restrict__ found) {
+    extern __shared__ unsigned long long knn_lds[];
+    unsigned long long *mine = knn_lds + threadIdx.x;                           // entry e: mine[e * THREADS]
+    const int64_t t = (int64_t)blockIdx.x * THREADS + threadIdx.x;
+    const int64_t n_in = hdr[kInCells] < M ? hdr[kInCells] : M;
+    const unsigned long long mask = (unsigned long long)(S - 1);
+    bool active = false, far = false;
+    int64_t row = 0;
+    int32_t self = -1;
+    uint32_t s0 = kNoSlot;
+    float qx = 0.f, qy = 0.f, qz = 0.f;
+    int bx = 0, by = 0, bz = 0;
+    if (CROSS) {
+        if (t < Q) {
+            row = t;
+            qx = queries[3 * t], qy = queries[3 * t + 1], qz = queries[3 * t + 2];
+            if (finite3(qx, qy, qz)) {
+                active = cell_of(qx, qy, qz, h, bx, by, bz);
+                far = !active;
+            }
+            if (!active) knn_empty(row, k, index, dist2, found);
+        }
+        const unsigned long long b = __ballot(far);
+        if (b && (threadIdx.x & 63) == 0) atomicAdd(hdr + kQueriesFar, (int)__popcll(b));
+    } else {
+        if (t < M && slot[t] == kNoSlot) knn_empty(t, k, index, dist2, found);
+        if (t < n_in) {
+            const Ent me = sorted[t];
+            s0 = sslot[t];
+            if ((int64_t)s0 < S && me.i >= 0 && me.i < M) {                     // always, for a ws from the same points
+                active = true;
+                row = self = me.i;
+                qx = me.x, qy = me.y, qz = me.z;
+                const unsigned long long key = keys[s0];
+                bx = (int)(key >> 42) & kCellMask, by = (int)(key >> 21) & kCellMask, bz = (int)key & kCellMask;
+            }
+        }
+    }
+    if (!active) return;
+    const double px = (double)qx, py = (double)qy, pz = (double)qz;
+    int cnt = 0, wpos = 0;
+    unsigned long long worst = 0;
+#pragma unroll 1
+    for (int c = 0; c < 27; ++c) {
+        const int ox = c % 3 - 1, oy = (c / 3) % 3 - 1, oz = c / 9 - 1;
+        const int nx = bx + ox, ny = by + oy, nz = bz + oz;
+        if (nx < 1 || nx > kCellMask || ny < 1 || ny > kCellMask || nz < 1 || nz > kCellMask) continue;   // holds no point
+        int64_t b = 0, e = 0;
+        const unsigned long long want = cell_key(nx, ny, nz);
+        unsigned long long s = !CROSS && c == 13 ? (unsigned long long)s0 : mix64(want) & mask;
+        for (int64_t probe = 0; probe < S; ++probe) {
+            const unsigned long long cur = keys[s];
+            if (cur == want) {
+                b = start[s];
+                e = start[s + 1];
+                break;
+            }
+            if (cur == kEmptyKey) break;
+            s = (s + 1) & mask;
+        }
+        if (b < 0 || e < b || e > n_in) b = e = 0;                              // never, for a ws from the same points
+        for (int64_t kk = b; kk < e; ++kk) {
+            const Ent q = sorted[kk];
+            const double dx = (double)q.x - px, dy = (double)q.y - py, dz = (double)q.z - pz;
+            const double d2 = (dx * dx + dy * dy) + dz * dz;
+            if (!(d2 <= r2) || (!CROSS && q.i == self)) continue;
+            const unsigned long long key = knn_key(d2, q.i);
+            if (cnt < k) {
+                mine[cnt * THREADS] = key;
+                if (cnt == 0 || key > worst) worst = key, wpos = cnt;
+                ++cnt;
+            } else if (key < worst) {
+                mine[wpos * THREADS] = key;
+                worst = mine[0], wpos = 0;
+                for (int a = 1; a < k; ++a) {
+                    const unsigned long long v = mine[a * THREADS];
+                    if (v > worst) worst = v, wpos = a;
+                }
+            }
+        }
+    }
+    for (int a = 1; a < cnt; ++a) {
+        const unsigned long long v = mine[a * THREADS];
+        int at = a;
+        while (at > 0 && mine[(at - 1) * THREADS] > v) {
+            mine[at * THREADS] = mine[(at - 1) * THREADS];
+            --at;
+        }
+        mine[at * THREADS] = v;
+    }
+    for (int a = 0; a < cnt; ++a) {
+        const int64_t j = (int64_t)(mine[a * THREADS] & kRowMask);
+        double d2 = (double)INFINITY;
+        if (j < M) {                                                            // always, for a ws from the same points
+            const double dx = (double)points[3 * j] - px, dy = (double)points[3 * j + 1] - py, dz = (double)points[3 * j + 2] - pz;
+            d2 = (dx * dx + dy * dy) + dz * dz;
+        }
+        index[row * k + a] = (int32_t)j;
+        dist2[row * k + a] = (float)d2;
+    }
+    knn_empty(row, k, index, dist2, found, cnt);
+    found[row] = cnt;
+}
+
+// count = found + 1 and the nine moments of a point and its k nearest others, with the quantisation of k_cl_query; a
+// point without a cell gets zeros, as k_cl_insert gives it.  The point's own offset is 0 and adds nothing.
+__global__ void __launch_bounds__(kThreads) k_knn_moments(const float *__restrict__ points, int64_t M, double h, double scale,
+                                                           const int32_t *__restrict__ index, const int32_t *__restrict__ found,
+                                                           int k, int32_t *__restrict__ count, int64_t *__restrict__ moments) {
+    const int64_t i = row_of();
+    if (i >= M) return;
+    const float x = points[3 * i], y = points[3 * i + 1], z = points[3 * i + 2];
+    int bx, by, bz;
+    const bool has = finite3(x, y, z) && cell_of(x, y, z, h, bx, by, bz);
+    const int n = has ? min(max(found[i], 0), k) : 0;
+    const double px = (double)x, py = (double)y, pz = (double)z;
+    int64_t a[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    for (int e = 0; e < n; ++e) {
+        const int64_t j = index[i * k + e];
+        if (j < 0 || j >= M) continue;                                          // never, for an index of the same points
+        const int qx = (int)rint(((double)points[3 * j] - px) * scale), qy = (int)rint(((double)points[3 * j + 1] - py) * scale),
+                  qz = (int)rint(((double)points[3 * j + 2] - pz) * scale);
+        a[0] += qx;
+        a[1] += qy;
+        a[2] += qz;
+        a[3] += (int64_t)qx * qx;
+        a[4] += (int64_t)qx * qy;
+        a[5] += (int64_t)qx * qz;
+        a[6] += (int64_t)qy * qy;
+        a[7] += (int64_t)qy * qz;
+        a[8] += (int64_t)qz * qz;
+    }
+    count[i] = has ? n + 1 : 0;
+#pragma unroll
+    for (int m = 0; m < 9; ++m) moments[9 * i + m] = a[m];
+}
+
+__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// q of the statistical filter: the sum over a complete row's k neighbours of floor(sqrt(rint(d2 factor))), factor =
+// 2^32 / r^2; -1 for a row that is not complete.  n, sum q and sum q^2 - the latter as the sums of its low and its high
+// 32 bits, each below 2^62 - go to the header by integer atomics of per-wave sums: they commute.
+__global__ void __launch_bounds__(kThreads) k_knn_mean_distance(const float *__restrict__ points, int64_t M, double factor,
+                                                                 const int32_t *__restrict__ index,
+                                                                 const int32_t *__restrict__ found, int k,
+                                                                 int32_t *__restrict__ q, int32_t *__restrict__ hdr) {
+    const int64_t i = row_of();
+    int64_t sum = -1;
+    if (i < M && found[i] == k) {
+        const double px = (double)points[3 * i], py = (double)points[3 * i + 1], pz = (double)points[3 * i + 2];
+        sum = 0;
+        for (int e = 0; e < k; ++e) {
+            const int64_t j = index[i * k + e];
+            if (j < 0 || j >= M) continue;                                      // never, for an index of the same points
+            const double dx = (double)points[3 * j] - px, dy = (double)points[3 * j + 1] - py, dz = (double)points[3 * j + 2] - pz;
+            const double D = rint(((dx * dx + dy * dy) + dz * dz) * factor);
+            // D <= 2^32 + 1 for d2 <= r r; anything else (a stale index) is clamped, so that the sum stays an int32
+            const int64_t Di = D >= 0.0 && D <= 4294967297.0 ? (int64_t)D : 0;
+            int64_t s = (int64_t)sqrt((double)Di);
+            while (s * s > Di) --s;
+            while ((s + 1) * (s + 1) <= Di) ++s;
+            sum += s;
+        }
+        q[i] = (int32_t)sum;
+    } else if (i < M) {
+        q[i] = -1;
+    }
+    const bool complete = sum >= 0;
+    const unsigned long long b = __ballot(complete);
+    if (!b) return;
+    const unsigned long long v = complete ? (unsigned long long)sum : 0ull, vv = v * v;
+    const unsigned long long s1 = wave_sum(v), lo = wave_sum(vv & 0xffffffffull), hi = wave_sum(vv >> 32);
+    if ((threadIdx.x & 63) == 0) {
+        unsigned long long *h64 = (unsigned long long *)hdr;
+        atomicAdd(hdr + kComplete, (int)__popcll(b));
+        atomicAdd(h64 + kSumQ, s1);
+        atomicAdd(h64 + kSumQQLo, lo);
+        atomicAdd(h64 + kSumQQHi, hi);
+    }
+}
+
 inline bool ws_ok(const void *ws) { return ws && ((uintptr_t)ws & 15) == 0; }
 inline bool aligned(const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 inline int64_t keep_tiles(int64_t M) { return M ? (M + kTile - 1) / kTile : 1; }
+inline bool radius_ok(float radius) { return radius > 0.f && radius < INFINITY; }                    // NaN fails
+inline double cell_edge(float radius) { return (double)radius * (1.0 + 0x1p-10); }
+
+// The six launches that build the index: the same for the counting query and the k-NN query.  count / moments: where
+// a point without a cell gets its zeros, or NULL.
+void launch_index(hipStream_t st, const float *points, int64_t M, float radius, void *ws, const ClWs &m, int32_t *count,
+                  int64_t *moments) {
+    const ClPtr p = cl_ptr(ws, m);
+    const dim3 block(kThreads);
+    const dim3 tiles((unsigned)m.ntile);
+    hipLaunchKernelGGL(k_cl_clear, grid_of(m.slot / 16), block, 0, st, (int4 *)ws, m.keys / 16, m.slot / 16);
+    // M = 0: no thread has a row.  The launches are kept so that their number is fixed.
+    hipLaunchKernelGGL(k_cl_insert, grid_of(M), block, 0, st, points, M, cell_edge(radius), p.keys, p.start, m.S, p.slot, p.rank,
+                       count, moments, p.hdr);
+    hipLaunchKernelGGL(k_cl_tile_counts, tiles, block, 0, st, p.start, m.S + 1, p.tile);
+    launch_scan(st, p.hdr + kInCells, ScanJob{p.tile, m.ntile});
+    hipLaunchKernelGGL(k_cl_starts, tiles, block, 0, st, p.start, m.S + 1, p.tile);
+    hipLaunchKernelGGL(k_cl_fill, grid_of(M), block, 0, st, points, M, p.slot, p.rank, p.start, m.S, p.sorted, p.sslot);
+}
+
+template <int THREADS>
+void launch_knn(hipStream_t st, const float *points, int64_t M, const float *queries, int64_t Q, const ClPtr &p, const ClWs &m,
+                float radius, int k, int32_t *index, float *dist2, int32_t *found) {
+    const double r = (double)radius;
+    const dim3 grid((unsigned)(Q ? (Q + THREADS - 1) / THREADS : 1));
+    const size_t lds = sizeof(unsigned long long) * (size_t)k * THREADS;
+    if (queries)
+        hipLaunchKernelGGL((k_knn_query<THREADS, true>), grid, dim3(THREADS), lds, st, points, queries, Q, p.sorted, p.sslot, p.slot,
+                           p.start, p.keys, m.S, M, p.hdr, cell_edge(radius), r * r, k, index, dist2, found);
+    else
+        hipLaunchKernelGGL((k_knn_query<THREADS, false>), grid, dim3(THREADS), lds, st, points, queries, Q, p.sorted, p.sslot, p.slot,
+                           p.start, p.keys, m.S, M, p.hdr, cell_edge(radius), r * r, k, index, dist2, found);
+}
+
+// The two launches that count the rows a filter keeps, and the one that moves them.
+void launch_keep_count(hipStream_t st, const int32_t *v, int64_t M, int lo, int hi, const ClPtr &p) {
+    const int64_t tiles = keep_tiles(M);                                        // <= ntile: the offsets fit the tile array
+    hipLaunchKernelGGL(k_cl_keep_count, dim3((unsigned)tiles), dim3(kThreads), 0, st, v, M, lo, hi, p.tile);
+    launch_scan(st, p.hdr + kKept, ScanJob{p.tile, tiles});
+}
+
+struct KeepArgs {
+    const float *points;
+    const uint8_t *colors;
+    const int64_t *index;
+    const int32_t *v;
+    int64_t M, M2;
+    const void *ws;
+    int64_t ws_bytes;
+    float *points_out;
+    uint8_t *colors_out;
+    int64_t *index_out, *rows_out;
+};
+
+inline bool keep_args_ok(const KeepArgs &a, ClWs &m) {
+    return cl_layout(a.M, m) && ws_ok(a.ws) && a.ws_bytes >= m.bytes && a.M2 >= 0 && a.M2 <= a.M &&
+           ((a.points && a.v) || a.M == 0) && (a.points_out || a.M2 == 0) && (a.colors != nullptr) == (a.colors_out != nullptr) &&
+           (!a.index || a.index_out) && aligned(a.points, 4) && aligned(a.v, 4) && aligned(a.points_out, 4) &&
+           aligned(a.index, 8) && aligned(a.index_out, 8) && aligned(a.rows_out, 8);
+}
+
+void launch_keep_scatter(hipStream_t st, const KeepArgs &a, const ClWs &m, int lo, int hi) {
+    const ClPtr p = cl_ptr(const_cast<void *>(a.ws), m);
+    hipLaunchKernelGGL(k_cl_keep_scatter, dim3((unsigned)keep_tiles(a.M)), dim3(kThreads), 0, st, a.points, a.colors, a.index, a.v,
+                       a.M, lo, hi, p.tile, a.M2, a.points_out, a.colors_out, a.index_out, a.rows_out);
+}
 
 }  // namespace
 
@@ -458,16 +762,8 @@ int m3_cloud_neighbors(const float *points, int64_t M, float radius, double scal
     hipStream_t st = (hipStream_t)stream;
     const ClPtr p = cl_ptr(ws, m);
     const dim3 block(kThreads);
-    const dim3 tiles((unsigned)m.ntile);
-    const double r = (double)radius, h = r * (1.0 + 0x1p-10);
-    hipLaunchKernelGGL(k_cl_clear, grid_of(m.slot / 16), block, 0, st, (int4 *)ws, m.keys / 16, m.slot / 16);
-    // M = 0: no thread has a row.  The launches are kept so that their number is fixed.
-    hipLaunchKernelGGL(k_cl_insert, grid_of(M), block, 0, st, points, M, h, p.keys, p.start, m.S, p.slot, p.rank, count,
-                       moments, p.hdr);
-    hipLaunchKernelGGL(k_cl_tile_counts, tiles, block, 0, st, p.start, m.S + 1, p.tile);
-    launch_scan(st, p.hdr + kInCells, ScanJob{p.tile, m.ntile});
-    hipLaunchKernelGGL(k_cl_starts, tiles, block, 0, st, p.start, m.S + 1, p.tile);
-    hipLaunchKernelGGL(k_cl_fill, grid_of(M), block, 0, st, points, M, p.slot, p.rank, p.start, m.S, p.sorted, p.sslot);
+    const double r = (double)radius;
+    launch_index(st, points, M, radius, ws, m, count, moments);
     if (moments)
         hipLaunchKernelGGL(k_cl_query<true>, grid_of(M), block, 0, st, p.sorted, p.sslot, p.start, p.keys, m.S, M, p.hdr,
                            r * r, scale, count, moments);
@@ -494,11 +790,7 @@ int m3_cloud_radius_count(const int32_t *count, int64_t M, int min_neighbors, vo
     ClWs m;
     M3_REQUIRE(cl_layout(M, m) && ws_ok(ws) && ws_bytes >= m.bytes);
     M3_REQUIRE((count || M == 0) && aligned(count, 4) && min_neighbors >= 0);
-    hipStream_t st = (hipStream_t)stream;
-    const ClPtr p = cl_ptr(ws, m);
-    const int64_t tiles = keep_tiles(M);                                        // <= ntile: the offsets fit the tile array
-    hipLaunchKernelGGL(k_cl_keep_count, dim3((unsigned)tiles), dim3(kThreads), 0, st, count, M, min_neighbors, p.tile);
-    launch_scan(st, p.hdr + kKept, ScanJob{p.tile, tiles});
+    launch_keep_count((hipStream_t)stream, count, M, min_neighbors, INT32_MAX, cl_ptr(ws, m));
     M3_CHECK_LAUNCH("m3_cloud_radius_count");
     return M3_OK;
 }
@@ -507,16 +799,73 @@ int m3_cloud_radius_scatter(const float *points, const uint8_t *colors, const in
                             int64_t M, int min_neighbors, const void *ws, int64_t ws_bytes, int64_t M2, float *points_out,
                             uint8_t *colors_out, int64_t *index_out, int64_t *rows_out, void *stream) {
     ClWs m;
-    M3_REQUIRE(cl_layout(M, m) && ws_ok(ws) && ws_bytes >= m.bytes);
-    M3_REQUIRE(M2 >= 0 && M2 <= M && ((points && count) || M == 0) && (points_out || M2 == 0) && min_neighbors >= 0);
-    M3_REQUIRE((colors != nullptr) == (colors_out != nullptr) && (!index || index_out));
-    M3_REQUIRE(aligned(points, 4) && aligned(count, 4) && aligned(points_out, 4) && aligned(index, 8) && aligned(index_out, 8) &&
-               aligned(rows_out, 8));
-    const ClPtr p = cl_ptr(const_cast<void *>(ws), m);
-    hipLaunchKernelGGL(k_cl_keep_scatter, dim3((unsigned)keep_tiles(M)), dim3(kThreads), 0, (hipStream_t)stream, points, colors,
-                       index, count, M, min_neighbors, p.tile, M2, points_out, colors_out, index_out, rows_out);
+    const KeepArgs a{points, colors, index, count, M, M2, ws, ws_bytes, points_out, colors_out, index_out, rows_out};
+    M3_REQUIRE(keep_args_ok(a, m) && min_neighbors >= 0);
+    launch_keep_scatter((hipStream_t)stream, a, m, min_neighbors, INT32_MAX);
     M3_CHECK_LAUNCH("m3_cloud_radius_scatter");
     return M3_OK;
 }
 
+int m3_knn_launches(void) { return kBuildLaunches; }
+
+int m3_knn_query(const float *points, int64_t M, float radius, const float *queries, int64_t Q, int k, int32_t *index,
+                 float *dist2, int32_t *found, void *ws, int64_t ws_bytes, void *stream) {
+    ClWs m;
+    M3_REQUIRE(cl_layout(M, m) && ws_ok(ws) && ws_bytes >= m.bytes && radius_ok(radius) && k >= 1 && k <= kKnnMaxK);
+    M3_REQUIRE(Q >= 0 && Q <= kMaxM && (queries || Q == M) && (points || M == 0) && ((index && dist2 && found) || Q == 0));
+    M3_REQUIRE(aligned(points, 4) && aligned(queries, 4) && aligned(index, 4) && aligned(dist2, 4) && aligned(found, 4));
+    hipStream_t st = (hipStream_t)stream;
+    const ClPtr p = cl_ptr(ws, m);
+    launch_index(st, points, M, radius, ws, m, nullptr, nullptr);
+    if (k <= 16) launch_knn<256>(st, points, M, queries, Q, p, m, radius, k, index, dist2, found);
+    else if (k <= 32) launch_knn<128>(st, points, M, queries, Q, p, m, radius, k, index, dist2, found);
+    else launch_knn<64>(st, points, M, queries, Q, p, m, radius, k, index, dist2, found);
+    M3_CHECK_LAUNCH("m3_knn_query");
+    return M3_OK;
+}
+
+int m3_knn_moments(const float *points, int64_t M, float radius, double scale, const int32_t *index, const int32_t *found,
+                   int k, int32_t *count, int64_t *moments, void *stream) {
+    M3_REQUIRE(M >= 0 && M <= kMaxM && ((points && index && found && count && moments) || M == 0) && k >= 1 && k <= kKnnMaxK);
+    M3_REQUIRE(aligned(points, 4) && aligned(index, 4) && aligned(found, 4) && aligned(count, 4) && aligned(moments, 8));
+    M3_REQUIRE(radius_ok(radius) && scale > 0.0 && scale < (double)INFINITY && scale * (double)radius <= 2097152.0);
+    hipLaunchKernelGGL(k_knn_moments, grid_of(M), dim3(kThreads), 0, (hipStream_t)stream, points, M, cell_edge(radius), scale,
+                       index, found, k, count, moments);
+    M3_CHECK_LAUNCH("m3_knn_moments");
+    return M3_OK;
+}
+
+int m3_knn_mean_distance(const float *points, int64_t M, double factor, const int32_t *index, const int32_t *found, int k,
+                         int32_t *q, void *ws, int64_t ws_bytes, void *stream) {
+    ClWs m;
+    M3_REQUIRE(cl_layout(M, m) && ws_ok(ws) && ws_bytes >= m.bytes && k >= 1 && k <= kKnnMaxK);
+    M3_REQUIRE(((points && index && found && q) || M == 0) && factor > 0.0 && factor < (double)INFINITY);
+    M3_REQUIRE(aligned(points, 4) && aligned(index, 4) && aligned(found, 4) && aligned(q, 4));
+    hipLaunchKernelGGL(k_knn_mean_distance, grid_of(M), dim3(kThreads), 0, (hipStream_t)stream, points, M, factor, index, found,
+                       k, q, cl_ptr(ws, m).hdr);
+    M3_CHECK_LAUNCH("m3_knn_mean_distance");
+    return M3_OK;
+}
+
+int m3_knn_stat_count(const int32_t *q, int64_t M, int threshold, void *ws, int64_t ws_bytes, void *stream) {
+    ClWs m;
+    M3_REQUIRE(cl_layout(M, m) && ws_ok(ws) && ws_bytes >= m.bytes);
+    M3_REQUIRE((q || M == 0) && aligned(q, 4) && threshold >= 0);
+    launch_keep_count((hipStream_t)stream, q, M, -1, threshold, cl_ptr(ws, m));
+    M3_CHECK_LAUNCH("m3_knn_stat_count");
+    return M3_OK;
+}
+
+int m3_knn_stat_scatter(const float *points, const uint8_t *colors, const int64_t *index, const int32_t *q, int64_t M,
+                        int threshold, const void *ws, int64_t ws_bytes, int64_t M2, float *points_out, uint8_t *colors_out,
+                        int64_t *index_out, int64_t *rows_out, void *stream) {
+    ClWs m;
+    const KeepArgs a{points, colors, index, q, M, M2, ws, ws_bytes, points_out, colors_out, index_out, rows_out};
+    M3_REQUIRE(keep_args_ok(a, m) && threshold >= 0);
+    launch_keep_scatter((hipStream_t)stream, a, m, -1, threshold);
+    M3_CHECK_LAUNCH("m3_knn_stat_scatter");
+    return M3_OK;
+}
+
 }  // extern "C"
+

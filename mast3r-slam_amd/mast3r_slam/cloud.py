@@ -19,10 +19,20 @@ are built on it, and are applied to what collect_map / SLAM.reconstruction retur
 
 The exact rule is in include/m3slam.h.  Counts and moments are integer sums over a set: two calls give identical bytes,
 and so do two orders of the input rows.  The filter's threshold counts other points - the project's own rule, close to
-but not claimed to be Open3D's remove_radius_outlier, whose nb_points includes the query.  k-nearest-neighbour queries,
-the statistical (mean k-NN distance) outlier filter, normal propagation over a minimum spanning tree for clouds without
-viewpoints, per-point radii, a `normals=` argument on the driver methods and normals in render_map are left out.  CPU
-tensors raise RuntimeError: there is no CPU path.
+but not claimed to be Open3D's remove_radius_outlier, whose nb_points includes the query.
+
+On the same index: cloud_knn, the k nearest points within a radius of every point or of another
+set of queries; remove_statistical_outliers, which drops the points whose mean distance to their k nearest is more than
+std_ratio deviations above the cloud's mean - a threshold that adapts to the cloud, where the radius filter has one
+absolute one; and cloud_normals_knn, normals over the k nearest instead of everything within the radius.
+
+    order              by key = (bits(d2) & ~(2^30 - 1)) | row, ascending: squared distance to 22 mantissa bits, ties to
+                       the lower row - two candidates whose d2 differ only in the dropped bits are ordered by row
+    q                  the sum over a complete row's k neighbours of floor(sqrt(rint(d2 2^32 / r^2))), an integer
+
+Unbounded k-NN, normal propagation over a minimum spanning tree for clouds without viewpoints, per-point radii, cross
+queries sorted through an index of their own, a `normals=` argument on the driver methods and normals in render_map are
+left out.  CPU tensors raise RuntimeError: there is no CPU path.
 """
 from __future__ import annotations
 
@@ -37,7 +47,7 @@ from . import _ffi
 from .export import _check_workspace, _with_pointmap
 
 __all__ = ["cloud_neighbors", "cloud_normals", "source_viewpoints", "remove_radius_outliers", "CloudNeighbors",
-           "workspace_bytes"]
+           "workspace_bytes", "cloud_knn", "KnnResult", "remove_statistical_outliers", "cloud_normals_knn", "MAX_K"]
 
 CloudNeighbors = namedtuple("CloudNeighbors", ["count", "moments", "out_of_range"])
 CloudNeighbors.__doc__ = ("count int32 [M]: the points within the radius, the point itself included, 0 for a point that is "
@@ -45,7 +55,14 @@ CloudNeighbors.__doc__ = ("count int32 [M]: the points within the radius, the po
                           "offsets times 2^20 / r, rounded) or None; out_of_range: always 0 - the call raises otherwise - "
                           "or None under stream capture, where nothing is read back.")
 
+KnnResult = namedtuple("KnnResult", ["index", "dist2", "found", "out_of_range"])
+KnnResult.__doc__ = ("index int32 [Q,k]: the rows of the nearest points in ascending key order, then -1; dist2 float32 [Q,k]: "
+                     "their squared distances (float64, rounded once), then +inf; found int32 [Q] = min(k, the candidates "
+                     "within the radius); out_of_range: always 0 - the call raises otherwise - or None under stream capture.")
+
 MAX_POINTS = 2 ** 30                                                    # include/m3slam.h
+MAX_K = 64
+_KNN_HDR_WORDS = 16                                                     # + queries out of range, n, S1, S2lo, S2hi
 _HDR_WORDS = 4                                                          # out of range, points in cells, kept rows, 0
 
 
@@ -134,6 +151,27 @@ def cloud_neighbors(points, radius, moments: bool = True, workspace: Optional[to
     return CloudNeighbors(count, mom, None if hdr is None else hdr[0])
 
 
+def _normals_args(points, toward, min_points):
+    """(points, toward, stride), checked as cloud_normals documents."""
+    if isinstance(min_points, bool) or not isinstance(min_points, (int, np.integer)) or min_points < 1 or min_points >= 2 ** 31:
+        raise ValueError(f"min_points must be an integer >= 1, got {min_points!r}")
+    _points(points)
+    m = int(points.shape[0])
+    stride = 0
+    if toward is not None:
+        if not isinstance(toward, torch.Tensor) or toward.dtype != torch.float32 or tuple(toward.shape) not in ((3,), (m, 3)):
+            got = f"{toward.dtype} {tuple(toward.shape)}" if isinstance(toward, torch.Tensor) else type(toward).__name__
+            raise ValueError(f"toward must be a {torch.float32} [3] or [{m},3] tensor, got {got}")
+        stride = 3 if toward.dim() == 2 else 0
+    points = _ffi.check(points, torch.float32, "points")
+    dev = points.device
+    if toward is not None:
+        toward = _ffi.check(toward, torch.float32, "toward")
+        if toward.device != dev:
+            raise ValueError(f"the cloud lives on {dev}, toward on {toward.device}")
+    return points, toward, stride
+
+
 def cloud_normals(points, radius, toward: Optional[torch.Tensor] = None, min_points: int = 3, return_variation: bool = False,
                   workspace: Optional[torch.Tensor] = None):
     """Normals float32 [M,3] of the points float32 [M,3] - or of the whole tuple collect_map / SLAM.reconstruction
@@ -152,22 +190,8 @@ def cloud_normals(points, radius, toward: Optional[torch.Tensor] = None, min_poi
             raise ValueError("a cloud is (points, colors[, index]), passed whole, or the points alone")
         points = points[0]
     r, scale = _radius(radius)
-    if isinstance(min_points, bool) or not isinstance(min_points, (int, np.integer)) or min_points < 1 or min_points >= 2 ** 31:
-        raise ValueError(f"min_points must be an integer >= 1, got {min_points!r}")
-    _points(points)
-    m = int(points.shape[0])
-    stride = 0
-    if toward is not None:
-        if not isinstance(toward, torch.Tensor) or toward.dtype != torch.float32 or tuple(toward.shape) not in ((3,), (m, 3)):
-            got = f"{toward.dtype} {tuple(toward.shape)}" if isinstance(toward, torch.Tensor) else type(toward).__name__
-            raise ValueError(f"toward must be a {torch.float32} [3] or [{m},3] tensor, got {got}")
-        stride = 3 if toward.dim() == 2 else 0
-    points = _ffi.check(points, torch.float32, "points")
-    dev = points.device
-    if toward is not None:
-        toward = _ffi.check(toward, torch.float32, "toward")
-        if toward.device != dev:
-            raise ValueError(f"the cloud lives on {dev}, toward on {toward.device}")
+    points, toward, stride = _normals_args(points, toward, min_points)
+    m, dev = int(points.shape[0]), points.device
     normals = torch.empty((m, 3), dtype=torch.float32, device=dev)
     variation = torch.empty((m,), dtype=torch.float32, device=dev) if return_variation else None
     if m:
@@ -208,15 +232,35 @@ def remove_radius_outliers(points, colors=None, index=None, radius=None, min_nei
     (7 launches), 2 for the kept count, one 16-byte read, one scatter.  ValueError without radius or min_neighbors, for
     min_neighbors < 0, mismatched rows, and ("radius too small for the extent of the cloud") when a point's grid cell
     reaches +-2^20; RuntimeError for CPU tensors."""
-    if isinstance(points, (tuple, list)):
-        if len(points) not in (2, 3) or colors is not None or index is not None:
-            raise ValueError("a cloud is (points, colors[, index]), passed whole or unpacked")
-        points, colors, index = (tuple(points) + (None,))[:3]
+    points, colors, index = _unpack(points, colors, index)
     if radius is None or min_neighbors is None:
         raise ValueError("radius and min_neighbors are required")
     r, scale = _radius(radius)
     if isinstance(min_neighbors, bool) or not isinstance(min_neighbors, (int, np.integer)) or not 0 <= min_neighbors < 2 ** 31 - 1:
         raise ValueError(f"min_neighbors must be an integer >= 0, got {min_neighbors!r}")
+    points, colors, index = _cloud(points, colors, index)
+    m, dev = int(points.shape[0]), points.device
+    m2 = 0
+    ws = count = None
+    if m:
+        ws = _workspace(None, m, dev)
+        count, _ = _neighbors(points, r, scale, False, ws)
+        _ffi.call("m3_cloud_radius_count", _ffi.ptr(count), m, int(min_neighbors), _ffi.ptr(ws), ws.numel(), _ffi.stream_ptr())
+        m2 = _header(ws, r)[2]                                          # the one synchronisation
+    return _scatter("m3_cloud_radius_scatter", points, colors, index, count, int(min_neighbors), ws, m2, return_rows)
+
+
+def _unpack(points, colors, index):
+    if isinstance(points, (tuple, list)):
+        if len(points) not in (2, 3) or colors is not None or index is not None:
+            raise ValueError("a cloud is (points, colors[, index]), passed whole or unpacked")
+        points, colors, index = (tuple(points) + (None,))[:3]
+    return points, colors, index
+
+
+def _cloud(points, colors, index):
+    """The three tensors of a cloud, checked: ValueError for what no device call is needed to refuse, then RuntimeError for
+    CPU tensors."""
     _points(points)
     m = int(points.shape[0])
     if not isinstance(colors, torch.Tensor) or colors.dtype != torch.uint8 or tuple(colors.shape) != (m, 3):
@@ -232,19 +276,181 @@ def remove_radius_outliers(points, colors=None, index=None, radius=None, min_nei
         index = _ffi.check(index, torch.int64, "index")
     if colors.device != dev or (index is not None and index.device != dev):
         raise ValueError(f"points live on {dev}, colors on {colors.device}" + (f", index on {index.device}" if index is not None else ""))
-    m2 = 0
-    if m:
-        ws = _workspace(None, m, dev)
-        count, _ = _neighbors(points, r, scale, False, ws)
-        _ffi.call("m3_cloud_radius_count", _ffi.ptr(count), m, int(min_neighbors), _ffi.ptr(ws), ws.numel(), _ffi.stream_ptr())
-        m2 = _header(ws, r)[2]                                          # the one synchronisation
+    return points, colors, index
+
+
+def _scatter(entry: str, points, colors, index, values, bound: int, ws, m2: int, return_rows: bool):
+    """The ordered compaction of both filters: the m2 rows whose `values` pass the predicate of `entry` at `bound`."""
+    m, dev = int(points.shape[0]), points.device
     p2 = torch.empty((m2, 3), dtype=torch.float32, device=dev)
     c2 = torch.empty((m2, 3), dtype=torch.uint8, device=dev)
     i2 = torch.empty((m2,), dtype=torch.int64, device=dev) if index is not None else None
     rows = torch.empty((m2,), dtype=torch.int64, device=dev) if return_rows else None
     if m2:
-        _ffi.call("m3_cloud_radius_scatter", _ffi.ptr(points), _ffi.ptr(colors), _ffi.ptr(index), _ffi.ptr(count), m,
-                  int(min_neighbors), _ffi.ptr(ws), ws.numel(), m2, _ffi.ptr(p2), _ffi.ptr(c2), _ffi.ptr(i2), _ffi.ptr(rows),
-                  _ffi.stream_ptr())
+        _ffi.call(entry, _ffi.ptr(points), _ffi.ptr(colors), _ffi.ptr(index), _ffi.ptr(values), m, bound, _ffi.ptr(ws), ws.numel(),
+                  m2, _ffi.ptr(p2), _ffi.ptr(c2), _ffi.ptr(i2), _ffi.ptr(rows), _ffi.stream_ptr())
     out = (p2, c2) if index is None else (p2, c2, i2)
     return out + (rows,) if return_rows else out
+
+
+# ---- k nearest within the radius -------------------------------------------------------------------------------------
+def _k(k) -> int:
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= MAX_K:
+        raise ValueError(f"k must be an integer in 1 ... {MAX_K}, got {k!r}")
+    return int(k)
+
+
+def _knn(points: torch.Tensor, r: float, k: int, queries: Optional[torch.Tensor], ws: torch.Tensor):
+    """Queue the seven launches: (index, dist2, found)."""
+    m, dev = int(points.shape[0]), points.device
+    q = m if queries is None else int(queries.shape[0])
+    index = torch.empty((q, k), dtype=torch.int32, device=dev)
+    dist2 = torch.empty((q, k), dtype=torch.float32, device=dev)
+    found = torch.empty((q,), dtype=torch.int32, device=dev)
+    _ffi.call("m3_knn_query", _ffi.ptr(points), m, r, _ffi.ptr(queries), q, k, _ffi.ptr(index), _ffi.ptr(dist2), _ffi.ptr(found),
+              _ffi.ptr(ws), ws.numel(), _ffi.stream_ptr())
+    return index, dist2, found
+
+
+def _knn_header(ws: torch.Tensor, r: float):
+    """The 16 header words, or None under stream capture; ValueError when a point or a query is out of range."""
+    if torch.cuda.is_current_stream_capturing():
+        return None
+    hdr = ws[:4 * _KNN_HDR_WORDS].view(torch.int32).tolist()
+    if hdr[0]:
+        raise _too_small(r, hdr[0])
+    if hdr[3]:
+        raise ValueError(f"radius too small for the extent of the queries: at radius {r}, {hdr[3]} queries have a cell "
+                         "coordinate beyond +-2^20")
+    return hdr
+
+
+def cloud_knn(points, k, radius, queries: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> KnnResult:
+    """KnnResult(index, dist2, found, out_of_range): the k nearest points within `radius` of every point of the float32
+    [M,3] device tensor `points` - or, with `queries` float32 [Q,3] on the same device, of every query.
+
+    The search is the k nearest WITHIN the radius (Open3D's hybrid search): a query with fewer than k candidates has
+    found < k, index -1 and dist2 +inf in the rest of its row.  Without `queries` row i is not its own neighbour; other
+    rows at the same position are, at distance 0.  With `queries` nothing is excluded.  Points and queries that are not
+    finite find nothing and are found by nobody.  Candidates are ordered by key = (bits(d2) & ~(2^30 - 1)) | row: by
+    squared distance (float64) to 22 mantissa bits, ties to the lower row - so two candidates whose d2 differ only in the
+    dropped 30 bits are ordered by row, not by distance.  The result is a function of the point set and the query alone:
+    identical bytes on every call.  k: an integer in 1 ... 64.
+
+    7 launches and one 64-byte read.  ValueError for a bad k, radius, points or queries (before any device call), and
+    ("radius too small for the extent ...") when the grid cell of a point or a query reaches +-2^20.  workspace: as in
+    cloud_neighbors - with it the call can be captured; nothing is read back then and out_of_range is None.  RuntimeError
+    for CPU tensors."""
+    k = _k(k)
+    r, _ = _radius(radius)
+    _points(points)
+    if queries is not None:
+        _points(queries, "queries")
+        if queries.device != points.device:
+            raise ValueError(f"the cloud lives on {points.device}, the queries on {queries.device}")
+    points = _ffi.check(points, torch.float32, "points")
+    if queries is not None:
+        queries = _ffi.check(queries, torch.float32, "queries")
+    ws = _workspace(workspace, int(points.shape[0]), points.device)
+    index, dist2, found = _knn(points, r, k, queries, ws)
+    hdr = _knn_header(ws, r)
+    return KnnResult(index, dist2, found, None if hdr is None else hdr[0] + hdr[3])
+
+
+def cloud_normals_knn(points, radius, k, toward: Optional[torch.Tensor] = None, min_points: int = 3,
+                      return_variation: bool = False, workspace: Optional[torch.Tensor] = None, return_moments: bool = False):
+    """cloud_normals over an adaptive neighbourhood: point i and its k nearest others within `radius` (cloud_knn's order)
+    instead of every point within the radius.  Arguments, outputs and errors are those of cloud_normals; k is an integer
+    in 1 ... 64.  return_moments appends (count int32 [M], moments int64 [M,9]) of those neighbourhoods: count = found + 1.
+    Where no point has more than k others within the radius they are cloud_neighbors' bytes, and so are the normals.
+
+    9 launches (7 of the k-NN query, the moments of the k nearest, the normals) and one 64-byte read."""
+    if isinstance(points, (tuple, list)):
+        if len(points) < 2:
+            raise ValueError("a cloud is (points, colors[, index]), passed whole, or the points alone")
+        points = points[0]
+    k = _k(k)
+    r, scale = _radius(radius)
+    points, toward, stride = _normals_args(points, toward, min_points)
+    m, dev = int(points.shape[0]), points.device
+    normals = torch.empty((m, 3), dtype=torch.float32, device=dev)
+    variation = torch.empty((m,), dtype=torch.float32, device=dev) if return_variation else None
+    count = torch.empty((m,), dtype=torch.int32, device=dev)
+    mom = torch.empty((m, 9), dtype=torch.int64, device=dev)
+    if m:
+        ws = _workspace(workspace, m, dev)
+        index, _, found = _knn(points, r, k, None, ws)
+        _ffi.call("m3_knn_moments", _ffi.ptr(points), m, r, scale, _ffi.ptr(index), _ffi.ptr(found), k, _ffi.ptr(count),
+                  _ffi.ptr(mom), _ffi.stream_ptr())
+        _ffi.call("m3_cloud_normals", _ffi.ptr(points), m, _ffi.ptr(count), _ffi.ptr(mom), _ffi.ptr(toward), stride,
+                  int(min_points), _ffi.ptr(normals), _ffi.ptr(variation), _ffi.stream_ptr())
+        _knn_header(ws, r)
+    out = (normals, variation) if return_variation else (normals,)
+    out = out + (count, mom) if return_moments else out
+    return out if len(out) > 1 else out[0]
+
+
+def _std_ratio(std_ratio) -> float:
+    if isinstance(std_ratio, bool) or not isinstance(std_ratio, (int, float, np.integer, np.floating)) or \
+            not math.isfinite(float(std_ratio)):
+        raise ValueError(f"std_ratio must be a finite number, got {std_ratio!r}")
+    return float(std_ratio)
+
+
+def statistical_threshold(n: int, s1: int, s2: int, std_ratio: float) -> float:
+    """T = mu + std_ratio sqrt(var) in float64 from the exact integers n, S1 = sum q, S2 = sum q^2 (include/m3slam.h)."""
+    if n < 1:
+        return -1.0
+    mu = s1 / n
+    var = (n * s2 - s1 * s1) / (n * (n - 1)) if n >= 2 else 0.0
+    return mu + std_ratio * math.sqrt(var)
+
+
+def remove_statistical_outliers(points, colors=None, index=None, k: int = 20, std_ratio: float = 2.0, radius=None,
+                                return_rows: bool = False, return_stats: bool = False):
+    """The cloud without the points whose mean distance to their k nearest neighbours is more than std_ratio standard
+    deviations above the mean of that distance over the cloud: (points, colors) or (points, colors, index) as passed -
+    whole or unpacked, as for remove_radius_outliers - in input order; return_rows adds the kept input rows, int64;
+    return_stats adds a dict(q int32 [M], n, S1, S2, T) last.
+
+    The neighbours are cloud_knn's: the k nearest OTHER points within `radius` (required: the search is bounded).  The
+    selection runs in exact integers.  A row is complete when it has k neighbours; q_i is the sum over them of
+    floor(sqrt(rint(d2 2^32 / r^2))), the mean distance in units of r / (k 2^16), -1 for a row that is not complete.
+    The device adds up n = the complete rows, S1 = sum q and S2 = sum q^2; mu = S1 / n, var = (n S2 - S1^2) / (n (n - 1))
+    (0 for n < 2) and T = mu + std_ratio sqrt(var) are float64 operations on exact Python integers, and a row stays iff
+    it is complete and q_i <= T.  Identical bytes on every call.
+
+    Against Open3D's remove_statistical_outlier: (1) the radius bound - a point with fewer than k others within `radius`
+    is dropped, and it takes no part in mu and var; (2) distances in the integer units above, not float64.  Where every
+    point is complete the selection is Open3D's up to arithmetic; nothing more is claimed.
+
+    11 launches (7 of the k-NN query, q and its sums, 2 for the kept count, one scatter) and two reads: the 64-byte
+    header with n, S1, S2, then the kept count.  Not capturable, as remove_radius_outliers is not.  ValueError without a
+    radius, for k outside 1 ... 64 or not an integer, a std_ratio that is not finite, mismatched rows, and ("radius too
+    small for the extent of the cloud") when a point's grid cell reaches +-2^20; RuntimeError for CPU tensors."""
+    points, colors, index = _unpack(points, colors, index)
+    if radius is None:
+        raise ValueError("radius is required: the k nearest are searched within it")
+    k = _k(k)
+    ratio = _std_ratio(std_ratio)
+    r, _ = _radius(radius)
+    points, colors, index = _cloud(points, colors, index)
+    m, dev = int(points.shape[0]), points.device
+    q = torch.empty((m,), dtype=torch.int32, device=dev)
+    n = s1 = s2 = m2 = bound = 0
+    ws = None
+    if m:
+        ws = _workspace(None, m, dev)
+        nn, _, found = _knn(points, r, k, None, ws)
+        _ffi.call("m3_knn_mean_distance", _ffi.ptr(points), m, 2.0 ** 32 / (r * r), _ffi.ptr(nn), _ffi.ptr(found), k, _ffi.ptr(q),
+                  _ffi.ptr(ws), ws.numel(), _ffi.stream_ptr())
+        hdr = _knn_header(ws, r)                                        # the first read
+        u64 = lambda w: (hdr[w] & 0xffffffff) | ((hdr[w + 1] & 0xffffffff) << 32)
+        n, s1, s2 = hdr[4], u64(6), u64(8) + (u64(10) << 32)
+    t = statistical_threshold(n, s1, s2, ratio)
+    if n and t >= 0.0:
+        bound = min(int(math.floor(t)), 2 ** 31 - 1)
+        _ffi.call("m3_knn_stat_count", _ffi.ptr(q), m, bound, _ffi.ptr(ws), ws.numel(), _ffi.stream_ptr())
+        m2 = ws[8:12].view(torch.int32).item()                          # the second read
+    out = _scatter("m3_knn_stat_scatter", points, colors, index, q, bound, ws, m2, return_rows)
+    return out + (dict(q=q, n=n, S1=s1, S2=s2, T=t),) if return_stats else out

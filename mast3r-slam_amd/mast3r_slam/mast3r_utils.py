@@ -25,7 +25,8 @@ filter_components) and the vertex normals and lit vertex colours of mast3r_slam/
 save_ply_mesh_normals writes them) and the vertex clustering of mast3r_slam/simplify.py (simplify_mesh, simplify_counts)
 and the edge topology and smoothing of mast3r_slam/smooth.py (mesh_topology, smooth_mesh) and the point-cloud
 neighbourhoods of mast3r_slam/cloud.py (cloud_neighbors, cloud_normals, source_viewpoints, remove_radius_outliers;
-save_ply_normals writes a cloud with normals).
+save_ply_normals writes a cloud with normals) and the k nearest neighbours on the same index (cloud_knn,
+remove_statistical_outliers, cloud_normals_knn).
 """
 from __future__ import annotations
 
@@ -51,7 +52,8 @@ from .components import ComponentsInfo, filter_components, mesh_components
 from .normals import shade_vertices, vertex_normals
 from .simplify import SimplifyInfo, simplify_counts, simplify_mesh
 from .smooth import MeshTopology, mesh_topology, smooth_mesh
-from .cloud import CloudNeighbors, cloud_neighbors, cloud_normals, remove_radius_outliers, source_viewpoints
+from .cloud import (CloudNeighbors, KnnResult, cloud_knn, cloud_neighbors, cloud_normals, cloud_normals_knn,
+                    remove_radius_outliers, remove_statistical_outliers, source_viewpoints)
 
 __all__ = [
     "load_mast3r", "resize_img", "frame_to_numpy", "downsample", "mast3r_inference_mono", "mast3r_asymmetric_inference",
@@ -69,6 +71,7 @@ __all__ = [
     "simplify_mesh", "simplify_counts", "SimplifyInfo",
     "smooth_mesh", "mesh_topology", "MeshTopology",
     "cloud_neighbors", "cloud_normals", "source_viewpoints", "remove_radius_outliers", "CloudNeighbors", "save_ply_normals",
+    "cloud_knn", "KnnResult", "remove_statistical_outliers", "cloud_normals_knn",
 ]
 
 
