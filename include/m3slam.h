@@ -1145,6 +1145,99 @@ int m3_knn_stat_scatter(const float *points, const uint8_t *colors, const int64_
                         int threshold, const void *ws, int64_t ws_bytes, int64_t M2, float *points_out, uint8_t *colors_out,
                         int64_t *index_out, int64_t *rows_out, void *stream);
 
+/* Registration of a source cloud onto a target cloud over Sim(3): point-to-point and point-to-plane ICP on the same index
+ * (DESIGN.md section 7q).  Host side: mast3r_slam/register.py.  This text is the contract; tests/icp_twin.py restates it
+ * in numpy and state, history, sums and correspondences of device and twin agree byte for byte.
+ *
+ * Arithmetic.  Only float64 + - * /, each rounded on its own; a unary minus is exact.  No sqrt and no transcendental
+ * function takes part in an iteration.  Brackets below give the order of the operations.
+ *
+ * Pose.  x' = s R x + t: R double [9] row-major, t double [3], s double.  `pose` in the calls below is HOST memory,
+ * double [13] = R | t | s, read before the call returns.
+ *
+ * Per source row i (source float32 [Ns,3]; x, y, z converted to float64):
+ *     p_a = s * ((R_a0 x + R_a1 y) + R_a2 z) + t_a                          a = 0, 1, 2
+ *     q32 = (float)p per axis: the search query.  The row is FINITE when the three components of q32 are.
+ *   Correspondence: the k = 1 cross-mode result of m3_knn_query on the target with the query q32 - the same cells
+ *   (h = r (1 + 2^-10)), the same candidates (target rows that are finite and in range with d2 <= (double)r (double)r,
+ *   d = (double)target_j - (double)q32), the smallest key (bits(d2) & ~(2^30 - 1)) | j.  A row that is not finite, a
+ *   finite row whose own cell coordinate reaches +-2^20 (OUT OF RANGE) and a row without candidate have no
+ *   correspondence: j = -1.
+ *   Residual, from the float64 p, not from q32:  e_a = p_a - (double)target_j,a.
+ *
+ * Terms of a contributing row: 36 values v, the upper triangle of H = J^T J row by row (H00 .. H06, H11 .. H16, ...,
+ * H66: v[0 .. 27]), g = J^T residual (v[28 .. 34]) and the cost (v[35]); unknowns (tau [3], omega [3], sigma).
+ *   Point to point (mode 0): every row with a correspondence contributes.  With (x, y, z) = p:
+ *     H row 0:  1, 0, 0, 0, z, -y, x        row 1:  1, 0, -z, 0, x, y        row 2:  1, y, -x, 0, z
+ *     H33 = y y + z z, H34 = -(x y), H35 = -(x z), H36 = 0;  H44 = x x + z z, H45 = -(y z), H46 = 0;
+ *     H55 = x x + y y, H56 = 0;  H66 = (x x + y y) + z z
+ *     g = e0, e1, e2, y e2 - z e1, z e0 - x e2, x e1 - y e0, (x e0 + y e1) + z e2;  cost = (e0 e0 + e1 e1) + e2 e2
+ *   (J = [I | -[p]x | p] with the products by 0 and 1 carried out and z y - y z = 0.)
+ *   Point to plane (mode 1): n = (double)target_normals_j.  The row contributes when the three components of the
+ *   float32 normal are finite and not all zero (m3_cloud_normals writes (0,0,0) for sparse points).
+ *     J = n0, n1, n2, y n2 - z n1, z n0 - x n2, x n1 - y n0, (n0 x + n1 y) + n2 z;   rho = (n0 e0 + n1 e1) + n2 e2
+ *     H_uv = J_u J_v,  g_u = J_u rho,  cost = rho rho
+ *   A row that does not contribute has 36 times +0.0.
+ *
+ * Reduction.  A tile is 256 consecutive source rows (the last one padded with rows that do not contribute).  Within a
+ * tile each of the 36 sums is the pairwise tree over the slots: x = x[0::2] + x[1::2], eight times.  Per tile also three
+ * integers: contributing rows (PAIRS), finite rows, rows out of range.  Second stage, 256 slots: slot j starts at +0.0
+ * and adds the partials of tiles j, j + 256, j + 512, ... in ascending order; then the same tree over the 256 slots.
+ * The integers are added exactly.  No float atomics: the bytes do not depend on scheduling.
+ *
+ * Step (mode-independent), from the 36 sums S and the pair count:
+ *   n = 7 with scale, else 6 (the leading 6 x 6 block of H, sigma = 0).
+ *   pairs < min_pairs:  status = 1 (too few pairs).
+ *   else LDL^T without pivoting, for j = 0 .. n-1:
+ *       w_k = L_jk d_k and d_j = (..((H_jj - L_j0 w_0) - L_j1 w_1) ..) - L_j,j-1 w_j-1                   k < j
+ *       d_j <= 1e-12 H_jj, or d_j not finite:  status = 2 (singular), stop
+ *       L_ij = ((..(H_ij - L_i0 w_0) ..) - L_i,j-1 w_j-1) / d_j                                           i > j
+ *     y_i = (..((-g_i) - L_i0 y_0) ..) - L_i,i-1 y_i-1;      delta_i = (..((y_i / d_i) - L_i+1,i delta_i+1) ..) -
+ *     L_n-1,i delta_n-1 for i = n-1 .. 0;  (tau, omega, sigma) = delta.
+ *   status != 0: the pose stays and the iteration is finished.  Otherwise, with a = omega * 0.5,
+ *     c = 2 / (1 + ((a0 a0 + a1 a1) + a2 a2)), k = 1 + sigma,
+ *     D00 = 1 + c (-(a1 a1 + a2 a2)), D11 = 1 + c (-(a0 a0 + a2 a2)), D22 = 1 + c (-(a0 a0 + a1 a1)),
+ *     D01 = c (a0 a1 - a2), D02 = c (a0 a2 + a1), D10 = c (a0 a1 + a2), D12 = c (a1 a2 - a0), D20 = c (a0 a2 - a1),
+ *     D21 = c (a1 a2 + a0)                 (Cayley's map I + 2 / (1 + a.a) ([a]x + [a]x [a]x): orthogonal, I + [omega]x
+ *                                           to first order)
+ *     R_ab <- (D_a0 R_0b + D_a1 R_1b) + D_a2 R_2b;   t_a <- k ((D_a0 t_0 + D_a1 t_1) + D_a2 t_2) + tau_a;   s <- k s
+ *     tt = (tau0 tau0 + tau1 tau1) + tau2 tau2, ww likewise of omega, rr = tol * (double)r;
+ *     done = 1 when tt <= rr rr and ww <= tol tol and sigma sigma <= tol tol.
+ *   Every iteration that ran adds 1 to `iterations run` and writes its history row: pairs, cost, tt, ww, sigma (tt = ww
+ *   = sigma = 0 when status != 0).  Once done or status is set, the kernels of the remaining iterations return at once.
+ *
+ * Evaluation.  After the last iteration one more accumulate in mode 0 at the final pose and one reduction:
+ * eval pairs and eval cost (the squared error sum).  fitness = eval pairs / finite rows and inlier_rmse =
+ * sqrt(eval cost / eval pairs) are the host's.  pairs int32 [Ns], when given: the final correspondence, -1 where none.
+ *
+ * ws, 16-byte aligned, contents ignored on entry: the target's index (m3_cloud_ws_bytes(Nt) rounded up to 16) | state
+ * double [24] | history double [iterations][5], rounded up to 16 bytes | tile partials 8 bytes [ntile][40] (36 sums,
+ * int64 pairs, finite, out of range, 0), ntile = max(1, ceil(Ns / 256)).  State words: [0..8] R, [9..11] t, [12] s,
+ * [13] iterations run, [14] done, [15] status, [16] pairs and [17] cost of the last iteration, [18] finite source rows and
+ * [19] rows out of range of the last accumulate, [20] eval pairs, [21] eval cost, [22..23] 0.  The index header keeps
+ * its meaning: int32 [0] = target points out of range.
+ * m3_icp_ws_bytes(Ns, Nt, iterations): 0 for Ns or Nt outside 0 ... 2^30 or iterations outside 0 ... 1000.
+ * m3_icp_launches(iterations) = 6 + 2 iterations + 2 whatever the clouds hold (0: iterations out of range): the six index
+ * launches of the target, two per iteration, two for the evaluation.  Nothing allocates or synchronises: the call can be
+ * captured into a graph.  Every range and row read from ws is bounds-checked: a stale ws gives wrong numbers, not a fault.
+ * m3_icp_sums: the index, one accumulate at `pose` and the reduction (8 launches; ws of m3_icp_ws_bytes(Ns, Nt, 0)):
+ * count int64 [3] = pairs, finite rows, rows out of range; sums double [36]; pairs int32 [Ns] or NULL - all device memory.
+ * M3_ERR_INVALID_ARG, before any HIP call: a NULL pose, count or sums; source NULL with Ns > 0, target NULL with Nt > 0;
+ * a misaligned pointer; a radius that is not finite and > 0; a mode other than 0, 1; mode 1 without normals (Nt > 0);
+ * iterations outside 0 ... 1000; min_pairs < 1; tol not finite or < 0; with_scale other than 0, 1; a ws that is NULL,
+ * short or not 16-byte aligned.
+ *
+ * Left out: robust kernels and trimming, a normal-compatibility gate, source rows sorted through the target's cells,
+ * multi-scale radii, colour terms, global registration (FPFH, RANSAC). */
+int64_t m3_icp_ws_bytes(int64_t Ns, int64_t Nt, int iterations);
+int m3_icp_launches(int iterations);
+int m3_icp_sums(const float *source, int64_t Ns, const float *target, const float *target_normals, int64_t Nt, float radius,
+                int mode, const double *pose, int64_t *count, double *sums, int32_t *pairs, void *ws, int64_t ws_bytes,
+                void *stream);
+int m3_icp_register(const float *source, int64_t Ns, const float *target, const float *target_normals, int64_t Nt,
+                    float radius, int mode, const double *pose, int with_scale, int iterations, double tol, int64_t min_pairs,
+                    int32_t *pairs, void *ws, int64_t ws_bytes, void *stream);
+
 /* ---------------------------------------------------------- camera intrinsics */
 
 /* Focal length of every keyframe from its own pointmap.  Host side: mast3r_slam/intrinsics.py.

@@ -26,7 +26,8 @@ save_ply_mesh_normals writes them) and the vertex clustering of mast3r_slam/simp
 and the edge topology and smoothing of mast3r_slam/smooth.py (mesh_topology, smooth_mesh) and the point-cloud
 neighbourhoods of mast3r_slam/cloud.py (cloud_neighbors, cloud_normals, source_viewpoints, remove_radius_outliers;
 save_ply_normals writes a cloud with normals) and the k nearest neighbours on the same index (cloud_knn,
-remove_statistical_outliers, cloud_normals_knn).
+remove_statistical_outliers, cloud_normals_knn) and the registration of two clouds of mast3r_slam/register.py
+(register_clouds, icp_sums).
 """
 from __future__ import annotations
 
@@ -54,6 +55,7 @@ from .simplify import SimplifyInfo, simplify_counts, simplify_mesh
 from .smooth import MeshTopology, mesh_topology, smooth_mesh
 from .cloud import (CloudNeighbors, KnnResult, cloud_knn, cloud_neighbors, cloud_normals, cloud_normals_knn,
                     remove_radius_outliers, remove_statistical_outliers, source_viewpoints)
+from .register import IcpSums, Registration, icp_sums, read_registration, register_clouds, registration_workspace_bytes
 
 __all__ = [
     "load_mast3r", "resize_img", "frame_to_numpy", "downsample", "mast3r_inference_mono", "mast3r_asymmetric_inference",
@@ -72,6 +74,7 @@ __all__ = [
     "smooth_mesh", "mesh_topology", "MeshTopology",
     "cloud_neighbors", "cloud_normals", "source_viewpoints", "remove_radius_outliers", "CloudNeighbors", "save_ply_normals",
     "cloud_knn", "KnnResult", "remove_statistical_outliers", "cloud_normals_knn",
+    "register_clouds", "icp_sums", "Registration", "IcpSums", "registration_workspace_bytes", "read_registration",
 ]
 
 
