@@ -56,6 +56,8 @@ struct TailArgs {
     // second head (blockIdx.y = 1): its own weights; X / pts / conf advance by one head's extent
     const bf16_t *Wc2, *W42;
     const float *bias2, *b42;
+    int wt;                 // Y (both groups) spans less than 2^31 - 16 bytes: its 16-byte stores go out write-through through a
+                            //   descriptor on Y with 32-bit offsets (store16_wt, gemm_common.h); 0 = plain pointer stores
 };
 
 // EP: what happens to the 128 output channels of a workgroup
@@ -87,6 +89,8 @@ k_conv_tail(const TailArgs ain) {
         a.Y += z * 128;
         if (EP == EP_ADD) a.R += z * 128;
     }
+    const auto y_rsrc = stream_rsrc(a.Y);                  // output stores: this group's, this output half's Y (kernel arguments and
+                                                            // blockIdx only: scalar); null for the fused tail, which does not use it
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     unsigned char *halo = lds, *wst = lds + kHaloBytes, *patch = lds + kHaloBytes + 2 * kWStage;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -377,7 +381,8 @@ k_conv_tail(const TailArgs ain) {
                 int oy, ox;
                 pix(pass, rl, oy, ox);
                 if (ox < a.W)
-                    *reinterpret_cast<uint4 *>(a.Y + (((size_t)b * a.H + oy) * a.W + ox) * a.cout + wc * 64 + ch * 8) = o;
+                    store16_out<2>(a.wt != 0, y_rsrc, a.Y, (unsigned)((b * a.H + oy) * a.W + ox) * (unsigned)a.cout + wc * 64 + ch * 8,
+                                   (((size_t)b * a.H + oy) * a.W + ox) * a.cout + wc * 64 + ch * 8, o);
             }
             asm volatile("" ::: "memory");
         }
@@ -417,7 +422,8 @@ k_conv_tail(const TailArgs ain) {
                 const int oy = oy0 + wp * 4 + (i >> 1);
                 const int ox = ox0 + (i & 1) * 16 + (int)((0x3D9F2A40E6C851B7ULL >> (4 * (rl & 15))) & 15);
                 if (ox < a.W)
-                    *reinterpret_cast<uint4 *>(a.Y + (((size_t)b * a.H + oy) * a.W + ox) * a.cout + wc * 64 + ch * 8) = v;
+                    store16_out<2>(a.wt != 0, y_rsrc, a.Y, (unsigned)((b * a.H + oy) * a.W + ox) * (unsigned)a.cout + wc * 64 + ch * 8,
+                                   (((size_t)b * a.H + oy) * a.W + ox) * a.cout + wc * 64 + ch * 8, v);
             }
             asm volatile("" ::: "memory");
         }
@@ -515,6 +521,7 @@ static int dpt_tail_launch(const void *X, const void *Wc, const float *bias, con
     a.pts = pts; a.conf = conf; a.Y = (bf16_t *)Y; a.R = (const bf16_t *)R; a.cout = tail ? 128 : cout; a.relu_in = relu_in;
     a.zero16 = (const bf16_t *)zero16; a.B = B; a.H = H; a.W = W;
     a.IH = upsample ? H / 2 : H; a.IW = upsample ? W / 2 : W;
+    a.wt = !tail && out_fits32((long long)groups * B * H * W * cout, 2) ? 1 : 0;   // Y through 32-bit byte offsets (both groups' extent)
     const dim3 grid((unsigned)((H / TH) * ((W + TW - 1) / TW) * B), groups, tail ? 1 : cout / 128), blk(kThreads);
     hipStream_t st = (hipStream_t)stream;
 #define M3_TAIL(DTV, UP, CI, EPV)                                                                                \

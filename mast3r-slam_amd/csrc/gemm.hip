@@ -310,7 +310,9 @@ k_gemm(const GemmArgs gin) {
 }
 
 template <int MODE, int T, int DT>
-int launch_dt(const GemmArgs &a, int epi, hipStream_t st) {
+int launch_dt(const GemmArgs &ain, int epi, hipStream_t st) {
+    GemmArgs a = ain;
+    a.wt = gemm_store_policy(a, epi);                            // write-through output stores where 32-bit offsets reach
     constexpr int kLdsBytes = k_gemm_stages(T) * (2 * T) * BK * 2;      // 64 KiB (T = 128: 2 stages; T = 64: 4 stages)
     const int tiles = m3_cdiv(a.M, T) * m3_cdiv(a.N, T);
     dim3 grid(tiles, a.groups > 1 ? a.groups : 1, a.splits > 1 ? a.splits : 1), blk(kThreads);

@@ -250,7 +250,9 @@ k_gemm256(const GemmArgs gin) {
 }
 
 template <int MODE, int BN, int DT>
-int launch256(const GemmArgs &a, int epi, hipStream_t st) {
+int launch256(const GemmArgs &ain, int epi, hipStream_t st) {
+    GemmArgs a = ain;
+    a.wt = gemm_store_policy(a, epi);                            // write-through output stores where 32-bit offsets reach
     constexpr int kLdsBytes = 2 * (BM + BN) * BK * 2 + BM * 8;    // 128 KiB / 112 KiB of stages + the LayerNorm-fold row table
     const int tiles = m3_cdiv(a.M, BM) * m3_cdiv(a.N, BN);
     // dense staging: 32-bit byte offsets from the tile's first row (256 rows of K, plus the K advance) stay below 2^31

@@ -96,6 +96,24 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t stream_rsrc(const void *base) 
 __device__ __forceinline__ void blds16(__amdgpu_buffer_rsrc_t r, unsigned lane_off, unsigned wave_off, void *lds_wave_base) {
     __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void *)lds_wave_base, 16, lane_off, wave_off, 0, 0);
 }
+// 16-byte WRITE-THROUGH output store (buffer_store_dwordx4 ... offen sc1) through a descriptor on the output's base: the line
+// goes to memory with the store and does not stay dirty in the XCD's L2.  A kernel's outputs are read by the NEXT kernel, under
+// another tile-to-XCD map and behind the boundary's acquire - they gain nothing from staying in L2, and whatever a kernel leaves
+// dirty there is written back at the boundary with every CU idle (profiles/store_policy.md: 0.8 - 1.3 us per launch behind a
+// 32 - 128 MB burst).  The byte offset is one 32-bit VGPR: no 64-bit address per store.  The builtin, not inline asm (see
+// pack_bf16).  Only for outputs whose whole extent stays below 2^31 - 16 bytes (out_fits32: the launchers' test).
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void store16_wt(__amdgpu_buffer_rsrc_t r, unsigned byte_off, uint4 v) {
+    __builtin_amdgcn_raw_buffer_store_b128(u32x4{v.x, v.y, v.z, v.w}, r, byte_off, 0, /*aux: sc1*/ 16);
+}
+// 16-byte output store at element `idx` of a tensor of ESZ-byte elements: write-through when the launcher found the extent in
+// range (wt: kernel-uniform), else the plain pointer store
+template <int ESZ>
+__device__ __forceinline__ void store16_out(bool wt, __amdgpu_buffer_rsrc_t r, void *base, unsigned idx32, size_t idx, uint4 v) {
+    if (wt) store16_wt(r, idx32 * (unsigned)ESZ, v);
+    else *reinterpret_cast<uint4 *>(reinterpret_cast<unsigned char *>(base) + idx * ESZ) = v;
+}
+inline bool out_fits32(long long elements, int esz) { return elements >= 0 && elements * esz < (1ll << 31) - 16; }
 
 // Workgroup barrier that LDS traffic cannot cross.  For LLVM `__builtin_amdgcn_s_barrier()` touches no memory, so
 // the scheduler is free to move ds_reads - and the s_waitcnt that retires them - across it: in the round-1 build the
@@ -170,7 +188,18 @@ struct GemmArgs {
     int ln_slots;
     float ln_eps;
     long long ln_gstride, stats_gstride;       // floats between group 0's and group 1's statistics (may be negative)
+    int wt;                 // set by the launchers (gemm_store_policy): every output of the launch, group stride included, spans less
+                            //   than 2^31 - 16 bytes - the row-contiguous epilogue's 16-byte stores then go out write-through
+                            //   through a buffer descriptor with 32-bit offsets (store16_wt); 0 = plain pointer stores
 };
+// the launchers' test for GemmArgs::wt (EPI_RELU_HEAD4 has no 16-byte output)
+inline int gemm_store_policy(const GemmArgs &a, int epi) {
+    if (epi < 0 || epi > 6 /*EPI_BF16_ROPE*/ || a.M <= 0 || a.ldc <= 0) return 0;
+    const bool f32 = (epi == 2 /*EPI_F32*/ || epi == 3 /*EPI_F32_ACCUM*/) && !a.C_lo;
+    const long long gs = a.groups > 1 ? (a.c_gstride < 0 ? -a.c_gstride : a.c_gstride) : 0;
+    const long long planes = a.splits > 1 ? a.splits : 1;          // split-K partial planes follow each other
+    return out_fits32(gs + planes * a.M * a.ldc, f32 ? 4 : 2) ? 1 : 0;
+}
 
 // Per-group view of the arguments (group 1 of a 2-group launch).
 template <int EPI>
@@ -482,6 +511,8 @@ __device__ __forceinline__ void ln_row_table(const GemmArgs &g, float2 *tab, int
 // so every wave transposes its own sub-tile through a private LDS scratch (padded rows, no
 // workgroup barrier needed) and writes/reads global memory 16 bytes per lane with 8 (bf16) or 16
 // (fp32) consecutive lanes per row: full 128-byte lines, 2x fewer instructions.
+// The 16-byte stores go out write-through through a buffer descriptor (store16_out) where the launcher found the output
+// below 2^31 - 16 bytes (g.wt); the hi / lo planes, updated in place, and the element-wise fallback keep plain stores.
 //   wave sub-tile = (16*NI) rows x (16*NJ) columns at (m_base, n_base); wlds = this wave's scratch,
 //   64 * (32*NJ + 16) bytes (9216 for NJ = 4, 13312 for NJ = 6).
 // Bias / activation / RoPE are applied in the accumulator layout before the transpose, residuals
@@ -511,6 +542,11 @@ __device__ __forceinline__ void epilogue_rows(const GemmArgs &g, f32x4 (&acc)[NI
         }
         return;
     }
+    // Output stores of the row-contiguous side: 16 bytes per lane, write-through through descriptors on the (group's) output
+    // bases when g.wt says the extent allows 32-bit offsets (store16_out).  Kernel arguments and blockIdx only: scalar.
+    // (The hi / lo planes keep plain stores: see there.)
+    const bool wt = g.wt != 0;
+    const auto c_rsrc = stream_rsrc(g.C), c16_rsrc = stream_rsrc(F32OUT ? g.C16 : nullptr);
     // Bias of this lane's columns: UNCONDITIONAL loads from clamped addresses under one kernel-uniform test, the column bound
     // applied to the values.  Written as `(bias && n < N) ? load : 0` hipcc branched around every load and waited for each in
     // turn (s_and_saveexec / global_load / s_waitcnt vmcnt(0), four times): four dependent L2 round trips in front of every
@@ -611,19 +647,24 @@ __device__ __forceinline__ void epilogue_rows(const GemmArgs &g, f32x4 (&acc)[NI
                         const unsigned l0 = pack16<DT>(v.x - lo16<DT>(h0), v.y - hi16<DT>(h0));
                         const unsigned l1 = pack16<DT>(v.z - lo16<DT>(h1), v.w - hi16<DT>(h1));
                         const unsigned g0 = dpp_xor1(h0), g1 = dpp_xor1(h1), k0 = dpp_xor1(l0), k1 = dpp_xor1(l1);
+                        // PLAIN stores: the planes are updated in place, so the lines are in L2 from the residual read and a plain
+                        // store is absorbed there; written through, the step's residual launches took ~1 us longer each and the
+                        // step 0.09 ms (profiles/store_policy.md) - measured and not kept
                         if (!(lane & 1) && m < g.M && n < g.N) {    // the even lane of a pair stores 8 columns of both planes
                             *reinterpret_cast<uint4 *>(reinterpret_cast<bf16_t *>(g.C16) + (size_t)m * g.ldc + n) = uint4{h0, h1, g0, g1};
                             *reinterpret_cast<uint4 *>(reinterpret_cast<bf16_t *>(g.C_lo) + (size_t)m * g.ldc + n) = uint4{l0, l1, k0, k1};
                         }
                     } else {
+                    const unsigned e32 = (unsigned)m * (unsigned)g.ldc + (unsigned)n;
+                    const size_t e = (size_t)m * g.ldc + n;
                     if (m < g.M && n < g.N)
-                        *reinterpret_cast<float4 *>(reinterpret_cast<float *>(g.C) + (size_t)m * g.ldc + n) = v;
+                        store16_out<4>(wt, c_rsrc, g.C, e32, e, uint4{__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z), __float_as_uint(v.w)});
                     if (g.C16) {                                    // kernel-uniform: 16-bit copy of the stream (LayerNorm fold)
                         // two neighbouring lanes hold 8 consecutive columns of a row: the even one stores all 16 bytes
                         const unsigned p0 = pack16<DT>(v.x, v.y), p1 = pack16<DT>(v.z, v.w);
                         const unsigned q0 = dpp_xor1(p0), q1 = dpp_xor1(p1);
                         if (!(lane & 1) && m < g.M && n < g.N)
-                            *reinterpret_cast<uint4 *>(reinterpret_cast<bf16_t *>(g.C16) + (size_t)m * g.ldc + n) = uint4{p0, p1, q0, q1};
+                            store16_out<2>(wt, c16_rsrc, g.C16, e32, e, uint4{p0, p1, q0, q1});
                     }
                     }
                     if (g.stats_out) {                              // kernel-uniform: (sum, sum of squares) per 32-column slot
@@ -648,7 +689,7 @@ __device__ __forceinline__ void epilogue_rows(const GemmArgs &g, f32x4 (&acc)[NI
                     o.z = pack16<DT>(b.x + lo16<DT>(u.z), b.y + hi16<DT>(u.z));
                     o.w = pack16<DT>(b.z + lo16<DT>(u.w), b.w + hi16<DT>(u.w));
                     if (m < g.M && n < g.N)
-                        *reinterpret_cast<uint4 *>(reinterpret_cast<bf16_t *>(g.C) + (size_t)m * g.ldc + n) = o;
+                        store16_out<2>(wt, c_rsrc, g.C, (unsigned)m * (unsigned)g.ldc + (unsigned)n, (size_t)m * g.ldc + n, o);
                 }
             }
             asm volatile("" ::: "memory");
@@ -742,7 +783,7 @@ __device__ __forceinline__ void epilogue_rows(const GemmArgs &g, f32x4 (&acc)[NI
                 if (SWZ && (rl & 1)) v = uint4{v.z, v.w, v.x, v.y};
                 const int m = m_base + pass * PR + rl, n = n_base + ch * 8;
                 if (m < g.M && n < g.N)
-                    *reinterpret_cast<uint4 *>(reinterpret_cast<bf16_t *>(g.C) + (size_t)m * g.ldc + n) = v;
+                    store16_out<2>(wt, c_rsrc, g.C, (unsigned)m * (unsigned)g.ldc + (unsigned)n, (size_t)m * g.ldc + n, v);
             }
             asm volatile("" ::: "memory");
         }
