@@ -1,6 +1,6 @@
 """Inputs for which the correct answer of a kernel is EXACT, and an element-wise checker.
 
-Two constructions ("Exact-input tests"):
+Three constructions ("Exact-input tests"):
 
 * integer GEMM: operands, bias and residual hold small integers (or integers times a power of two), so every product and
   every partial sum is an integer below 2^24: fp32 accumulation is exact in ANY order, on any tile shape.  The kernel must
@@ -8,6 +8,9 @@ Two constructions ("Exact-input tests"):
 * routing attention: key j carries the code of j's 10 bits in {-1, +1}, query i is 20 x the code of its target pi(i).  The
   target's score beats every other key's by >= 30 nats, so the softmax row is (1, 0, ...) to below 2^-24 and the output row
   must be V[pi(i)] bit for bit.
+* power-of-two softmax: one-hot keys and integer query tables make every score one exact product and every softmax weight
+  2^(s - m) an exact power of two; row profiles prescribe the maximum of each key tile, so each rescale branch of the
+  attention kernels runs on known rows, and the weighted sum is compared element-wise with float64 under a derived bound.
 
 Plain helper module: CPU tensors only, seeded, no GPU import.  tests/test_exact_inputs.py checks the promises made here
 without any kernel.
@@ -297,6 +300,198 @@ def uniform_problem(tq: int, tk: int, b: int, h: int, seed: int):
 
 def uniform_expected64(v: torch.Tensor, tq: int, kv_batch_shift: int = 0) -> torch.Tensor:
     return v.double().roll(-kv_batch_shift, 0).mean(1, keepdim=True).expand(-1, tq, -1)
+
+
+# ------------------------------------------------------------------------------- power-of-two softmax weights
+# Row profiles: what a query row prescribes as the maximum of each key tile (64 keys), relative to its first tile.
+POW2_PROFILES = ("flat", "stair", "jump", "fall", "keeper", "keeper-last", "keeper-twice", "tail-max", "ripple")
+POW2_OVERFLOW = ("overflow-l", "overflow-inf")
+POW2_ALL = POW2_PROFILES + POW2_OVERFLOW
+# key tiles a profile needs to exist; with fewer the row is "flat" (and recorded as flat: see pow2_profile_ids)
+POW2_MIN_TILES = {"flat": 1, "stair": 2, "jump": 2, "fall": 2, "keeper": 3, "keeper-last": 2, "keeper-twice": 6, "tail-max": 1,
+                  "ripple": 2, "overflow-l": 2, "overflow-inf": 2}
+POW2_VARIANTS = ("mixed", "banded", "overflow")
+POW2_TAIL_MAX = 5                                # the lone last key of a tail-max row, above every other key's tile offset
+
+
+def pow2_profile_ids(tq: int, tk: int, b: int, h: int, variant: str):
+    """(prof, kpos), both int64 [b, h, tq]: index into POW2_ALL and the counter that places a profile's event tile.
+    mixed:    prof = (row + head + batch) % P - every 16-row query tile holds every profile; kpos = row // P.
+    banded:   prof = (row // 32 + head + batch) % P - a wave holds ONE profile in both workgroup shapes, and with
+              kpos = row // 32 all its rows meet the event in the same tile.
+    overflow: mixed, but rows < 64 of even heads run over POW2_ALL (the two overflow profiles included).
+    A profile that needs more key tiles than ceil(tk / 64) becomes flat HERE, so the ids say what the rows really are."""
+    p, nt = len(POW2_PROFILES), (tk + 63) // 64
+    row, head, bat = torch.arange(tq)[None, None, :], torch.arange(h)[None, :, None], torch.arange(b)[:, None, None]
+    zero = torch.zeros(b, h, tq, dtype=torch.int64)
+    if variant == "banded":
+        prof, kpos = (row // 32 + head + bat) % p, row // 32 + zero
+    else:
+        assert variant in ("mixed", "overflow")
+        prof, kpos = (row + head + bat) % p, row // p + zero
+        if variant == "overflow":
+            sel = ((row < 64) & (head % 2 == 0)).expand(b, h, tq)
+            prof = torch.where(sel, (row + head + bat) % len(POW2_ALL), prof)
+            kpos = torch.where(sel, row // len(POW2_ALL) + zero, kpos)
+    need = torch.tensor([POW2_MIN_TILES[n] for n in POW2_ALL])
+    return torch.where(need[prof] <= nt, prof, torch.zeros_like(prof)), kpos
+
+
+def pow2_problem(tq: int, tk: int, b: int, h: int, seed: int, variant: str = "mixed"):
+    """Attention inputs whose every softmax weight is an exact power of two.
+      k [b, tk, h*64]  one-hot: key j has the class 4 * slot + sub, slot = (j // 64) % 16 (its key tile, tk <= 1024) and sub in
+                       0..3 - its own random layout per batch item and head, each sub 16 times per full tile; in the last tile
+                       key tk - 1 ALONE has sub 3 (the others 0..2), so a row can single it out;
+      q [b, tq, h*64]  a table of 64 integers per row and head: q[4 * slot + sub] = off[slot] - lvl[slot][sub] + shift, with off
+                       the profile's tile offsets, lvl a random permutation of 0..3 per row and slot (a spread of 0..3 below the
+                       tile's maximum) and shift a per-row integer that centres the table in [-127, 127] (+ a jitter of +-5);
+      v                as routing_problem: non-zero integers in +-[1, 8], its own per batch item and head.
+    The score s_ij = q_i . k_j = q_i[class_j] is ONE non-zero product: exact in the matrix core in any order, and with an
+    exp2 softmax (prescaled entry points as they are, classic ones at scale = ln 2) every weight 2^(s - m) is a power of two
+    whatever reference m the kernel holds.  Tile offsets per profile (event tiles move with kpos; t = tile, nt = tiles):
+      flat 0 | stair 3 (t - nt + 1) on the last four tiles, 36 lower (still climbing by 3) before | jump +40 in one tile > 0 |
+      fall 0, then -30 | keeper +70 in a tile that is neither first nor last | keeper-last +70 in the last | keeper-twice
+      +70 in tile 1 or 2, +135 in tile nt - 2 or nt - 3 | tail-max 0, key tk - 1 at +POW2_TAIL_MAX | ripple (3 t + row) % 6 |
+      overflow-l +105 / overflow-inf +140 in one tile > 0.
+    Returns q, k, v (float32 holders, exact in bf16 and fp16) and info = dict(prof, table [b,h,tq,64] (= q per head), cls
+    [b,h,tk])."""
+    assert 1 <= tk <= 1024
+    g = _gen(seed)
+    nt = (tk + 63) // 64
+    prof, kpos = pow2_profile_ids(tq, tk, b, h, variant)
+    idx = {n: i for i, n in enumerate(POW2_ALL)}
+    t = torch.arange(16)[None, None, None, :]
+    pr, kp = prof[..., None], kpos[..., None]
+    row = torch.arange(tq)[None, None, :, None]
+    tl = t - (nt - 1)
+    at = lambda pos: (t == pos).long()
+    anywhere = 1 + kp % max(nt - 1, 1)                                    # a tile that is not the first
+    inner = 1 + kp % max(nt - 2, 1)                                       # ... nor the last
+    offs = {
+        "stair": torch.where(tl >= -3, 3 * tl, 3 * (tl + 4) - 36),
+        "jump": 40 * at(anywhere),
+        "fall": -30 * (t > 0).long(),
+        "keeper": 70 * at(inner),
+        "keeper-last": 70 * at(nt - 1),
+        "keeper-twice": 70 * at(1 + kp % 2) + 135 * at(nt - 2 - (kp // 2) % 2),
+        "ripple": (3 * t + row) % 6,
+        "overflow-l": 105 * at(anywhere),
+        "overflow-inf": 140 * at(anywhere),
+    }
+    off = torch.zeros(b, h, tq, 16, dtype=torch.int64)
+    for name, o in offs.items():
+        off = torch.where(pr == idx[name], o.expand_as(off), off)
+    off = torch.where(t < nt, off, torch.zeros_like(off))                 # slots without a key tile: never read
+    lvl = torch.rand(b, h, tq, 16, 4, generator=g).argsort(-1)
+    table = off[..., None] - lvl                                          # [b,h,tq,16,4]
+    tm = prof == idx["tail-max"]
+    table[..., nt - 1, 3] = torch.where(tm, torch.full_like(prof, POW2_TAIL_MAX), table[..., nt - 1, 3])
+    table = table.reshape(b, h, tq, 64)
+    hi, lo = table.amax(-1, keepdim=True), table.amin(-1, keepdim=True)
+    table = table - (hi + lo) // 2 + torch.randint(-5, 6, (b, h, tq, 1), generator=g)
+    assert int(table.abs().max()) <= 127
+    q = table.permute(0, 2, 1, 3).reshape(b, tq, h * HD).float().contiguous()
+    sub = (torch.rand(b, h, 16, 64, generator=g).argsort(-1) % 4).reshape(b, h, 1024)[..., :tk].contiguous()
+    last = (nt - 1) * 64
+    sub[..., last:] = sub[..., last:] % 3
+    sub[..., tk - 1] = 3
+    cls = (torch.arange(tk) // 64 % 16) * 4 + sub                         # [b,h,tk]
+    k = torch.nn.functional.one_hot(cls, 64).float().permute(0, 2, 1, 3).reshape(b, tk, h * HD).contiguous()
+    v = (torch.randint(1, 9, (b, tk, h * HD), generator=g) * (torch.randint(0, 2, (b, tk, h * HD), generator=g) * 2 - 1)).float()
+    return q, k, v, dict(prof=prof, table=table, cls=cls)
+
+
+def pow2_scores(q: torch.Tensor, k: torch.Tensor, kv_batch_shift: int = 0) -> torch.Tensor:
+    """float64 q k^T per batch item and head, [b, h, tq, tk] (integers: exact); item bi reads the keys of (bi + shift) % b."""
+    b, tq, c = q.shape
+    tk, h = k.shape[1], c // HD
+    qh = q.double().view(b, tq, h, HD).transpose(1, 2)
+    kh = k.double().view(b, tk, h, HD).transpose(1, 2).roll(-kv_batch_shift, 0)
+    return qh @ kh.transpose(-1, -2)
+
+
+def pow2_tile_maxima(s: torch.Tensor) -> torch.Tensor:
+    """[..., tq, nt]: the largest score of every 64-key tile."""
+    tk = s.shape[-1]
+    nt = (tk + 63) // 64
+    sp = torch.nn.functional.pad(s, (0, nt * 64 - tk), value=float("-inf"))
+    return sp.reshape(s.shape[:-1] + (nt, 64)).amax(-1)
+
+
+def pow2_exponent_error(s: torch.Tensor) -> torch.Tensor:
+    """E_cls per row [..., tq] for the classic entry points launched at scale = ln 2: they form the exp2 argument as
+    fma32(s, c32, -float32(m * c32)) with c32 = float32(float32(ln 2) * 1.4426950408889634f) (the product rounded on its own
+    in one score per tile: both forms are evaluated), where the argument meant is s - m.  Largest deviation over the row's
+    keys and over m in the row's tile maxima (every running maximum is one of them), times ln 2 (d 2^x = ln 2 2^x dx, and
+    2^x <= 1), times 2 for margin.  Computed from the problem alone; float32 fma through float64, as _fma32 of the CPU tests."""
+    c32 = float(np.float32(np.float32(math.log(2.0)) * np.float32(1.4426950408889634)))
+    m = pow2_tile_maxima(s)                                               # [..., tq, nt]
+    mb = (m * c32).float().double()[..., None, :]                         # float32(m * c32)
+    sx = s[..., :, None]                                                  # [..., tq, tk, 1]
+    want = sx - m[..., None, :]
+    fused = (sx * c32 - mb).float().double()
+    split = ((sx * c32).float().double() - mb).float().double()
+    err = torch.maximum((fused - want).abs(), (split - want).abs())
+    return 2.0 * math.log(2.0) * err.amax((-1, -2))
+
+
+def pow2_reference(q, k, v, kv_batch_shift: int = 0, classic: bool = False):
+    """float64 reference of the power-of-two problem on the tensors' device, sharing no code with the kernel:
+    w_j = 2^(s_j - M), ref = sum w v / sum w, A = sum w |v| / sum w.  Returns dict(ref, A [b,tq,h*64], narrow (all of the
+    row's log2-weights in [-8, 0]), gap_ok (every log2-weight in [-12, 0] or <= -30), ecls (pow2_exponent_error, or zeros
+    unless classic) - the last three [b,tq,h*64] as well, constant over a head's 64 columns)."""
+    b, tq, c = q.shape
+    tk, h = k.shape[1], c // HD
+    s = pow2_scores(q, k, kv_batch_shift)
+    d = s - s.amax(-1, keepdim=True)
+    w = torch.exp2(d)
+    vh = v.double().view(b, tk, h, HD).transpose(1, 2).roll(-kv_batch_shift, 0)
+    den = w.sum(-1, keepdim=True)
+    cols = lambda x: x.transpose(1, 2).reshape(b, tq, c)                  # [b,h,tq,64] -> [b,tq,h*64]
+    rows = lambda x: cols(x[..., None].expand(b, h, tq, HD))              # [b,h,tq]    -> [b,tq,h*64]
+    ecls = pow2_exponent_error(s) if classic else torch.zeros_like(den[..., 0])
+    return dict(ref=cols(w @ vh / den), A=cols(w @ vh.abs() / den), narrow=rows(d.amin(-1) >= -8),
+                gap_ok=rows(((d >= -12) | (d <= -30)).all(-1)), ecls=rows(ecls))
+
+
+def pow2_allowance(r: dict, tk: int) -> torch.Tensor:
+    """t, the allowance for the kernel's fp32 arithmetic, relative to A = sum w |v| / sum w (e = 2^-24):
+        t = c e A + 2 E_cls A
+    narrow rows (all log2-weights in [-8, 0]; tk <= 1024, |v| <= 8): every partial sum of l (<= 2^10, multiples of 2^-8 of the
+      largest weight) and of o (<= 2^13) fits in 22 bits, so both accumulate EXACTLY in any order under any lagging
+      reference (a change of reference is a power of two).  c = 8: l built from unrounded exp2 outputs of 1 ulp each where the
+      kernel sums them on the VALU (2), 1 / l (2), the product o * (1 / l) (1), slack (3).
+    other rows: c = tk + 8 - one fp32 rounding per accumulated key (the matrix core's internal order is not documented).
+    E_cls: pow2_exponent_error, zero for the prescaled entry points; it moves every weight by at most a factor 1 +- E_cls,
+      hence numerator and denominator by E_cls A each."""
+    c = torch.where(r["narrow"], torch.full_like(r["A"], 8.0), torch.full_like(r["A"], tk + 8.0))
+    return c * 2.0 ** -24 * r["A"] + 2.0 * r["ecls"] * r["A"]
+
+
+def pow2_bound(r: dict, tk: int, dt) -> torch.Tensor:
+    """Per-element bound: one rounding to the output type of a value within t of ref, u (|ref| + t) + t."""
+    t = pow2_allowance(r, tk)
+    return torch.finfo(dt).eps / 2 * (r["ref"].abs() + t) + t
+
+
+def pow2_online_softmax_f32(s: torch.Tensor, vh: torch.Tensor, reverse: bool = False) -> torch.Tensor:
+    """The plain online softmax in float32 on the CPU, one key at a time with a per-key running maximum (numpy, operation by
+    operation): m' = max(m, s_j), alpha = 2^(m - m'), p = 2^(s_j - m'), l = l alpha + p, o = o alpha + p v_j; out = o / l.
+    s [b,h,tq,tk] integers, vh [b,h,tk,64]; keys in reversed order if asked.  Returns float32 [b,h,tq,64], not rounded."""
+    sn, vn = s.numpy().astype(np.float32), vh.numpy().astype(np.float32)
+    b, h, tq, tk = sn.shape
+    m = np.full((b, h, tq), -np.inf, np.float32)
+    l = np.zeros((b, h, tq), np.float32)
+    o = np.zeros((b, h, tq, HD), np.float32)
+    with np.errstate(invalid="ignore"):
+        for j in (range(tk - 1, -1, -1) if reverse else range(tk)):
+            mn = np.maximum(m, sn[..., j])
+            alpha = np.exp2(m - mn).astype(np.float32)
+            p = np.exp2(sn[..., j] - mn).astype(np.float32)
+            l = (l * alpha).astype(np.float32) + p
+            o = (o * alpha[..., None]).astype(np.float32) + (p[..., None] * vn[:, :, None, j, :]).astype(np.float32)
+            m = mn
+    return torch.from_numpy((o / l[..., None]).astype(np.float32))
 
 
 # ------------------------------------------------------------------------------------------ integer convolution

@@ -167,6 +167,168 @@ def test_uniform_attention_mean_is_exact(tk):
     assert torch.equal(exp.float().double(), exp)                           # ... and in fp32: integer sum times 2^-n
 
 
+# --------------------------------------------------------------------------------- power-of-two softmax weights
+# every (Tq, Tk) of test_power_of_two_softmax_every_rescale_path, batch and heads cut down where only the token counts matter
+POW2_SHAPES = [(130, 328, 2, 2), (200, 512, 2, 3), (65, 129, 1, 2), (96, 1024, 1, 2), (7, 64, 2, 1)]
+_POW2 = {}
+
+
+def _pow2(shape, variant):
+    """(q, k, v, info, {shift: (s, reference dict)}) of one problem, built once for the tests below."""
+    if (shape, variant) not in _POW2:
+        tq, tk, b, h = shape
+        q, k, v, info = X.pow2_problem(tq, tk, b, h, seed=tq + tk + h, variant=variant)
+        per_shift = {sh: (X.pow2_scores(q, k, sh), X.pow2_reference(q, k, v, sh)) for sh in ((0, 1) if b >= 2 else (0,))}
+        _POW2[(shape, variant)] = (q, k, v, info, per_shift)
+    return _POW2[(shape, variant)]
+
+
+@pytest.mark.parametrize("variant", X.POW2_VARIANTS)
+@pytest.mark.parametrize("shape", POW2_SHAPES, ids=str)
+def test_power_of_two_problem_keeps_its_conditions(shape, variant):
+    """Conditions 1 - 4 of the construction: integer tables in [-127, 127] whose scores are the prescribed table
+    entries; every final log2-weight in [-12, 0] or <= -30; flat rows narrow and at least a quarter of the mixed launch
+    narrow; every profile present at every shape that has the key tiles for it, with the tile maxima it promises."""
+    tq, tk, b, h = shape
+    nt = (tk + 63) // 64
+    q, k, v, info, per_shift = _pow2(shape, variant)
+    prof, table, cls = info["prof"], info["table"], info["cls"]
+    name = {n: i for i, n in enumerate(X.POW2_ALL)}
+    # 1. integers in range, exact in both 16-bit types; one-hot keys; q k^T is the prescribed table
+    assert torch.equal(q, q.round()) and float(q.abs().max()) <= 127
+    for dt in DT16:
+        for t in (q, k, v):
+            assert torch.equal(t.to(dt).float(), t)
+    assert bool(((k == 0) | (k == 1)).all()) and torch.equal(k.view(b, tk, h, 64).sum(-1), torch.ones(b, tk, h))
+    assert int(v.abs().min()) >= 1 and int(v.abs().max()) <= 8
+    assert torch.equal(cls // 4, (torch.arange(tk) // 64).expand(b, h, tk))
+    for sh, (s, r) in per_shift.items():
+        want = torch.gather(table, 3, cls.roll(-sh, 0)[:, :, None, :].expand(b, h, tq, tk))
+        assert torch.equal(s, want.double())
+        # 2. the gap, row by row
+        assert bool(r["gap_ok"].all()), f"{int((~r['gap_ok']).sum()) // 64} rows with a log2-weight inside (-30, -12)"
+        # 3. narrow rows
+        nar = r["narrow"].view(b, tq, h, 64)[..., 0].transpose(1, 2)                     # [b,h,tq]
+        assert bool(nar[prof == name["flat"]].all())
+        assert bool(nar[prof == name["tail-max"]].all()) and bool(nar[prof == name["ripple"]].all())
+        if variant == "mixed":
+            assert float(nar.double().mean()) >= 0.25
+        # the lone maximum of a tail-max row is key tk - 1
+        tm = prof == name["tail-max"]
+        assert bool((s.argmax(-1)[tm] == tk - 1).all()) and bool(((s == s.amax(-1, keepdim=True)).sum(-1)[tm] == 1).all())
+        # what the profiles promise of the tile maxima, relative to the first tile's
+        rel = X.pow2_tile_maxima(s)
+        rel = rel - rel[..., :1]
+        top, arg = rel.amax(-1), rel.argmax(-1)
+        big = (rel >= 60).sum(-1)
+        if nt > 1:
+            for n, lo, hi in (("jump", 37, 40), ("overflow-l", 102, 105), ("overflow-inf", 137, 140)):
+                sel = prof == name[n]
+                assert bool(((top[sel] >= lo) & (top[sel] <= hi) & (arg[sel] > 0)).all()), n
+            sel = prof == name["keeper"]
+            assert bool(((big[sel] == 1) & (arg[sel] > 0) & (arg[sel] < nt - 1) & (top[sel] == 70)).all())
+            sel = prof == name["keeper-last"]
+            assert bool(((big[sel] == 1) & (arg[sel] == nt - 1) & (top[sel] >= 67)).all())
+            sel = prof == name["keeper-twice"]
+            assert bool(((big[sel] == 2) & (top[sel] == 135) & (arg[sel] < nt - 1) & (rel[..., 1:3].amax(-1)[sel] == 70)).all())
+            sel = prof == name["fall"]
+            assert bool((rel[..., 1:].amax(-1)[sel] <= -30).all())
+            sel = prof == name["stair"]
+            step = rel[..., 1:] - rel[..., :-1]
+            assert bool((step[sel][:, :max(nt - 2, 0)] >= 3).all()) and bool((step[sel] >= 0).all())
+    # 4. every profile that has the tiles for it occurs, in this very shape
+    have = set(torch.unique(prof).tolist())
+    pool = X.POW2_ALL if variant == "overflow" else X.POW2_PROFILES
+    avail = {name[n] for n in pool if X.POW2_MIN_TILES[n] <= nt}
+    if variant == "banded":
+        # (row // 32 + head + batch) % P reaches every profile only where there are enough bands, heads and batch items
+        reach = {(r32 + hh + bb) % len(X.POW2_PROFILES) for r32 in range((tq + 31) // 32) for hh in range(h) for bb in range(b)}
+        avail = {name["flat"]} | {i for i in avail if i in reach}
+        assert have == avail, (sorted(have), sorted(avail))
+        if shape == (200, 512, 2, 3):
+            assert have == set(range(len(X.POW2_PROFILES)))
+    else:
+        assert have == (avail | {name["flat"]}), (sorted(have), sorted(avail))
+        if nt >= 6 and tq >= 11:
+            assert have == {name[n] for n in pool}
+    if variant == "overflow":
+        ov = prof >= len(X.POW2_PROFILES)
+        assert not bool(ov[:, 1::2].any()) and not bool(ov[:, :, 64:].any())       # rows < 64 of even heads only
+
+
+def test_power_of_two_profile_assignments():
+    """mixed: every 16-row query tile of a wave holds every profile; banded: 32 consecutive rows share one profile; the full
+    batch and head counts of the first GPU shape reach every profile in both."""
+    p = len(X.POW2_PROFILES)
+    mixed, _ = X.pow2_profile_ids(130, 328, 16, 16, "mixed")
+    banded, kpos = X.pow2_profile_ids(130, 328, 16, 16, "banded")
+    for r0 in range(0, 128, 16):
+        assert len(torch.unique(mixed[3, 5, r0:r0 + 16])) == p                  # 6 key tiles: enough for keeper-twice
+    assert set(torch.unique(mixed).tolist()) == set(range(p)) == set(torch.unique(banded).tolist())
+    for r0 in range(0, 130, 32):
+        assert bool((banded[:, :, r0:r0 + 32] == banded[:, :, r0:r0 + 1]).all())
+        assert bool((kpos[:, :, r0:r0 + 32] == kpos[:, :, r0:r0 + 1]).all())
+    # a profile without the tiles for it is recorded as flat, never silently kept under its own name
+    small, _ = X.pow2_profile_ids(200, 150, 2, 3, "overflow")
+    assert set(torch.unique(small).tolist()) == {i for i, n in enumerate(X.POW2_ALL) if X.POW2_MIN_TILES[n] <= 3}
+
+
+@pytest.mark.parametrize("variant", ["mixed", "overflow"])
+@pytest.mark.parametrize("shape", POW2_SHAPES, ids=str)
+def test_power_of_two_bound_holds_for_float32_online_softmax(shape, variant):
+    """The plain online softmax in float32 on the CPU, one key at a time, forward and in reversed key order: within a QUARTER
+    of the allowance t on narrow rows and within t on all rows (before the output rounding), and within the full bound after
+    rounding to either 16-bit type.  If it were not, the operation count behind c would be wrong."""
+    tq, tk, b, h = shape
+    q, k, v, info, per_shift = _pow2(shape, variant)
+    for sh, (s, r) in per_shift.items():
+        vh = v.view(b, tk, h, 64).transpose(1, 2).roll(-sh, 0)
+        t = X.pow2_allowance(r, tk)
+        for reverse in (False, True):
+            emu = X.pow2_online_softmax_f32(s, vh, reverse).transpose(1, 2).reshape(b, tq, h * 64)
+            diff = (emu.double() - r["ref"]).abs()
+            unit = 2.0 ** -24 * r["A"]
+            nar = r["narrow"]
+            worst_n = float((diff / unit)[nar].max())
+            worst_o = float((diff / t)[~nar].max()) if bool((~nar).any()) else 0.0
+            print(f"{shape} {variant} shift {sh} reversed {reverse}: narrow rows {worst_n:.2f} units of 2^-24 A (c = 8); "
+                  f"other rows {worst_o:.4f} of t (c = {tk + 8})")
+            assert bool((diff[nar] <= t[nar] / 4).all()) and bool((diff <= t).all())
+            for dt in DT16:
+                X.assert_within(emu.to(dt), r["ref"], X.pow2_bound(r, tk, dt), f"float32 online softmax, {dt}")
+
+
+def test_power_of_two_bound_sees_a_tail_key_counted_twice_and_a_forgotten_rescale():
+    """Two local errors on the reference side: the clamped copy of key Tk - 1 left unmasked once (every row moves, the tail-max
+    rows most), and ONE query row whose accumulator misses the 2^-64 of the range keeper (its first tiles weigh 2^64 too
+    much) - the checker names that row."""
+    shape = (130, 328, 2, 2)
+    tq, tk, b, h = shape
+    q, k, v, info, per_shift = _pow2(shape, "mixed")
+    s, r = per_shift[0]
+    bound = X.pow2_bound(r, tk, torch.bfloat16)
+    X.assert_within(r["ref"].bfloat16(), r["ref"], bound, "the reference itself")
+    k2, v2 = torch.cat([k, k[:, -1:]], 1), torch.cat([v, v[:, -1:]], 1)
+    twice = X.pow2_reference(q, k2, v2)["ref"]
+    tm = (info["prof"] == X.POW2_ALL.index("tail-max")).transpose(1, 2)[..., None].expand(b, tq, h, 64).reshape(b, tq, h * 64)
+    over = (twice - r["ref"]).abs() > bound
+    assert float(over[tm].double().mean()) > 0.9
+    with pytest.raises(AssertionError):
+        X.assert_within(twice.bfloat16(), r["ref"], bound, "tail key counted twice")
+    # keeper row (batch 0, head 0): o of the tiles before the event keeps its scale, l is scaled
+    row = int((info["prof"][0, 0] == X.POW2_ALL.index("keeper")).nonzero()[0])
+    d = s[0, 0, row] - s[0, 0, row].max()
+    w = torch.exp2(d)
+    event = int(d.argmax()) // 64
+    w_bad = w.clone()
+    w_bad[:event * 64] *= 2.0 ** 64
+    vh = v.view(b, tk, h, 64)[0, :, 0].double()
+    bad = r["ref"].clone()
+    bad[0, row, :64] = (w_bad @ vh) / w.sum()
+    with pytest.raises(AssertionError, match=rf"row {row} "):
+        X.assert_within(bad.bfloat16(), r["ref"], bound, "forgotten rescale")
+
+
 # ----------------------------------------------------------------------------------------- the checker notices
 def _correct_answer(dt):
     a, w, b = X.int_gemm(300, 132, 3072, seed=21)
