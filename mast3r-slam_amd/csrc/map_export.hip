@@ -1,16 +1,15 @@
 // Dense map export (mast3r_slam/export.py): world points and colours of K keyframes, filtered by average confidence,
 // compacted in source order and optionally thinned to one point per voxel.  Stage A is count -> scan -> scatter over
-// 1024-point workgroup tiles; stage B claims voxels in an open-addressing table with integer atomics and then reuses the
-// same count -> scan -> scatter.  Output positions come from an exclusive scan, never from an atomic counter, and the
+// 1024-point workgroup tiles; stage B claims voxels in the key table of table_dev.h and then reuses the same
+// count -> scan -> scatter.  Output positions come from an exclusive scan, never from an atomic counter, and the
 // only atomics are integer CAS / max, so the bytes of every output are the same on every call.
 #include "common.h"
 #include "sim3_dev.h"
 #include "map_points.h"
 #include "compact_dev.h"
+#include "table_dev.h"
 
 namespace {
-
-constexpr unsigned long long kEmpty = ~0ull;  // a packed voxel key uses 63 bits
 
 // Kept points per workgroup.  X is only read by threads with a point that passed the confidence test.
 __global__ void __launch_bounds__(kThreads) k_export_count(const float *const *__restrict__ X,
@@ -63,21 +62,15 @@ __global__ void __launch_bounds__(kThreads) k_export_scatter(const float *const 
 // ---- stage B -----------------------------------------------------------------------------------------------------
 struct VoxelWs {
     int32_t *hdr, *offs;
-    uint32_t *slot;                  // [M] table slot of each point, 0xffffffff = dropped
+    uint32_t *slot;                  // [M] table slot of each point, kNoSlot = dropped
     unsigned long long *keys, *vals; // [slots]
     int64_t slots, blocks, bytes;
 };
 
-inline int64_t voxel_slots(int64_t M) {
-    int64_t s = 1024;
-    while (s < 2 * M) s *= 2;        // at most half full
-    return s;
-}
-
 inline VoxelWs voxel_ws(void *ws, int64_t M) {
     VoxelWs v;
     v.blocks = (M + kTile - 1) / kTile;
-    v.slots = voxel_slots(M);
+    v.slots = table_slots(2 * M);
     char *p = (char *)ws;
     v.hdr = (int32_t *)p;
     v.offs = v.hdr + kHdrWords;
@@ -98,12 +91,6 @@ __device__ __forceinline__ unsigned conf_key(float c) {
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
-__device__ __forceinline__ unsigned long long mix64(unsigned long long x) {
-    x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ull;
-    x ^= x >> 27; x *= 0x94d049bb133111ebull;
-    return x ^ (x >> 31);
-}
-
 // One point per thread: claim the voxel's slot (CAS on the key) and raise its value to (confidence key, ~i): the
 // largest confidence wins, equal confidences go to the smaller i.  Both atomics commute, so the winner does not depend
 // on the order in which points arrive (the slot a voxel lands in does; nothing that is output depends on it).
@@ -111,33 +98,22 @@ __global__ void __launch_bounds__(kThreads) k_voxel_insert(const float *__restri
                                                             int64_t M, float voxel, unsigned long long *__restrict__ keys,
                                                             unsigned long long *__restrict__ vals, int64_t slots,
                                                             uint32_t *__restrict__ slot, int32_t *__restrict__ hdr) {
-    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    const int64_t i = row_of();
     if (i >= M) return;
     const float vx = floorf(points[3 * i] / voxel), vy = floorf(points[3 * i + 1] / voxel),
                 vz = floorf(points[3 * i + 2] / voxel);
     constexpr float kLim = 1048576.f;                                           // 2^20: 21 bits per axis after the offset
     if (!(fabsf(vx) < kLim && fabsf(vy) < kLim && fabsf(vz) < kLim)) {
-        slot[i] = 0xffffffffu;
+        slot[i] = kNoSlot;
         atomicAdd(&hdr[1], 1);
         return;
     }
-    const unsigned long long key = ((unsigned long long)((int)vx + 1048576) << 42) |
-                                   ((unsigned long long)((int)vy + 1048576) << 21) |
-                                   (unsigned long long)((int)vz + 1048576);
     const unsigned long long val = ((unsigned long long)conf_key(conf[i]) << 32) | (unsigned)~(unsigned)i;
-    unsigned long long s = mix64(key) & (unsigned long long)(slots - 1);
-    for (int64_t probe = 0; probe < slots; ++probe) {                           // the table is at most half full
-        unsigned long long cur = keys[s];
-        if (cur == kEmpty) cur = atomicCAS(&keys[s], kEmpty, key);
-        if (cur == kEmpty || cur == key) {
-            atomicMax(&vals[s], val);
-            slot[i] = (uint32_t)s;
-            return;
-        }
-        s = (s + 1) & (unsigned long long)(slots - 1);
-    }
-    slot[i] = 0xffffffffu;                                                      // unreachable: slots >= 2 M
-    atomicAdd(&hdr[1], 1);
+    bool claimed;
+    const uint32_t s = key_claim(keys, slots, cell_key((int)vx + kCellBias, (int)vy + kCellBias, (int)vz + kCellBias), claimed);
+    slot[i] = s;
+    if (s != kNoSlot) atomicMax(&vals[s], val);
+    else atomicAdd(&hdr[1], 1);                                                 // unreachable: slots >= 2 M
 }
 
 // Bits of the thread's four consecutive points that won their voxel.
@@ -149,7 +125,7 @@ __device__ __forceinline__ unsigned voxel_winners(const uint32_t *__restrict__ s
         const int64_t i = i0 + j;
         if (i >= M) continue;
         const uint32_t s = slot[i];
-        if (s != 0xffffffffu && (unsigned)vals[s] == (unsigned)~(unsigned)i) keep |= 1u << j;
+        if (s != kNoSlot && (unsigned)vals[s] == (unsigned)~(unsigned)i) keep |= 1u << j;
     }
     return keep;
 }
@@ -236,7 +212,7 @@ int m3_map_export_scatter(const float *const *X, const float *const *C, const vo
 }
 
 int64_t m3_map_voxel_table_slots(int64_t M) {
-    return M >= 1 && M <= 0x7fffffff ? voxel_slots(M) : 0;
+    return M >= 1 && M <= 0x7fffffff ? table_slots(2 * M) : 0;
 }
 
 int64_t m3_map_voxel_ws_bytes(int64_t M) {

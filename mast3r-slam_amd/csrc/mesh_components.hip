@@ -20,8 +20,7 @@
 // Header words: [0] V2, [1] F2 (the totals of the scan), [4] components with a face, [5] largest, [6] winner (-1: no
 // valid face), [7] invalid faces, [8..9] the uint64 winner key, [10..12] the filter of the last m3_mesh_components_count
 // (min_faces, the bits of min_fraction, largest_only), which the scatter reads back; the others are unused.
-#include "common.h"
-#include "compact_dev.h"
+#include "table_dev.h"
 
 namespace {
 
@@ -37,8 +36,6 @@ struct CcWs {
     int64_t offV, offF, parent, label, count, remap, bytes;      // byte offsets into ws
 };
 
-inline int64_t pad16(int64_t b) { return (b + 15) / 16 * 16; }
-
 inline bool cc_layout(int64_t V, int64_t F, CcWs &m) {
     if (V < 0 || F < 0 || V > kMaxRows || F > kMaxRows) return false;
     m.ntileV = (V + kThreads - 1) / kThreads;
@@ -52,11 +49,6 @@ inline bool cc_layout(int64_t V, int64_t F, CcWs &m) {
     m.bytes = m.remap + pad16(4 * V);
     return true;
 }
-
-// A grid of at least one workgroup, so that the header work of thread 0 is done for V = 0 too.
-inline dim3 grid_of(int64_t tiles) { return dim3((unsigned)(tiles > 0 ? tiles : 1)); }
-
-__device__ __forceinline__ int64_t row_of() { return (int64_t)blockIdx.x * kThreads + threadIdx.x; }
 
 __device__ __forceinline__ int32_t load_parent(const int32_t *parent, int32_t x) {
     return __hip_atomic_load(parent + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -97,12 +89,6 @@ __device__ __forceinline__ void unite(int32_t *parent, int32_t a, int32_t b) {
     }
 }
 
-__device__ __forceinline__ bool face_valid(const int32_t *__restrict__ faces, int64_t f, int64_t V, int32_t (&r)[3]) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i) r[i] = faces[(size_t)3 * f + i];
-    return r[0] >= 0 && r[0] < V && r[1] >= 0 && r[1] < V && r[2] >= 0 && r[2] < V;
-}
-
 __global__ void __launch_bounds__(kThreads) k_cc_init(int64_t V, int32_t *__restrict__ parent, int32_t *__restrict__ count,
                                                        int32_t *__restrict__ hdr) {
     const int64_t v = row_of();
@@ -116,9 +102,8 @@ __global__ void __launch_bounds__(kThreads) k_cc_hook(const int32_t *__restrict_
                                                        int32_t *__restrict__ hdr) {
     const int64_t f = row_of();
     int32_t r[3];
-    const bool in = f < F, ok = in && face_valid(faces, f, V, r);
-    const unsigned long long bad = __ballot(in && !ok);
-    if (bad && (threadIdx.x & 63) == 0) atomicAdd(hdr + kInvalid, (int)__popcll(bad));   // F < 2^31: no overflow
+    const bool in = f < F, ok = in && load_face(faces, f, V, r);
+    count_invalid(in, ok, hdr + kInvalid);
     if (!ok) return;
     if (r[0] != r[1]) unite(parent, r[0], r[1]);
     if (r[1] != r[2]) unite(parent, r[1], r[2]);
@@ -138,7 +123,7 @@ __global__ void __launch_bounds__(kThreads) k_cc_count_faces(const int32_t *__re
                                                               const int32_t *__restrict__ label, int32_t *__restrict__ count) {
     const int64_t f = row_of();
     int32_t r[3];
-    const bool ok = f < F && face_valid(faces, f, V, r);
+    const bool ok = f < F && load_face(faces, f, V, r);
     const unsigned long long any = __ballot(ok);
     if (!any) return;                                                           // wave-uniform
     const int32_t root = ok ? label[r[0]] : -1;
@@ -206,7 +191,7 @@ __device__ __forceinline__ bool vertex_kept(int64_t v, int64_t V, const int32_t 
 __device__ __forceinline__ bool face_kept(const int32_t *__restrict__ faces, int64_t f, int64_t V, int64_t F,
                                           const int32_t *__restrict__ label, const int32_t *__restrict__ count,
                                           const int32_t *__restrict__ hdr, const Filter &fl, int32_t (&r)[3]) {
-    return f < F && face_valid(faces, f, V, r) && component_kept(label[r[0]], count, hdr, fl);
+    return f < F && load_face(faces, f, V, r) && component_kept(label[r[0]], count, hdr, fl);
 }
 
 // Kept vertices per tile.  The scatter has no filter arguments: it reads the filter this kernel leaves in the header (the
@@ -274,8 +259,6 @@ __global__ void __launch_bounds__(kThreads) k_cc_faces(const int32_t *__restrict
     if (rows_out) rows_out[o] = f;
 }
 
-inline bool ws_ok(const void *ws) { return ws && ((uintptr_t)ws & 15) == 0; }
-
 }  // namespace
 
 extern "C" {
@@ -296,7 +279,7 @@ int m3_mesh_components_label(const int32_t *faces, int64_t V, int64_t F, void *w
     char *p = (char *)ws;
     int32_t *hdr = (int32_t *)ws, *parent = (int32_t *)(p + m.parent), *label = (int32_t *)(p + m.label);
     int32_t *count = (int32_t *)(p + m.count);
-    const dim3 gv = grid_of(m.ntileV), gf = grid_of(m.ntileF), block(kThreads);
+    const dim3 gv = grid_of(V), gf = grid_of(F), block(kThreads);     // one workgroup for V = 0: thread 0 clears the header
     hipLaunchKernelGGL(k_cc_init, gv, block, 0, st, V, parent, count, hdr);
     if (F > 0) hipLaunchKernelGGL(k_cc_hook, gf, block, 0, st, faces, V, F, parent, hdr);
     hipLaunchKernelGGL(k_cc_flatten, gv, block, 0, st, V, parent, label, labels_out);
@@ -323,8 +306,8 @@ int m3_mesh_components_count(void *ws, int64_t V, int64_t F, const int32_t *face
     int32_t *cntV = (int32_t *)(p + m.offV), *cntF = (int32_t *)(p + m.offF);
     const Filter fl{min_faces, largest_only, min_fraction};
     const dim3 block(kThreads);
-    hipLaunchKernelGGL(k_cc_count_vertices, grid_of(m.ntileV), block, 0, st, V, label, count, hdr, fl, cntV);
-    hipLaunchKernelGGL(k_cc_count_kept_faces, grid_of(m.ntileF), block, 0, st, faces, V, F, label, count, hdr, fl, cntF);
+    hipLaunchKernelGGL(k_cc_count_vertices, grid_of(V), block, 0, st, V, label, count, hdr, fl, cntV);
+    hipLaunchKernelGGL(k_cc_count_kept_faces, grid_of(F), block, 0, st, faces, V, F, label, count, hdr, fl, cntF);
     launch_scan(st, hdr, ScanJob{cntV, m.ntileV}, ScanJob{cntF, m.ntileF});                         // V2 to word 0, F2 to word 1
     M3_CHECK_LAUNCH("m3_mesh_components_count");
     return M3_OK;
@@ -344,9 +327,9 @@ int m3_mesh_components_scatter(const float *vertices, const uint8_t *colors, con
     const int32_t *offV = (const int32_t *)(p + m.offV), *offF = (const int32_t *)(p + m.offF);
     int32_t *remap = (int32_t *)(p + m.remap);
     const dim3 block(kThreads);
-    hipLaunchKernelGGL(k_cc_vertices, grid_of(m.ntileV), block, 0, st, vertices, colors, V, label, count, hdr, offV, V2, remap,
+    hipLaunchKernelGGL(k_cc_vertices, grid_of(V), block, 0, st, vertices, colors, V, label, count, hdr, offV, V2, remap,
                        vertices_out, colors_out, vertex_rows_out);
-    hipLaunchKernelGGL(k_cc_faces, grid_of(m.ntileF), block, 0, st, faces, V, F, label, count, hdr, offF, remap, F2, faces_out,
+    hipLaunchKernelGGL(k_cc_faces, grid_of(F), block, 0, st, faces, V, F, label, count, hdr, offF, remap, F2, faces_out,
                        face_rows_out);
     M3_CHECK_LAUNCH("m3_mesh_components_scatter");
     return M3_OK;

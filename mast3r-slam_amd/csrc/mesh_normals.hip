@@ -1,7 +1,7 @@
 // Per-vertex normals of a triangle mesh and vertex colours lit with them (mast3r_slam/normals.py).
 // The rule is stated once, in include/m3slam.h; tests/normals_twin.py restates it in numpy.
 //
-// clear -> faces -> vertices, whatever V and F are.  A face adds its unit normal, scaled by 2^24 and rounded to an
+// fill -> faces -> vertices, whatever V and F are.  A face adds its unit normal, scaled by 2^24 and rounded to an
 // integer, to three int64 sums of each of its three vertices.  The only atomics are 64-bit integer adds, which commute:
 // the sums depend neither on the order of the faces nor on the order of the threads, so two calls give identical bytes
 // (a float atomic sum would not: DESIGN.md section 7k).  The vertex pass divides by the length in float64.
@@ -12,21 +12,15 @@
 // lanes add to the same row (a fan around one hub) the wave sums them in registers and one lane adds.
 //
 // Compiled with -ffp-contract=off: every fp32 and float64 operation of the rule is rounded on its own.
-#include "common.h"
+#include "table_dev.h"
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int kThreads = 256;
 constexpr int64_t kMaxRows = 0x7fffffff;      // V and F stay below 2^31
 constexpr float kMinLen2 = 0x1p-80f;          // faces with a smaller squared length of e1 x e2 contribute nothing
 constexpr float kScale = 16777216.0f;         // 2^24
 constexpr int kShared = M3_WAVE / 2;          // lanes on one row from which the wave adds them up first
-
-inline int64_t pad16(int64_t b) { return (b + 15) / 16 * 16; }
-inline dim3 grid_of(int64_t rows) { return dim3((unsigned)(rows > 0 ? m3_cdiv(rows, kThreads) : 1)); }
-
-__device__ __forceinline__ int64_t row_of() { return (int64_t)blockIdx.x * kThreads + threadIdx.x; }
 
 // Sum k of a vertex row: three planes of V sums, so that the adds of one wave instruction to neighbouring rows are
 // contiguous.
@@ -38,18 +32,10 @@ __device__ __forceinline__ long long wave_sum(long long v) {
     return v;
 }
 
-// The sums are cleared 16 bytes per thread (the workspace is 16-byte aligned and a multiple of 16 bytes long).
-__global__ void __launch_bounds__(kThreads) k_normals_clear(int4 *__restrict__ ws, int64_t n16) {
-    const int64_t i = row_of();
-    if (i < n16) ws[i] = int4{0, 0, 0, 0};
-}
-
 // q of face f: false when the face contributes nothing (an index outside [0, V): nothing is dereferenced).
 __device__ __forceinline__ bool face_normal(const float *__restrict__ vertices, const int32_t *__restrict__ faces, int64_t V,
                                             int64_t f, int32_t (&r)[3], long long (&q)[3]) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i) r[i] = faces[3 * f + i];
-    if (r[0] < 0 || r[1] < 0 || r[2] < 0 || r[0] >= V || r[1] >= V || r[2] >= V) return false;
+    if (!load_face(faces, f, V, r)) return false;
     float p[3][3];
 #pragma unroll
     for (int i = 0; i < 3; ++i)
@@ -175,11 +161,11 @@ int m3_mesh_normals_launches(void) { return 3; }
 int m3_mesh_normals(const float *vertices, const int32_t *faces, int64_t V, int64_t F, void *ws, int64_t ws_bytes,
                     float *normals, void *stream) {
     const int64_t need = m3_mesh_normals_ws_bytes(V);
-    M3_REQUIRE(need > 0 && F >= 0 && F <= kMaxRows && ws && ((uintptr_t)ws & 15) == 0 && ws_bytes >= need);
+    M3_REQUIRE(need > 0 && F >= 0 && F <= kMaxRows && ws_ok(ws) && ws_bytes >= need);
     M3_REQUIRE((V == 0 || (vertices && normals)) && (F == 0 || faces));
     M3_REQUIRE(aligned4(vertices) && aligned4(faces) && aligned4(normals));
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_normals_clear, grid_of(need / 16), dim3(kThreads), 0, st, (int4 *)ws, need / 16);
+    launch_fill(st, ws, need / 16, need / 16, 0, 0);                            // the workspace is a multiple of 16 bytes long
     // V = 0: no index is valid; F = 0: no thread has a face.  The launches are kept so that their number is fixed.
     hipLaunchKernelGGL(k_normals_faces, grid_of(F), dim3(kThreads), 0, st, vertices, faces, V, F, (unsigned long long *)ws);
     hipLaunchKernelGGL(k_normals_vertices, grid_of(V), dim3(kThreads), 0, st, (const long long *)ws, V, normals);

@@ -6,9 +6,10 @@
 //          (its leader; leaders per tile) -> one thread per face (leaders of its rows, the drops, claim or lower the
 //          key's slot) -> winners per tile -> one scan of both counts.
 // scatter: leaders write their cluster (and their output row into ws) -> winning faces, and cluster_of.
-// Eight launches whatever the mesh holds.  The only atomics are integer ones whose results commute: CAS to claim a slot,
-// min for the leader row and for the face row, add for the sums.  Which slot a cell or a face key lands in depends on the
-// arrival order; nothing that is output does.  Output rows are tile offset + rank (compact_dev.h), never a counter.
+// Eight launches whatever the mesh holds.  The cells live in the key table of table_dev.h.  The only atomics are integer
+// ones whose results commute: the claim of a slot, min for the leader row and for the face row, add for the sums.  Which
+// slot a face key lands in depends on the arrival order, as for a cell; nothing that is output does.  Output rows are
+// tile offset + rank (compact_dev.h), never a counter.
 //
 // A face key is the triple of its clusters' LEADER rows, rotated so the smallest comes first: clusters are output in the
 // order of their leaders, so this is the rotation of the output rows, and the face pass does not have to wait for the
@@ -24,19 +25,17 @@
 // voxel_size, which the scatter reads back; the others are 0.
 //
 // Compiled with -ffp-contract=off: every float64 operation of the rule is rounded on its own.
-#include "common.h"
-#include "compact_dev.h"
+#include "table_dev.h"
 #pragma clang fp contract(off)
 
 namespace {
 
 constexpr int kCountLaunches = 6, kScatterLaunches = 2;
-constexpr int kSvHdrWords = 16;
+constexpr int kSvHdrWords = 16;               // the fill zeroes them: kSvHdrWords / 4 int4 at the head of ws
 constexpr int kOutOfRange = 2, kInvalid = 3, kVoxel = 4;
 constexpr int64_t kMaxRows = 0x7fffffff;      // V and F stay below 2^31
-constexpr unsigned long long kEmptyKey = ~0ull;   // a packed cell key uses 63 bits
 constexpr int32_t kNoRow = 0x7fffffff;        // an empty leader / face slot: above every row
-constexpr double kCellLim = 1048576.0;        // 2^20: 21 bits per axis after the offset
+constexpr double kCellLim = 1048576.0;        // 2^20: 21 bits per axis after the offset (kCellBias)
 constexpr double kQ = 16777216.0;             // 2^24
 
 struct SvWs {
@@ -44,27 +43,19 @@ struct SvWs {
     int64_t offV, offF, vslot, vlead, vrow, fslot, keys, lead, ftab, cnt, sums, bytes;      // byte offsets into ws
 };
 
-inline int64_t pad16(int64_t b) { return (b + 15) / 16 * 16; }
-
-inline int64_t table_slots(int64_t n) {
-    int64_t s = 1024;
-    while (s < 2 * n) s *= 2;                 // at most half full
-    return s;
-}
-
 inline bool sv_layout(int64_t V, int64_t F, SvWs &m) {
     if (V < 0 || F < 0 || V > kMaxRows || F > kMaxRows) return false;
     m.ntileV = V ? (V + kThreads - 1) / kThreads : 1;    // at least one tile: the one workgroup of an empty grid
     m.ntileF = F ? (F + kThreads - 1) / kThreads : 1;    // writes its count, 0
-    m.SV = table_slots(V);
-    m.SF = table_slots(F);
+    m.SV = table_slots(2 * V);
+    m.SF = table_slots(2 * F);
     m.offV = kSvHdrWords * 4;
     m.offF = m.offV + pad16(4 * m.ntileV);
     m.vslot = m.offF + pad16(4 * m.ntileF);
     m.vlead = m.vslot + pad16(4 * V);
     m.vrow = m.vlead + pad16(4 * V);
     m.fslot = m.vrow + pad16(4 * V);
-    m.keys = m.fslot + pad16(4 * F);          // from here on the clear kernel fills: ff .. | 7fffffff .. | 0 ..
+    m.keys = m.fslot + pad16(4 * F);          // from here on the fill: ff .. | 7fffffff .. | 0 ..
     m.lead = m.keys + 8 * m.SV;
     m.ftab = m.lead + 4 * m.SV;
     m.cnt = m.ftab + 4 * m.SF;
@@ -97,28 +88,6 @@ inline SvPtr sv_ptr(void *ws, const SvWs &m) {
     return q;
 }
 
-inline dim3 grid_of(int64_t tiles) { return dim3((unsigned)tiles); }
-
-__device__ __forceinline__ int64_t row_of() { return (int64_t)blockIdx.x * kThreads + threadIdx.x; }
-
-__device__ __forceinline__ unsigned long long mix64(unsigned long long x) {
-    x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ull;
-    x ^= x >> 27; x *= 0x94d049bb133111ebull;
-    return x ^ (x >> 31);
-}
-
-// Tables and header are cleared by a kernel, 16 bytes per thread: a captured memset left its words uncleared on replay
-// (DESIGN.md section 7l).  int4 [0, a) = ff .., [a, b) = 7fffffff .., [b, n) = 0.
-__global__ void __launch_bounds__(kThreads) k_sv_clear(int4 *__restrict__ tables, int64_t a, int64_t b, int64_t n,
-                                                        int4 *__restrict__ hdr, float voxel) {
-    const int64_t i = row_of();
-    if (i < kSvHdrWords / 4) hdr[i] = int4{0, 0, 0, 0};
-    if (i == 1) hdr[1].x = __float_as_int(voxel);                               // word kVoxel
-    if (i >= n) return;
-    const int w = i < a ? -1 : i < b ? kNoRow : 0;
-    tables[i] = int4{w, w, w, w};
-}
-
 // Cell and quantised offset of one coordinate; false when it is out of range (NaN and infinities fail the test).
 __device__ __forceinline__ bool cell_of(float x, double voxel, int &cell, long long &q) {
     const double t = (double)x / voxel;
@@ -129,7 +98,8 @@ __device__ __forceinline__ bool cell_of(float x, double voxel, int &cell, long l
     return true;
 }
 
-// One vertex per thread: claim the slot of its cell, lower the slot's leader to this row, add to the slot's sums.
+// One vertex per thread: claim the slot of its cell, lower the slot's leader to this row, add to the slot's sums.  Thread 0
+// leaves the bits of voxel_size in the header, which the fill has just zeroed.
 // Keyframe meshes arrive in pixel order, so neighbouring lanes usually share a cell.  A run of adjacent lanes with the
 // same cell adds up inside the wave first (a segmented shuffle sum: q < 2^24 + 1 and a colour < 2^8 over 64 lanes fit 32
 // bits), and its first lane - the run's smallest row - probes, claims and adds once for all of them: eight atomics per run
@@ -150,6 +120,7 @@ __global__ void __launch_bounds__(kThreads) k_sv_insert(const float *__restrict_
 #pragma unroll
         for (int k = 0; k < 3; ++k) in = cell_of(vertices[3 * v + k], voxel, cell[k], q[k]) && in;
     }
+    if (v == 0) hdr[kVoxel] = __float_as_int(voxel_f);
     const unsigned long long out = __ballot(v < V && !in);
     if (out && lane == 0) atomicAdd(hdr + kOutOfRange, (int)__popcll(out));      // V < 2^31: no overflow
     if (!__ballot(in)) {                                                        // wave-uniform: nothing to insert
@@ -157,8 +128,7 @@ __global__ void __launch_bounds__(kThreads) k_sv_insert(const float *__restrict_
         return;
     }
     // every lane of the wave stays to the last shuffle
-    const unsigned long long key = !in ? kEmptyKey : ((unsigned long long)(cell[0] + 1048576) << 42) |
-                                   ((unsigned long long)(cell[1] + 1048576) << 21) | (unsigned long long)(cell[2] + 1048576);
+    const unsigned long long key = !in ? kEmptyKey : cell_key(cell[0] + kCellBias, cell[1] + kCellBias, cell[2] + kCellBias);
     unsigned x[5] = {(unsigned)q[0], (unsigned)q[1], (unsigned)q[2], 0u, 0u};    // q.x, q.y, q.z, red | green << 16, blue
     if (in) {
         x[3] = (unsigned)colors[3 * v] | ((unsigned)colors[3 * v + 1] << 16);
@@ -180,15 +150,9 @@ __global__ void __launch_bounds__(kThreads) k_sv_insert(const float *__restrict_
         }
     }
     unsigned s32 = 0u;
-    if (in && head) {
-        const unsigned long long mask = (unsigned long long)(SV - 1);
-        unsigned long long s = mix64(key) & mask;
-        for (int64_t probe = 0; probe < SV; ++probe) {                          // the table is at most half full: this ends
-            unsigned long long cur = keys[s];
-            if (cur == kEmptyKey) cur = atomicCAS(&keys[s], kEmptyKey, key);
-            if (cur == kEmptyKey || cur == key) break;
-            s = (s + 1) & mask;
-        }
+    bool claimed;
+    const uint32_t s = in && head ? key_claim(keys, SV, key, claimed) : kNoSlot;
+    if (s != kNoSlot) {                                                         // always, for a lane that looked
         atomicMin(lead + s, (int32_t)v);                                        // the run's smallest row
         atomicAdd(cnt + s, after + 1);
         const unsigned c[3] = {x[3] & 0xffffu, x[3] >> 16, x[4]};
@@ -197,7 +161,7 @@ __global__ void __launch_bounds__(kThreads) k_sv_insert(const float *__restrict_
             atomicAdd(sums + (int64_t)k * SV + s, (unsigned long long)x[k]);
             atomicAdd(sums + (int64_t)(3 + k) * SV + s, (unsigned long long)c[k]);
         }
-        s32 = (unsigned)s;
+        s32 = s;
     }
     const unsigned long long upto = heads & (~0ull >> (63 - lane));             // heads at or below my lane: never empty (lane 0)
     s32 = __shfl(s32, 63 - __clzll((long long)upto), 64);                        // the slot my run's first lane found
@@ -222,13 +186,6 @@ __global__ void __launch_bounds__(kThreads) k_sv_leaders(int64_t V, const uint32
     if (threadIdx.x == 0) cntV[blockIdx.x] = total;
 }
 
-// The rows of face f: 0 = valid, 1 = a row outside [0, V).
-__device__ __forceinline__ bool face_rows(const int32_t *__restrict__ faces, int64_t f, int64_t V, int32_t (&r)[3]) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i) r[i] = faces[3 * f + i];
-    return r[0] >= 0 && r[0] < V && r[1] >= 0 && r[1] < V && r[2] >= 0 && r[2] < V;
-}
-
 // The key of a face with valid rows r: the leaders of its clusters, rotated so the smallest comes first.  false when
 // the face is dropped: a row out of range, or two rows in one cluster.
 __device__ __forceinline__ bool face_key(const int32_t (&r)[3], const int32_t *__restrict__ vlead, int32_t (&k)[3]) {
@@ -246,9 +203,8 @@ __global__ void __launch_bounds__(kThreads) k_sv_faces(const int32_t *__restrict
                                                         int64_t SF, uint32_t *__restrict__ fslot, int32_t *__restrict__ hdr) {
     const int64_t f = row_of();
     int32_t r[3], k[3];
-    const bool in = f < F, ok = in && face_rows(faces, f, V, r);
-    const unsigned long long bad = __ballot(in && !ok);
-    if (bad && (threadIdx.x & 63) == 0) atomicAdd(hdr + kInvalid, (int)__popcll(bad));     // F < 2^31: no overflow
+    const bool in = f < F, ok = in && load_face(faces, f, V, r);
+    count_invalid(in, ok, hdr + kInvalid);
     if (!in) return;
     if (!ok || !face_key(r, vlead, k)) {
         fslot[f] = 0u;                                                          // no slot ever holds a dropped face's row
@@ -261,7 +217,7 @@ __global__ void __launch_bounds__(kThreads) k_sv_faces(const int32_t *__restrict
         if (cur == kNoRow) cur = atomicCAS(ftab + s, kNoRow, (int32_t)f);
         if (cur == kNoRow) break;                                               // claimed
         int32_t r2[3], k2[3];
-        face_rows(faces, cur, V, r2);                                           // an occupant is a face that has a key
+        load_face(faces, cur, V, r2);                                           // an occupant is a face that has a key
         face_key(r2, vlead, k2);
         if (k2[0] == k[0] && k2[1] == k[1] && k2[2] == k[2]) {
             atomicMin(ftab + s, (int32_t)f);
@@ -312,11 +268,12 @@ __global__ void __launch_bounds__(kThreads) k_sv_vertices(const float *__restric
         return;
     }
     const double voxel = (double)__int_as_float(hdr[kVoxel]);
-    const unsigned long long key = keys[s];
+    int b[3];
+    cell_unkey(keys[s], b[0], b[1], b[2]);
     const double den = (double)n * kQ;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        const int cell = (int)((key >> (21 * (2 - k))) & 0x1fffffull) - 1048576;
+        const int cell = b[k] - kCellBias;
         const double mean = (double)(long long)sums[(int64_t)k * SV + s] / den;
         vertices_out[3 * o + k] = (float)(((double)cell + mean) * voxel);
         const unsigned long long C = sums[(int64_t)(3 + k) * SV + s];
@@ -345,15 +302,12 @@ __global__ void __launch_bounds__(kThreads) k_sv_scatter_faces(const int32_t *__
     const int64_t o = (int64_t)offs[blockIdx.x] + block_prefix(on ? 1u : 0u, total);
     if (!on || o >= F2) return;                                                 // o < F2 always holds for a ws from the same inputs
     int32_t r[3], k[3];
-    face_rows(faces, f, V, r);
+    load_face(faces, f, V, r);
     face_key(r, vlead, k);
 #pragma unroll
     for (int i = 0; i < 3; ++i) faces_out[3 * o + i] = vrow[k[i]];
     if (face_rows_out) face_rows_out[o] = f;
 }
-
-inline bool ws_ok(const void *ws) { return ws && ((uintptr_t)ws & 15) == 0; }
-inline bool aligned(const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 
 }  // namespace
 
@@ -374,10 +328,10 @@ int m3_mesh_simplify_count(const float *vertices, const uint8_t *colors, const i
     M3_REQUIRE(voxel_size > 0.f && voxel_size < INFINITY);                                           // NaN fails
     hipStream_t st = (hipStream_t)stream;
     const SvPtr p = sv_ptr(ws, m);
-    const dim3 gv = grid_of(m.ntileV), gf = grid_of(m.ntileF), block(kThreads);
+    const dim3 gv = grid_of(V), gf = grid_of(F), block(kThreads);
     const int64_t a = (m.lead - m.keys) / 16, b = (m.cnt - m.keys) / 16, n = (m.bytes - m.keys) / 16;
-    hipLaunchKernelGGL(k_sv_clear, dim3((unsigned)((n + kThreads - 1) / kThreads)), block, 0, st, (int4 *)p.keys, a, b, n,
-                       (int4 *)p.hdr, voxel_size);
+    hipLaunchKernelGGL(k_fill3, grid_of(n), block, 0, st, (int4 *)p.keys, a, b, n, -1, kNoRow, 0, (int4 *)p.hdr,
+                       kSvHdrWords / 4);
     // V = 0 or F = 0: no thread has a row.  The launches are kept so that their number is fixed.
     hipLaunchKernelGGL(k_sv_insert, gv, block, 0, st, vertices, colors, V, voxel_size, p.keys, p.lead, p.cnt, p.sums, m.SV,
                        p.vslot, p.vlead, p.hdr);
@@ -401,10 +355,10 @@ int m3_mesh_simplify_scatter(const float *vertices, const uint8_t *colors, const
     hipStream_t st = (hipStream_t)stream;
     const SvPtr p = sv_ptr(ws, m);
     const dim3 block(kThreads);
-    hipLaunchKernelGGL(k_sv_vertices, grid_of(m.ntileV), block, 0, st, vertices, colors, V, p.hdr, p.vslot, p.vlead, p.keys,
+    hipLaunchKernelGGL(k_sv_vertices, grid_of(V), block, 0, st, vertices, colors, V, p.hdr, p.vslot, p.vlead, p.keys,
                        p.cnt, p.sums, m.SV, p.offV, V2, p.vrow, vertices_out, colors_out);
-    const int64_t tiles = cluster_of_out && m.ntileV > m.ntileF ? m.ntileV : m.ntileF;
-    hipLaunchKernelGGL(k_sv_scatter_faces, grid_of(tiles), block, 0, st, faces, V, F, p.vlead, p.vrow, p.fslot, p.ftab, p.offF,
+    const int64_t rows = cluster_of_out && V > F ? V : F;                       // cluster_of takes a thread per vertex
+    hipLaunchKernelGGL(k_sv_scatter_faces, grid_of(rows), block, 0, st, faces, V, F, p.vlead, p.vrow, p.fslot, p.ftab, p.offF,
                        m.ntileF, F2, faces_out, face_rows_out, cluster_of_out);
     M3_CHECK_LAUNCH("m3_mesh_simplify_scatter");
     return M3_OK;

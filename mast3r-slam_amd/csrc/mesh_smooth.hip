@@ -6,10 +6,10 @@
 //         tile offset + rank -> one thread per face again (the corners that claimed a slot write each end into the
 //         other's row at a cursor, with the boundary bit; the header counts) -> sort every row and set its vertex's
 //         boundary flag.
-// Seven launches whatever the mesh holds.  The only atomics are integer ones whose results commute: CAS to claim a
-// slot, add for the counts, the degrees and the cursors.  Which slot an edge lands in and where in its row a neighbour
-// first lands depend on the arrival order; the sort removes the second and nothing that is output reads the first.
-// No thread waits for another.
+// Seven launches whatever the mesh holds.  The edges live in the key table of table_dev.h, which also has the fill and the
+// degrees -> row starts sequence.  The only atomics are integer ones whose results commute: the table's claim, add for
+// the counts, the degrees and the cursors.  Where in its row a neighbour first lands depends on the arrival order; the
+// sort removes that.  No thread waits for another.
 //
 // The cursor of a row is its start itself: the degrees are counted into off[1 + v], the scan turns them into row
 // starts, and the fill's atomicAdd on off[1 + v] hands out the positions and leaves the row's END there - the start of
@@ -35,8 +35,7 @@
 // [3] invalid faces, [8] E (the total of the edge-list scan); the others are 0.
 //
 // Compiled with -ffp-contract=off: every float64 operation of the rule is rounded on its own.
-#include "common.h"
-#include "compact_dev.h"
+#include "table_dev.h"
 #pragma clang fp contract(off)
 
 namespace {
@@ -46,8 +45,6 @@ constexpr int kSmHdrWords = 16;
 constexpr int kTwoE = 0, kBoundary = 1, kNonManifold = 2, kInvalid = 3, kEdges = 8;
 constexpr int64_t kMaxV = 0x7fffffff;
 constexpr int64_t kMaxF = 0x7fffffff / 6;     // the CSR holds at most 6 F entries, indexed in int32
-constexpr unsigned long long kEmptyKey = ~0ull;   // a packed edge key uses 62 bits
-constexpr uint32_t kNoSlot = ~0u;             // a face corner that claimed no slot (S <= 2^31)
 constexpr int kShortRow = 32;                 // rows up to this length are sorted by their own thread
 constexpr int32_t kRowMask = 0x7fffffff;      // a raw entry: the neighbour, and bit 31 = on a boundary edge
 constexpr unsigned kFinite = 1u, kPinned = 2u;
@@ -57,18 +54,15 @@ struct SmWs {
     int64_t tile, off, cnt, keys, bnd, fslot, raw, nbr, posA, posB, bytes;                     // byte offsets into ws
 };
 
-inline int64_t pad16(int64_t b) { return (b + 15) / 16 * 16; }
-
 inline bool sm_layout(int64_t V, int64_t F, SmWs &m) {
     if (V < 0 || F < 0 || V > kMaxV || F > kMaxF) return false;
     m.ntile = (V + 1 + kThreads - 1) / kThreads;         // tiles of the V + 1 row starts: at least one
     m.cap = 6 * F;
-    m.S = 1024;
-    while (m.S < m.cap) m.S *= 2;                        // 3 F edges at most: never more than half full
+    m.S = table_slots(m.cap);                            // 3 F edges at most
     m.tile = kSmHdrWords * 4;
     m.off = m.tile + pad16(4 * m.ntile);
     m.cnt = m.off + pad16(4 * (V + 2));
-    m.keys = m.cnt + 4 * m.S;                            // the clear kernel fills [0, keys) with 0 and [keys, bnd) with ff
+    m.keys = m.cnt + 4 * m.S;                            // the fill: [0, keys) 0 and [keys, bnd) ff
     m.bnd = m.keys + 8 * m.S;
     m.fslot = m.bnd + pad16(V);
     m.raw = m.fslot + pad16(12 * F);
@@ -109,28 +103,9 @@ inline SmPtr sm_ptr(void *ws, const SmWs &m) {
     return q;
 }
 
-inline dim3 grid_of(int64_t rows) { return dim3((unsigned)(rows ? (rows + kThreads - 1) / kThreads : 1)); }
-
-__device__ __forceinline__ int64_t row_of() { return (int64_t)blockIdx.x * kThreads + threadIdx.x; }
-
-__device__ __forceinline__ unsigned long long mix64(unsigned long long x) {
-    x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ull;
-    x ^= x >> 27; x *= 0x94d049bb133111ebull;
-    return x ^ (x >> 31);
-}
-
 __device__ __forceinline__ unsigned long long edge_key(int32_t a, int32_t b) {
-    const int32_t lo = a < b ? a : b, hi = a < b ? b : a;
+    const int32_t lo = a < b ? a : b, hi = a < b ? b : a;                        // 62 bits
     return ((unsigned long long)(uint32_t)lo << 31) | (unsigned long long)(uint32_t)hi;
-}
-
-// Header, degrees, counts and keys are cleared by a kernel, 16 bytes per thread: a captured memset left its words
-// uncleared on replay.  int4 [0, a) = 0, [a, n) = ff ..
-__global__ void __launch_bounds__(kThreads) k_sm_clear(int4 *__restrict__ ws, int64_t a, int64_t n) {
-    const int64_t i = row_of();
-    if (i >= n) return;
-    const int w = i < a ? 0 : -1;
-    ws[i] = int4{w, w, w, w};
 }
 
 // One face per thread: each of its three pairs claims or finds the slot of its key and adds 1 to the slot's count; the
@@ -142,84 +117,24 @@ __global__ void __launch_bounds__(kThreads) k_sm_faces(const int32_t *__restrict
                                                         int32_t *__restrict__ hdr) {
     const int64_t f = row_of();
     int32_t r[3] = {0, 0, 0};
-    const bool in = f < F;
-    bool ok = in;
-    if (in) {
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            r[i] = faces[3 * f + i];
-            ok = ok && r[i] >= 0 && r[i] < V;
-        }
-    }
-    const unsigned long long bad = __ballot(in && !ok);
-    if (bad && (threadIdx.x & 63) == 0) atomicAdd(hdr + kInvalid, (int)__popcll(bad));     // F < 2^31: no overflow
+    const bool in = f < F, ok = in && load_face(faces, f, V, r);
+    count_invalid(in, ok, hdr + kInvalid);
     if (!in) return;
-    const unsigned long long mask = (unsigned long long)(S - 1);
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
         const int32_t a = r[i], b = r[i == 2 ? 0 : i + 1];
         fslot[3 * f + i] = kNoSlot;
         if (!ok || a == b) continue;                                            // no edge
-        const unsigned long long key = edge_key(a, b);
-        unsigned long long s = mix64(key) & mask;
-        bool claimed = false, found = false;
-        for (int64_t probe = 0; probe < S; ++probe) {                           // the table is at most half full: this ends
-            unsigned long long cur = __hip_atomic_load(keys + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (cur == kEmptyKey) {
-                cur = atomicCAS(keys + s, kEmptyKey, key);
-                claimed = cur == kEmptyKey;
-            }
-            found = claimed || cur == key;
-            if (found) break;
-            s = (s + 1) & mask;
-        }
-        if (!found) continue;                                                   // never: 3 F pairs, at least 6 F slots
+        bool claimed;
+        const uint32_t s = key_claim(keys, S, edge_key(a, b), claimed);
+        if (s == kNoSlot) continue;                                             // never: 3 F pairs, at least 6 F slots
         atomicAdd(cnt + s, 1);
         if (claimed) {
             atomicAdd(deg + a, 1);
             atomicAdd(deg + b, 1);
-            fslot[3 * f + i] = (uint32_t)s;
+            fslot[3 * f + i] = s;
         }
     }
-}
-
-// Exclusive prefix of x over the workgroup in thread order, and the workgroup's total.
-__device__ __forceinline__ int block_exclusive(int x, int &total) {
-    __shared__ int wtot[kThreads / M3_WAVE];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int incl = x;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += t;
-    }
-    if (lane == 63) wtot[w] = incl;
-    __syncthreads();
-    int base = 0;
-    total = 0;
-#pragma unroll
-    for (int i = 0; i < kThreads / M3_WAVE; ++i) {
-        base += i < w ? wtot[i] : 0;
-        total += wtot[i];
-    }
-    return base + incl - x;
-}
-
-// The degrees of a tile of 256 rows, added up.  deg has n = V + 1 entries; the last is 0 and becomes 2 E.
-__global__ void __launch_bounds__(kThreads) k_sm_tile_degrees(const int32_t *__restrict__ deg, int64_t n,
-                                                               int32_t *__restrict__ tile) {
-    const int64_t i = row_of();
-    int total;
-    block_exclusive(i < n ? deg[i] : 0, total);
-    if (threadIdx.x == 0) tile[blockIdx.x] = total;
-}
-
-// Degrees to row starts, in place: the tile's offset + the rank inside the tile.
-__global__ void __launch_bounds__(kThreads) k_sm_starts(int32_t *__restrict__ deg, int64_t n, const int32_t *__restrict__ tile) {
-    const int64_t i = row_of();
-    int total;
-    const int start = tile[blockIdx.x] + block_exclusive(i < n ? deg[i] : 0, total);
-    if (i < n) deg[i] = start;
 }
 
 __device__ __forceinline__ int wave_sum(int x) {
@@ -361,22 +276,14 @@ __global__ void __launch_bounds__(kThreads) k_sm_scatter_edges(const int32_t *__
     const int n = upper_part(nbr, b, e, v, first);
     int total;
     int64_t o = (int64_t)tile[blockIdx.x] + block_exclusive(n, total);
-    const unsigned long long mask = (unsigned long long)(S - 1);
     for (int64_t k = first; k < e; ++k, ++o) {
         if (o >= E) return;                                                     // never, for a ws from the same faces
         const int32_t hi = nbr[k];
         const unsigned long long key = edge_key((int32_t)v, hi);
-        unsigned long long s = mix64(key) & mask;
-        int32_t c = 0;
-        for (int64_t probe = 0; probe < S; ++probe) {
-            const unsigned long long cur = keys[s];
-            if (cur == key) { c = cnt[s]; break; }
-            if (cur == kEmptyKey) break;
-            s = (s + 1) & mask;
-        }
+        const uint32_t s = key_find(keys, S, key, key_home(key, S));
         edges_out[2 * o] = (int32_t)v;
         edges_out[2 * o + 1] = hi;
-        edge_faces_out[o] = c;
+        edge_faces_out[o] = s == kNoSlot ? 0 : cnt[s];
     }
 }
 
@@ -465,9 +372,6 @@ __global__ void __launch_bounds__(kThreads) k_sm_copy(const float *__restrict__ 
     if (i < n) dst[i] = src[i];
 }
 
-inline bool ws_ok(const void *ws) { return ws && ((uintptr_t)ws & 15) == 0; }
-inline bool aligned(const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-
 }  // namespace
 
 extern "C" {
@@ -486,14 +390,11 @@ int m3_mesh_topology_build(const int32_t *faces, int64_t V, int64_t F, void *ws,
     hipStream_t st = (hipStream_t)stream;
     const SmPtr p = sm_ptr(ws, m);
     const dim3 block(kThreads);
-    const dim3 tiles((unsigned)m.ntile);
     int32_t *deg = p.off + 1;                                                   // degree, then start, then end of row v
-    hipLaunchKernelGGL(k_sm_clear, grid_of(m.bnd / 16), block, 0, st, (int4 *)ws, m.keys / 16, m.bnd / 16);
+    launch_fill(st, ws, m.keys / 16, m.bnd / 16, 0, -1);
     // V = 0 or F = 0: no thread has a row.  The launches are kept so that their number is fixed.
     hipLaunchKernelGGL(k_sm_faces, grid_of(F), block, 0, st, faces, V, F, p.keys, p.cnt, m.S, deg, p.fslot, p.hdr);
-    hipLaunchKernelGGL(k_sm_tile_degrees, tiles, block, 0, st, deg, V + 1, p.tile);
-    launch_scan(st, p.hdr + kTwoE, ScanJob{p.tile, m.ntile});                   // 2 E to word 0
-    hipLaunchKernelGGL(k_sm_starts, tiles, block, 0, st, deg, V + 1, p.tile);
+    launch_row_starts(st, deg, V + 1, p.tile, m.ntile, p.hdr + kTwoE);          // deg[V] is 0 and becomes 2 E, as word 0
     hipLaunchKernelGGL(k_sm_fill, grid_of(F), block, 0, st, faces, V, F, p.fslot, p.cnt, m.S, deg, p.raw, m.cap, p.hdr);
     hipLaunchKernelGGL(k_sm_sort, grid_of(V), block, 0, st, p.off, V, m.cap, p.raw, p.nbr, p.bnd);
     M3_CHECK_LAUNCH("m3_mesh_topology_build");

@@ -44,7 +44,8 @@ import numpy as np
 import torch
 
 from . import _ffi
-from .export import _check_workspace, _with_pointmap
+from ._mesh_args import take_workspace
+from .export import _with_pointmap
 
 __all__ = ["cloud_neighbors", "cloud_normals", "source_viewpoints", "remove_radius_outliers", "CloudNeighbors",
            "workspace_bytes", "cloud_knn", "KnnResult", "remove_statistical_outliers", "cloud_normals_knn", "MAX_K"]
@@ -94,13 +95,7 @@ def _points(points, name: str = "points") -> None:
 
 
 def _workspace(workspace: Optional[torch.Tensor], m: int, dev) -> torch.Tensor:
-    ws_bytes = workspace_bytes(m)
-    if workspace is None:
-        workspace = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
-    _check_workspace(workspace, ws_bytes)
-    if workspace.device != dev:
-        raise ValueError(f"the cloud lives on {dev}, the workspace on {workspace.device}")
-    return workspace
+    return take_workspace(workspace, workspace_bytes(m), dev, owner="the cloud lives")
 
 
 def _too_small(radius: float, n: int) -> ValueError:

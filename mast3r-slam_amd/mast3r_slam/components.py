@@ -30,7 +30,7 @@ import numpy as np
 import torch
 
 from . import _ffi
-from .export import _check_workspace, _empty_mesh
+from ._mesh_args import check_faces, check_mesh, empty_mesh_with_index, raise_invalid_faces, take_workspace, unpack_mesh
 
 __all__ = ["mesh_components", "filter_components", "ComponentsInfo", "workspace_bytes"]
 
@@ -50,30 +50,14 @@ def workspace_bytes(n_vertices: int, n_faces: int) -> int:
     return b
 
 
-def _faces(faces) -> torch.Tensor:
-    if not isinstance(faces, torch.Tensor) or faces.dtype != torch.int32 or faces.dim() != 2 or faces.shape[1] != 3:
-        got = f"{faces.dtype} {tuple(faces.shape)}" if isinstance(faces, torch.Tensor) else type(faces).__name__
-        raise ValueError(f"faces must be a torch.int32 [n,3] tensor, got {got}")
-    return _ffi.check(faces, torch.int32, "faces")
-
-
 def _label(faces: torch.Tensor, v: int, workspace: Optional[torch.Tensor], labels, faces_of) -> torch.Tensor:
     """Queue the labelling of `faces` over v vertex rows; returns the workspace."""
     f = int(faces.shape[0])
     ws_bytes = workspace_bytes(v, f)
-    if workspace is None:
-        workspace = torch.empty((ws_bytes,), dtype=torch.uint8, device=faces.device)
-    _check_workspace(workspace, ws_bytes)
-    if workspace.device != faces.device:
-        raise ValueError(f"the mesh lives on {faces.device}, the workspace on {workspace.device}")
+    workspace = take_workspace(workspace, ws_bytes, faces.device)
     _ffi.call("m3_mesh_components_label", _ffi.ptr(faces) if f else None, v, f, _ffi.ptr(workspace), ws_bytes, _ffi.ptr(labels),
               _ffi.ptr(faces_of), _ffi.stream_ptr())
     return workspace
-
-
-def _check_invalid(invalid: int, v: int) -> None:
-    if invalid:
-        raise ValueError(f"{invalid} faces name a vertex row outside [0, {v})")
 
 
 def mesh_components(faces, n_vertices: int, workspace: Optional[torch.Tensor] = None):
@@ -86,13 +70,13 @@ def mesh_components(faces, n_vertices: int, workspace: Optional[torch.Tensor] = 
     v = int(n_vertices)
     if v != n_vertices or v < 0 or v > MAX_ROWS:
         raise ValueError(f"n_vertices must be an integer in 0 ... 2^31 - 1, got {n_vertices}")
-    faces = _faces(faces)
+    faces = check_faces(faces)
     dev = faces.device
     labels = torch.empty((v,), dtype=torch.int32, device=dev)
     faces_of = torch.empty((v,), dtype=torch.int32, device=dev)
     ws = _label(faces, v, workspace, labels, faces_of)
     hdr = ws[:4 * _HDR_WORDS].view(torch.int32).tolist()                  # the one synchronisation
-    _check_invalid(hdr[7], v)
+    raise_invalid_faces(hdr[7], v)
     return labels, faces_of, ComponentsInfo(hdr[4], hdr[5], hdr[6])
 
 
@@ -109,38 +93,26 @@ def filter_components(vertices, colors=None, faces=None, min_faces: int = 1, min
     An empty mesh in, or a filter that keeps nothing, gives the empty mesh.  workspace as for mesh_components.  ValueError
     when a face names a row outside [0, V), for a min_fraction outside [0, 1] or a min_faces that is no integer;
     RuntimeError for CPU tensors."""
-    if isinstance(vertices, (tuple, list)):
-        if len(vertices) < 3 or colors is not None or faces is not None:
-            raise ValueError("a mesh is (vertices, colors, faces[, index]), passed whole or unpacked")
-        vertices, colors, faces = vertices[:3]
+    vertices, colors, faces = unpack_mesh(vertices, colors, faces)
     if isinstance(min_faces, bool) or int(min_faces) != min_faces or abs(int(min_faces)) > MAX_ROWS:
         raise ValueError(f"min_faces must be an integer, got {min_faces}")
     fraction = float(np.float32(min_fraction))
     if not 0.0 <= fraction <= 1.0 or math.isnan(fraction):
         raise ValueError(f"min_fraction must lie in [0, 1], got {min_fraction}")
-    for t, dt, name in ((vertices, torch.float32, "vertices"), (colors, torch.uint8, "colors")):
-        if not isinstance(t, torch.Tensor) or t.dtype != dt or t.dim() != 2 or t.shape[1] != 3:
-            got = f"{t.dtype} {tuple(t.shape)}" if isinstance(t, torch.Tensor) else type(t).__name__
-            raise ValueError(f"{name} must be a {dt} [n,3] tensor, got {got}")
-    if colors.shape[0] != vertices.shape[0]:
-        raise ValueError(f"vertices has {vertices.shape[0]} rows, colors {colors.shape[0]}")
-    faces = _faces(faces)
-    vertices, colors = _ffi.check(vertices, torch.float32, "vertices"), _ffi.check(colors, torch.uint8, "colors")
+    vertices, colors, faces = check_mesh(vertices, colors, faces, rows_first=True)
     dev = faces.device
-    if vertices.device != dev or colors.device != dev:
-        raise ValueError(f"faces live on {dev}, vertices on {vertices.device}, colors on {colors.device}")
     v, f = int(vertices.shape[0]), int(faces.shape[0])
     if v == 0 and f == 0:
-        return _empty(dev, return_index)
+        return empty_mesh_with_index(dev, return_index)
     ws = _label(faces, v, workspace, None, None)
     st = _ffi.stream_ptr()
     _ffi.call("m3_mesh_components_count", _ffi.ptr(ws), v, f, _ffi.ptr(faces) if f else None, int(min_faces), fraction,
               1 if largest_only else 0, st)
     hdr = ws[:4 * _HDR_WORDS].view(torch.int32).tolist()                  # the one synchronisation: V2, F2 and the label words
-    _check_invalid(hdr[7], v)
+    raise_invalid_faces(hdr[7], v)
     v2, f2 = hdr[0], hdr[1]
     if f2 == 0:
-        return _empty(dev, return_index)
+        return empty_mesh_with_index(dev, return_index)
     out_v = torch.empty((v2, 3), dtype=torch.float32, device=dev)
     out_c = torch.empty((v2, 3), dtype=torch.uint8, device=dev)
     out_f = torch.empty((f2, 3), dtype=torch.int32, device=dev)
@@ -149,11 +121,4 @@ def filter_components(vertices, colors=None, faces=None, min_faces: int = 1, min
     _ffi.call("m3_mesh_components_scatter", _ffi.ptr(vertices), _ffi.ptr(colors), _ffi.ptr(faces), v, f, _ffi.ptr(ws), v2, f2,
               _ffi.ptr(out_v), _ffi.ptr(out_c), _ffi.ptr(out_f), _ffi.ptr(rows_v), _ffi.ptr(rows_f), st)
     return (out_v, out_c, out_f, rows_v, rows_f) if return_index else (out_v, out_c, out_f)
-
-
-def _empty(device, return_index: bool):
-    mesh = _empty_mesh(device, False)
-    if not return_index:
-        return mesh
-    return mesh + (torch.empty((0,), dtype=torch.int64, device=device), torch.empty((0,), dtype=torch.int64, device=device))
 

@@ -25,7 +25,7 @@ import numpy as np
 import torch
 
 from . import _ffi
-from .export import _check_workspace
+from ._mesh_args import check_rows3 as _rows3, take_workspace, unpack_mesh, whole_or_unpacked_error
 
 __all__ = ["vertex_normals", "shade_vertices", "workspace_bytes"]
 
@@ -38,16 +38,6 @@ def workspace_bytes(n_vertices: int) -> int:
     if b <= 0:
         raise ValueError(f"unsupported mesh of {n_vertices} vertices (0 ... 2^31 - 1)")
     return b
-
-
-def _rows3(*named):
-    """The (tensor, dtype, name) triples as contiguous device tensors: ValueError unless each is a dtype [n,3] tensor (all
-    of them are looked at before the first device check), RuntimeError for a CPU tensor."""
-    for t, dtype, name in named:
-        if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.dim() != 2 or t.shape[1] != 3:
-            got = f"{t.dtype} {tuple(t.shape)}" if isinstance(t, torch.Tensor) else type(t).__name__
-            raise ValueError(f"{name} must be a {dtype} [n,3] tensor, got {got}")
-    return [_ffi.check(t, dtype, name) for t, dtype, name in named]
 
 
 def _out(out, dtype, v: int, dev, name: str) -> torch.Tensor:
@@ -72,12 +62,10 @@ def vertex_normals(vertices, faces=None, out: Optional[torch.Tensor] = None, wor
     float32 [V,3] device tensor to write into; `workspace`: a 16-byte aligned uint8 device tensor of workspace_bytes(V),
     whose contents are ignored.  F = 0 gives zeros, V = 0 a [0,3] tensor.  RuntimeError for CPU tensors."""
     if isinstance(vertices, (tuple, list)):
-        if len(vertices) < 3 or faces is not None:
-            raise ValueError("a mesh is (vertices, colors, faces[, index]), passed whole or unpacked")
-        vertices, faces = vertices[0], vertices[2]
+        vertices, _, faces = unpack_mesh(vertices, None, faces)
     elif isinstance(faces, torch.Tensor) and faces.dtype == torch.uint8:    # vertex_normals(*mesh): colors, then faces
         if not isinstance(out, torch.Tensor) or out.dtype != torch.int32:
-            raise ValueError("a mesh is (vertices, colors, faces[, index]), passed whole or unpacked")
+            raise whole_or_unpacked_error()
         faces, out = out, None
         if isinstance(workspace, torch.Tensor) and workspace.dtype == torch.int64:         # the index of a 4-tuple
             workspace = None
@@ -88,11 +76,7 @@ def vertex_normals(vertices, faces=None, out: Optional[torch.Tensor] = None, wor
     v, f = int(vertices.shape[0]), int(faces.shape[0])
     ws_bytes = workspace_bytes(v)
     out = _out(out, torch.float32, v, dev, "out")
-    if workspace is None:
-        workspace = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
-    _check_workspace(workspace, ws_bytes)
-    if workspace.device != dev:
-        raise ValueError(f"the mesh lives on {dev}, the workspace on {workspace.device}")
+    workspace = take_workspace(workspace, ws_bytes, dev)
     _ffi.call("m3_mesh_normals", _ffi.ptr(vertices) if v else None, _ffi.ptr(faces) if f else None, v, f, _ffi.ptr(workspace),
               ws_bytes, _ffi.ptr(out) if v else None, _ffi.stream_ptr())
     return out

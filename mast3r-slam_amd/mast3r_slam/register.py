@@ -37,8 +37,8 @@ import numpy as np
 import torch
 
 from . import _ffi
+from ._mesh_args import take_workspace
 from .cloud import _points, _radius
-from .export import _check_workspace
 
 __all__ = ["register_clouds", "icp_sums", "Registration", "IcpSums", "registration_workspace_bytes", "read_registration",
            "STATUS", "MAX_ITERATIONS"]
@@ -137,13 +137,7 @@ def _on_device(source, target, target_normals):
 
 
 def _workspace(workspace, ns, nt, iterations, dev):
-    need = registration_workspace_bytes(ns, nt, iterations)
-    if workspace is None:
-        workspace = torch.empty((need,), dtype=torch.uint8, device=dev)
-    _check_workspace(workspace, need)
-    if workspace.device != dev:
-        raise ValueError(f"the clouds live on {dev}, the workspace on {workspace.device}")
-    return workspace
+    return take_workspace(workspace, registration_workspace_bytes(ns, nt, iterations), dev, owner="the clouds live")
 
 
 def _state_offset(nt: int) -> int:

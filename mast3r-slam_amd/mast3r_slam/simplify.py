@@ -32,7 +32,7 @@ import numpy as np
 import torch
 
 from . import _ffi
-from .export import _check_workspace, _empty_mesh
+from ._mesh_args import check_mesh, empty_mesh_with_index, raise_invalid_faces, take_workspace, unpack_mesh
 
 __all__ = ["simplify_mesh", "simplify_counts", "SimplifyInfo", "workspace_bytes"]
 
@@ -64,38 +64,18 @@ def _voxel(voxel_size) -> float:
 
 def _mesh(vertices, colors, faces):
     """The three arrays of a mesh passed whole or unpacked, checked: device tensors of the right dtype and shape."""
-    if isinstance(vertices, (tuple, list)):
-        if len(vertices) < 3 or colors is not None or faces is not None:
-            raise ValueError("a mesh is (vertices, colors, faces[, index]), passed whole or unpacked")
-        vertices, colors, faces = vertices[:3]
-    for t, dt, name in ((vertices, torch.float32, "vertices"), (colors, torch.uint8, "colors"), (faces, torch.int32, "faces")):
-        if not isinstance(t, torch.Tensor) or t.dtype != dt or t.dim() != 2 or t.shape[1] != 3:
-            got = f"{t.dtype} {tuple(t.shape)}" if isinstance(t, torch.Tensor) else type(t).__name__
-            raise ValueError(f"{name} must be a {dt} [n,3] tensor, got {got}")
-    if colors.shape[0] != vertices.shape[0]:
-        raise ValueError(f"vertices has {vertices.shape[0]} rows, colors {colors.shape[0]}")
-    faces = _ffi.check(faces, torch.int32, "faces")
-    vertices, colors = _ffi.check(vertices, torch.float32, "vertices"), _ffi.check(colors, torch.uint8, "colors")
-    dev = faces.device
-    if vertices.device != dev or colors.device != dev:
-        raise ValueError(f"faces live on {dev}, vertices on {vertices.device}, colors on {colors.device}")
-    return vertices, colors, faces
+    return check_mesh(*unpack_mesh(vertices, colors, faces))
 
 
 def _count(vertices, colors, faces, voxel: float, workspace: Optional[torch.Tensor]):
     """Queue the count stage and read the header: (workspace, V2, F2, out_of_range)."""
     v, f = int(vertices.shape[0]), int(faces.shape[0])
     ws_bytes = workspace_bytes(v, f)
-    if workspace is None:
-        workspace = torch.empty((ws_bytes,), dtype=torch.uint8, device=faces.device)
-    _check_workspace(workspace, ws_bytes)
-    if workspace.device != faces.device:
-        raise ValueError(f"the mesh lives on {faces.device}, the workspace on {workspace.device}")
+    workspace = take_workspace(workspace, ws_bytes, faces.device)
     _ffi.call("m3_mesh_simplify_count", _ffi.ptr(vertices) if v else None, _ffi.ptr(colors) if v else None,
               _ffi.ptr(faces) if f else None, v, f, voxel, _ffi.ptr(workspace), ws_bytes, _ffi.stream_ptr())
     hdr = workspace[:4 * _HDR_WORDS].view(torch.int32).tolist()          # the one synchronisation
-    if hdr[3]:
-        raise ValueError(f"{hdr[3]} faces name a vertex row outside [0, {v})")
+    raise_invalid_faces(hdr[3], v)
     return workspace, hdr[0], hdr[1], hdr[2]
 
 
@@ -134,10 +114,7 @@ def simplify_mesh(vertices, colors=None, faces=None, voxel_size=None, return_ind
     dev = faces.device
     v, f = int(vertices.shape[0]), int(faces.shape[0])
     if v == 0 and f == 0:
-        mesh = _empty_mesh(dev, False)
-        if not return_index:
-            return mesh
-        return mesh + (torch.empty((0,), dtype=torch.int64, device=dev), torch.empty((0,), dtype=torch.int64, device=dev))
+        return empty_mesh_with_index(dev, return_index)
     ws, v2, f2, _ = _count(vertices, colors, faces, voxel, workspace)
     out_v = torch.empty((v2, 3), dtype=torch.float32, device=dev)
     out_c = torch.empty((v2, 3), dtype=torch.uint8, device=dev)

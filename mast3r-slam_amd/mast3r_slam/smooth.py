@@ -32,8 +32,7 @@ import numpy as np
 import torch
 
 from . import _ffi
-from .export import _check_workspace
-from .simplify import _mesh
+from ._mesh_args import check_faces, check_mesh, check_shape3, raise_invalid_faces, take_workspace, unpack_mesh
 
 __all__ = ["smooth_mesh", "mesh_topology", "MeshTopology", "workspace_bytes"]
 
@@ -57,16 +56,6 @@ def workspace_bytes(n_vertices: int, n_faces: int) -> int:
     return b
 
 
-def _workspace(workspace: Optional[torch.Tensor], v: int, f: int, dev) -> torch.Tensor:
-    ws_bytes = workspace_bytes(v, f)
-    if workspace is None:
-        workspace = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
-    _check_workspace(workspace, ws_bytes)
-    if workspace.device != dev:
-        raise ValueError(f"the mesh lives on {dev}, the workspace on {workspace.device}")
-    return workspace
-
-
 def _build(faces: torch.Tensor, v: int, ws: torch.Tensor) -> None:
     f = int(faces.shape[0])
     _ffi.call("m3_mesh_topology_build", _ffi.ptr(faces) if f else None, v, f, _ffi.ptr(ws), ws.numel(), _ffi.stream_ptr())
@@ -82,19 +71,16 @@ def mesh_topology(faces, n_vertices: int, return_edges: bool = False, workspace:
     in between: its only synchronisation.  workspace: a 16-byte aligned uint8 device tensor of
     workspace_bytes(n_vertices, F).  ValueError when a face names a row outside [0, n_vertices); RuntimeError for a
     CPU tensor."""
-    if not isinstance(faces, torch.Tensor) or faces.dtype != torch.int32 or faces.dim() != 2 or faces.shape[1] != 3:
-        got = f"{faces.dtype} {tuple(faces.shape)}" if isinstance(faces, torch.Tensor) else type(faces).__name__
-        raise ValueError(f"faces must be a {torch.int32} [n,3] tensor, got {got}")
+    check_shape3(faces, torch.int32, "faces")                            # reported before a bad n_vertices, the device after it
     v = int(n_vertices)
     if v < 0 or v > MAX_VERTICES:
         raise ValueError(f"n_vertices must lie in 0 ... 2^31 - 1, got {n_vertices}")
-    faces = _ffi.check(faces, torch.int32, "faces")
+    faces = check_faces(faces, shape_checked=True)
     dev, f = faces.device, int(faces.shape[0])
-    ws = _workspace(workspace, v, f, dev)
+    ws = take_workspace(workspace, workspace_bytes(v, f), dev)
     _build(faces, v, ws)
     two_e, n_boundary, n_nonmanifold, invalid = ws[:4 * _HDR_WORDS].view(torch.int32).tolist()     # the one synchronisation
-    if invalid:
-        raise ValueError(f"{invalid} faces name a vertex row outside [0, {v})")
+    raise_invalid_faces(invalid, v)
     e = two_e // 2
     degree = torch.empty((v,), dtype=torch.int32, device=dev)
     boundary = torch.empty((v,), dtype=torch.bool, device=dev)
@@ -152,7 +138,7 @@ def smooth_mesh(vertices, colors=None, faces=None, iterations: int = 10, method:
         raise ValueError(f"pinned must be a {torch.bool} [V] tensor, got {got}")
     whole = isinstance(vertices, (tuple, list)) and len(vertices) >= 3
     mesh_colors, mesh_faces = (vertices[1], vertices[2]) if whole else (colors, faces)      # handed back as they came
-    vertices, _, faces_c = _mesh(vertices, colors, faces)
+    vertices, _, faces_c = check_mesh(*unpack_mesh(vertices, colors, faces))
     dev = faces_c.device
     v, f = int(vertices.shape[0]), int(faces_c.shape[0])
     if pinned is not None:
@@ -164,7 +150,7 @@ def smooth_mesh(vertices, colors=None, faces=None, iterations: int = 10, method:
     out = torch.empty((v, 3), dtype=torch.float32, device=dev)
     if v == 0:
         return out, mesh_colors, mesh_faces
-    ws = _workspace(workspace, v, f, dev)
+    ws = take_workspace(workspace, workspace_bytes(v, f), dev)
     _build(faces_c, v, ws)
     _ffi.call("m3_mesh_smooth_passes", _ffi.ptr(vertices), v, f, _ffi.ptr(ws), ws.numel(), _ffi.ptr(pinned), 1 if fix_boundary else 0,
               m, iterations, lam32, mu32, _ffi.ptr(out), _ffi.stream_ptr())

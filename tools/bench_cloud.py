@@ -40,7 +40,7 @@ from mast3r_slam import _ffi, cloud, export  # noqa: E402
 # A variant of the moment sums as this tool timed it against the shipped one (profiles/cloud_bench.md says what A and B
 # were): radius / voxel -> neighbour pass with moments, device ms, median of the two runs of (A, B).
 TRIED = {"2": (0.2981, 0.3755), "3": (0.5530, 0.6563), "4": (0.8917, 1.0061)}
-KERNELS = ("k_cl_clear", "k_cl_insert", "k_cl_tile_counts", "k_scan_counts", "k_cl_starts", "k_cl_fill", "k_cl_query",
+KERNELS = ("k_fill2", "k_cl_insert", "k_tile_sums", "k_scan_counts", "k_row_starts", "k_cl_fill", "k_cl_query",
            "k_cl_normals", "k_cl_keep_count", "k_cl_keep_scatter")
 
 

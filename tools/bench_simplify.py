@@ -50,7 +50,7 @@ ORIGIN, SIDE, D, K_FUSED, K_MESH = (-2.0, -2.0, 0.5), 4.0, 256, 16, 8
 # cell were merged inside the wave: (case, factor) -> (count stage device ms, median; k_sv_insert average ms or None).
 PER_VERTEX_ATOMICS = {("fused", 2.0): (0.0560, 0.0351), ("fused", 4.0): (0.0573, None), ("fused", 8.0): (0.0693, 0.0546),
                       ("keyframes", 2.0): (0.3243, 0.2751), ("keyframes", 4.0): (0.3317, None), ("keyframes", 8.0): (0.3753, 0.3252)}
-KERNELS = ("k_sv_clear", "k_sv_insert", "k_sv_leaders", "k_sv_faces", "k_sv_count_faces", "k_scan_counts", "k_sv_vertices",
+KERNELS = ("k_fill3", "k_sv_insert", "k_sv_leaders", "k_sv_faces", "k_sv_count_faces", "k_scan_counts", "k_sv_vertices",
            "k_sv_scatter_faces")
 
 

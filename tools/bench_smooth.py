@@ -40,7 +40,7 @@ PASSES = 20
 EARLIER = {"fused": {"A": (0.1966, 0.0446, 0.0765, 0.0205), "B": (0.1596, 0.0199, 0.0769, 0.0217)},
            "keyframes": {"A": (1.3980, 0.3590, 0.7945, 0.0179), "B": (0.9650, 0.0155, 0.7757, 0.0182)},
            "hub": {"A": (10.9507, 0.0049, 0.0517, 10.8652), "B": (2.2886, 0.0139, 0.0500, 2.1741)}}
-KERNELS = ("k_sm_clear", "k_sm_faces", "k_sm_tile_degrees", "k_scan_counts", "k_sm_starts", "k_sm_fill", "k_sm_sort", "k_sm_read", "k_sm_pass", "k_sm_copy")
+KERNELS = ("k_fill2", "k_sm_faces", "k_tile_sums", "k_scan_counts", "k_row_starts", "k_sm_fill", "k_sm_sort", "k_sm_read", "k_sm_pass", "k_sm_copy")
 
 
 def hub_mesh(dev):
