@@ -1,5 +1,6 @@
 // Inverse-pose table and observation planes of the keyframe map, shared by the multi-view consistency filter
-// (consistency.hip) and the volumetric fusion (tsdf.hip): step 1 of the consistency rule.
+// (consistency.hip) and the volumetric fusion (tsdf.hip): step 1 of the consistency rule, with
+// the workspace that holds them and the launches that fill it (section 7s).
 //
 // Include it as consistency.hip does: map_points.h with contraction on (the exporter's context), then
 // `#pragma clang fp contract(off)` and view_dev.h, in a file compiled with -ffp-contract=off.
@@ -50,6 +51,26 @@ __global__ void __launch_bounds__(kThreads) k_cons_plane(const float *const *__r
         for (int j = 0; j < kPts; ++j)
             if (t.n0 + j < N) Dk[j] = d[j];
     }
+}
+
+// ---- host side -------------------------------------------------------------------------------------------------------
+// An empty map is accepted by both passes: K == 0 with any grid.
+inline bool map_or_empty_ok(int K, int N) { return (K == 0 && N >= 1) || map_shape_ok(K, N); }
+
+// Workspace: the inverse-pose table, then the planes (both 16-byte aligned when ws is).  0 for a map that is not
+// accepted, and for the empty one.
+inline int64_t planes_ws_bytes(int K, int N) { return map_or_empty_ok(K, N) ? inv_bytes(K) + (int64_t)K * N * 4 : 0; }
+
+struct Planes { float *inv, *D; };
+
+inline Planes split_planes(void *ws, int K) { return Planes{(float *)ws, (float *)((char *)ws + inv_bytes(K))}; }
+
+// The two launches that fill a Planes for K >= 1 keyframes of N points.
+inline void launch_planes(const float *const *X, const float *const *C, const float *poses, const int32_t *Nk, int K, int N,
+                          int use_thresh, float thresh, float z_min, const Planes &w, hipStream_t st) {
+    const int tiles = m3_cdiv(N, kTile);
+    hipLaunchKernelGGL(k_cons_inverse, dim3(m3_cdiv(K, kThreads)), dim3(kThreads), 0, st, poses, K, w.inv);
+    hipLaunchKernelGGL(k_cons_plane, dim3(K * tiles), dim3(kThreads), 0, st, X, C, Nk, N, tiles, use_thresh, thresh, z_min, w.D);
 }
 
 }  // namespace

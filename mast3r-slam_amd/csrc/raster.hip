@@ -6,8 +6,8 @@
 // integer minima, which commute, so two calls give identical bytes.  Nothing here waits for the host: the view pose is
 // read from device memory and the call can be captured into a graph.
 //
-// Compiled with -ffp-contract=off: the vertex stage, the depth and the colour are separately rounded fp32 operations
-// (tests/raster_twin.py restates them).
+// Compiled with -ffp-contract=off: the depth and the colour are separately rounded fp32 operations (tests/raster_twin.py
+// restates them); the vertex stage projects through view_dev.h.
 #include "common.h"
 #pragma clang fp contract(off)
 #include "view_dev.h"
@@ -32,6 +32,7 @@ struct alignas(16) Rec { int sx, sy; float z; unsigned ok; };
 __global__ void __launch_bounds__(kThreads) k_raster_project(const float *__restrict__ vertices, int64_t V,
                                                               const float *__restrict__ view, float fx, float fy, float cx,
                                                               float cy, float near, float far, Rec *__restrict__ recs) {
+    const Pinhole pin{fx, fy, cx, cy};
     __shared__ float sv[kViewWords];
     if (threadIdx.x == 0) view_inverse(view, sv);
     __syncthreads();
@@ -40,8 +41,8 @@ __global__ void __launch_bounds__(kThreads) k_raster_project(const float *__rest
     const V3<float> c = view_point(sv, V3<float>{vertices[3 * i], vertices[3 * i + 1], vertices[3 * i + 2]});
     const float z = c.z;
     Rec r{0, 0, z, 0u};
-    if (z > near && z < far) {                                                 // NaN fails; near >= 0: z is positive
-        const float u = fx * (c.x / z) + cx, v = fy * (c.y / z) + cy;
+    if (in_depth(z, near, far)) {
+        const float u = image_u(pin, c), v = image_v(pin, c);
         if (fabsf(u) <= kGuard && fabsf(v) <= kGuard) {                         // NaN fails
             r.sx = (int)floorf(u * (float)kSub + 0.5f);
             r.sy = (int)floorf(v * (float)kSub + 0.5f);
@@ -197,7 +198,7 @@ __global__ void __launch_bounds__(kThreads) k_raster_faces(const int32_t *__rest
     }
 }
 
-// A thread owns 4 consecutive output pixels.  The winning face is loaded again and its edge functions recomputed at
+// As k_render_resolve, and for the same reason not a shared frame.  A thread owns 4 consecutive output pixels.  The winning face is loaded again and its edge functions recomputed at
 // the pixel, exactly; the colour is the perspective-correct blend of its vertex colours.
 __global__ void __launch_bounds__(kThreads) k_raster_resolve(const unsigned long long *__restrict__ keys,
                                                               const int32_t *__restrict__ faces,
@@ -286,8 +287,9 @@ int m3_raster_mesh(const float *vertices, const uint8_t *colors, const int32_t *
     M3_REQUIRE(need > 0 && F >= 0 && F <= kMaxRows && ws && rgb && depth);
     M3_REQUIRE((V == 0 || (vertices && colors)) && (F == 0 || (faces && view_pose)));        // an empty mesh is drawn
     M3_REQUIRE(((uintptr_t)ws & 15) == 0 && ws_bytes >= need && (cull == 0 || cull == 1));
-    M3_REQUIRE(fx > 0.f && fy > 0.f && fx < INFINITY && fy < INFINITY && cx == cx && cy == cy && near >= 0.f && near < far);
-    M3_REQUIRE(((bg_r | bg_g | bg_b) & ~255) == 0);
+    const Pinhole pin{fx, fy, cx, cy};
+    M3_REQUIRE(pinhole_ok(pin, false) && depth_range_ok(near, far));           // an infinite cx draws the background
+    M3_REQUIRE(background_ok(bg_r, bg_g, bg_b));
     hipStream_t st = (hipStream_t)stream;
     Rec *recs = (Rec *)ws;                                                      // V records, then the keys: both 16-byte aligned
     unsigned long long *keys = (unsigned long long *)(recs + V);
@@ -301,7 +303,7 @@ int m3_raster_mesh(const float *vertices, const uint8_t *colors, const int32_t *
         const int groups = m3_cdiv(F, kThreads), slices = groups >= kFillGroups ? 1 : min(64, kFillGroups / groups);
         hipLaunchKernelGGL(k_raster_faces, dim3(groups, slices), dim3(kThreads), 0, st, faces, F, recs, V, cull, Hv, Wv, keys);
     }
-    const unsigned bg = (unsigned)bg_r | ((unsigned)bg_g << 8) | ((unsigned)bg_b << 16);
+    const unsigned bg = pack_background(bg_r, bg_g, bg_b);
     hipLaunchKernelGGL(k_raster_resolve, dim3(m3_cdiv(P, 4 * kThreads)), dim3(kThreads), 0, st, keys, faces, recs, V, colors,
                        Wv, P, bg, rgb, depth, index);
     M3_CHECK_LAUNCH("m3_raster_mesh");

@@ -3,9 +3,9 @@
 // atomics are 64-bit integer minima, which commute, so two calls give identical bytes.  Nothing here waits for the
 // host: the view pose is read from device memory and the call can be captured into a graph.
 //
-// Compiled with -ffp-contract=off: the camera transform and the projection are separately rounded fp32 operations
-// (tests/render_twin.py restates them).  The world point is the exporter's: map_points.h is included with contraction
-// on, as map_export.hip compiles it.
+// Compiled with -ffp-contract=off for view_dev.h, which holds the camera transform, the projection and the checks of
+// the camera arguments.  The world point is the exporter's:
+// map_points.h is included with contraction on, as map_export.hip compiles it.
 #include "common.h"
 #pragma clang fp contract(fast)
 #include "sim3_dev.h"
@@ -26,6 +26,7 @@ __global__ void __launch_bounds__(kThreads) k_render_splat(const float *const *_
                                                             const float *__restrict__ view, float fx, float fy, float cx,
                                                             float cy, int Hv, int Wv, float near, float far,
                                                             unsigned long long *keys) {
+    const Pinhole pin{fx, fy, cx, cy};
     __shared__ float sv[kViewWords];
     if (threadIdx.x == 0) view_inverse(view, sv);
     const Tile t = tile_of(N, tiles, X, C);
@@ -40,12 +41,11 @@ __global__ void __launch_bounds__(kThreads) k_render_splat(const float *const *_
     for (int j = 0; j < kPts; ++j) {
         if (!((keep >> j) & 1u)) continue;
         const V3<float> c = view_point(sv, p[j]);
-        const float x = c.x, y = c.y, z = c.z;
-        if (!(z > near && z < far)) continue;                                   // NaN fails; near >= 0: z is positive
-        const float fu = floorf((fx * (x / z) + cx) + 0.5f), fv = floorf((fy * (y / z) + cy) + 0.5f);
+        if (!in_depth(c.z, near, far)) continue;
+        const float fu = nearest_pixel(image_u(pin, c)), fv = nearest_pixel(image_v(pin, c));
         if (!(fu >= (float)-R && fu < (float)(Wv + R) && fv >= (float)-R && fv < (float)(Hv + R))) continue;
         const int px = (int)fu, py = (int)fv;
-        const unsigned long long key = ((unsigned long long)__float_as_uint(z) << 32) | (unsigned)(t.k * N + t.n0 + j);
+        const unsigned long long key = ((unsigned long long)__float_as_uint(c.z) << 32) | (unsigned)(t.k * N + t.n0 + j);
 #pragma unroll
         for (int oy = -R; oy <= R; ++oy) {
             const int yy = py + oy;
@@ -60,6 +60,8 @@ __global__ void __launch_bounds__(kThreads) k_render_splat(const float *const *_
     }
 }
 
+// Shares its frame with k_raster_resolve by copy, not through one template (load, per-key functor, store): that template
+// compiled both kernels to other instructions and measured above the copies' range.
 // A thread owns 4 consecutive output pixels.  LAYOUT as fetch_rgb takes it.
 template <int LAYOUT>
 __global__ void __launch_bounds__(kThreads) k_render_resolve(const unsigned long long *__restrict__ keys,
@@ -136,8 +138,9 @@ int m3_render_map(const float *const *X, const float *const *C, const void *cons
     M3_REQUIRE((use_thresh == 0 || use_thresh == 1) && ((uintptr_t)ws & 15) == 0 && ws_bytes >= m3_render_ws_bytes(Hv, Wv));
     M3_REQUIRE(layout == M3_MAP_IMG_F32_CHW || layout == M3_MAP_IMG_U8_HWC);
     M3_REQUIRE(point_size == 1 || point_size == 3 || point_size == 5 || point_size == 7);
-    M3_REQUIRE(fx > 0.f && fy > 0.f && fx < INFINITY && fy < INFINITY && cx == cx && cy == cy && near >= 0.f && near < far);
-    M3_REQUIRE(((bg_r | bg_g | bg_b) & ~255) == 0);
+    const Pinhole pin{fx, fy, cx, cy};
+    M3_REQUIRE(pinhole_ok(pin, false) && depth_range_ok(near, far));           // an infinite cx draws the background
+    M3_REQUIRE(background_ok(bg_r, bg_g, bg_b));
     hipStream_t st = (hipStream_t)stream;
     unsigned long long *keys = (unsigned long long *)ws;
     const int64_t P = (int64_t)Hv * Wv;
@@ -154,7 +157,7 @@ int m3_render_map(const float *const *X, const float *const *C, const void *cons
         else M3_SPLAT(7);
 #undef M3_SPLAT
     }
-    const unsigned bg = (unsigned)bg_r | ((unsigned)bg_g << 8) | ((unsigned)bg_b << 16);
+    const unsigned bg = pack_background(bg_r, bg_g, bg_b);
     const dim3 rgrid(m3_cdiv(P, 4 * kThreads));
     if (layout == M3_MAP_IMG_F32_CHW)
         hipLaunchKernelGGL(k_render_resolve<0>, rgrid, dim3(kThreads), 0, st, keys, img, K > 0 ? N : 1, P, bg, rgb, depth, index);

@@ -97,9 +97,6 @@ inline bool vol_ok(float ox, float oy, float oz, float vs, int Dx, int Dy, int D
     return true;
 }
 
-// An empty map is accepted: it writes the unobserved volume.
-inline bool map_ok(int K, int N) { return (K == 0 && N >= 1) || map_shape_ok(K, N); }
-
 // The thread's voxel: false beyond the volume.
 __device__ __forceinline__ bool voxel_of(const Vol &v, int &i, int &iz, int &iy, int &ix) {
     i = blockIdx.x * kThreads + threadIdx.x;                                     // < 2^30 + 256
@@ -113,7 +110,8 @@ __device__ __forceinline__ bool voxel_of(const Vol &v, int &i, int &iz, int &iy,
 
 // One thread per voxel.  The keyframe loop is outermost; the inverse pose, the scale and the image pointer depend on j
 // alone, so they come through wave-uniform (scalar) loads.  Per used pair: the transform, one divide pair, one 4-byte
-// gather from D, one divide by trunc and one colour gather.
+// gather from D, one divide by trunc and one colour gather.  The lookup is k_cons_count's, written out in both and not
+// shared as one observe(): see the comment there.
 template <int LAYOUT>
 __global__ void __launch_bounds__(kThreads) k_tsdf_voxels(const void *const *__restrict__ img, const float *__restrict__ poses,
                                                            int K, int N, int H, int W, float fx, float fy, float cx, float cy,
@@ -125,6 +123,7 @@ __global__ void __launch_bounds__(kThreads) k_tsdf_voxels(const void *const *__r
     if (!voxel_of(vol, i, iz, iy, ix)) return;
     const V3<float> p{vol.ox + ((float)ix + 0.5f) * vol.vs, vol.oy + ((float)iy + 0.5f) * vol.vs,
                       vol.oz + ((float)iz + 0.5f) * vol.vs};
+    const Pinhole pin{fx, fy, cx, cy};
     const float fW = (float)W, fH = (float)H, lo = -trunc;
     float sum = 0.f;
     unsigned n = 0u, r = 0u, g = 0u, b = 0u, cn = 0u;
@@ -132,7 +131,7 @@ __global__ void __launch_bounds__(kThreads) k_tsdf_voxels(const void *const *__r
         const float *sv = inv + (size_t)kInvStride * j;
         const V3<float> c = view_point(sv, p);
         if (!(c.z > z_min)) continue;                                            // NaN fails
-        const float fu = floorf((fx * (c.x / c.z) + cx) + 0.5f), fv = floorf((fy * (c.y / c.z) + cy) + 0.5f);
+        const float fu = nearest_pixel(image_u(pin, c)), fv = nearest_pixel(image_v(pin, c));
         if (!(fu >= 0.f && fu < fW && fv >= 0.f && fv < fH)) continue;           // as floats: u may be huge or NaN
         const int m = (int)fv * W + (int)fu;
         const float d = D[(size_t)j * N + m];
@@ -312,9 +311,7 @@ __global__ void __launch_bounds__(kThreads) k_tsdf_faces(Vol vol, const unsigned
 
 extern "C" {
 
-int64_t m3_tsdf_integrate_ws_bytes(int K, int N) {
-    return map_shape_ok(K, N) ? inv_bytes(K) + (int64_t)K * N * 4 : 0;
-}
+int64_t m3_tsdf_integrate_ws_bytes(int K, int N) { return planes_ws_bytes(K, N); }
 
 int m3_tsdf_integrate_launches(void) { return kIntegrateLaunches; }
 
@@ -324,32 +321,28 @@ int m3_tsdf_integrate(const float *const *X, const float *const *C, const void *
                       int Dy, int Dz, void *ws, int64_t ws_bytes, float *tsdf, int32_t *weight, uint8_t *color,
                       uint8_t *colored, void *stream) {
     Vol vol;
-    M3_REQUIRE(H >= 1 && W >= 1 && H <= (1 << 24) && W <= (1 << 24) && (int64_t)H * W <= 0x7fffffff && map_ok(K, H * W));
+    const Pinhole pin{fx, fy, cx, cy};
+    M3_REQUIRE(grid_ok(H, W) && map_or_empty_ok(K, H * W));                      // an empty map writes the unobserved volume
     M3_REQUIRE((use_thresh == 0 || use_thresh == 1) && (layout == M3_MAP_IMG_F32_CHW || layout == M3_MAP_IMG_U8_HWC));
-    M3_REQUIRE(fx > 0.f && fy > 0.f && fx < INFINITY && fy < INFINITY && cx - cx == 0.f && cy - cy == 0.f);
+    M3_REQUIRE(pinhole_ok(pin, true));
     M3_REQUIRE(z_min >= 0.f && z_min < INFINITY && trunc > 0.f && trunc < INFINITY);
     M3_REQUIRE(vol_ok(ox, oy, oz, voxel_size, Dx, Dy, Dz, vol));
     M3_REQUIRE(tsdf && weight && color && ((uintptr_t)tsdf & 3) == 0 && ((uintptr_t)weight & 3) == 0);
     const int N = H * W;
     if (K > 0) {
         M3_REQUIRE(X && C && img && poses && Nk && ws);
-        M3_REQUIRE(((uintptr_t)ws & 15) == 0 && ws_bytes >= m3_tsdf_integrate_ws_bytes(K, N));
+        M3_REQUIRE(((uintptr_t)ws & 15) == 0 && ws_bytes >= planes_ws_bytes(K, N));
     }
     hipStream_t st = (hipStream_t)stream;
-    float *inv = (float *)ws;
-    float *D = K > 0 ? (float *)((char *)ws + inv_bytes(K)) : nullptr;
+    const Planes w = K > 0 ? split_planes(ws, K) : Planes{nullptr, nullptr};     // an empty map: ws may be null
     const dim3 block(kThreads), vgrid(m3_cdiv(vol.total, kThreads));
-    if (K > 0) {
-        const int tiles = m3_cdiv(N, kTile);
-        hipLaunchKernelGGL(k_cons_inverse, dim3(m3_cdiv(K, kThreads)), block, 0, st, poses, K, inv);
-        hipLaunchKernelGGL(k_cons_plane, dim3(K * tiles), block, 0, st, X, C, Nk, N, tiles, use_thresh, thresh, z_min, D);
-    }
+    if (K > 0) launch_planes(X, C, poses, Nk, K, N, use_thresh, thresh, z_min, w, st);
     if (layout == M3_MAP_IMG_F32_CHW)
-        hipLaunchKernelGGL(k_tsdf_voxels<0>, vgrid, block, 0, st, img, poses, K, N, H, W, fx, fy, cx, cy, z_min, vol, trunc, inv,
-                           D, tsdf, weight, color, colored);
+        hipLaunchKernelGGL(k_tsdf_voxels<0>, vgrid, block, 0, st, img, poses, K, N, H, W, fx, fy, cx, cy, z_min, vol, trunc, w.inv,
+                           w.D, tsdf, weight, color, colored);
     else
-        hipLaunchKernelGGL(k_tsdf_voxels<1>, vgrid, block, 0, st, img, poses, K, N, H, W, fx, fy, cx, cy, z_min, vol, trunc, inv,
-                           D, tsdf, weight, color, colored);
+        hipLaunchKernelGGL(k_tsdf_voxels<1>, vgrid, block, 0, st, img, poses, K, N, H, W, fx, fy, cx, cy, z_min, vol, trunc, w.inv,
+                           w.D, tsdf, weight, color, colored);
     M3_CHECK_LAUNCH("m3_tsdf_integrate");
     return M3_OK;
 }

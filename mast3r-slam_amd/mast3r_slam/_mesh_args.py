@@ -71,13 +71,14 @@ def check_mesh(vertices, colors, faces, rows_first: bool = False):
     return vertices, colors, faces
 
 
-def take_workspace(workspace: Optional[torch.Tensor], ws_bytes: int, device, owner: str = "the mesh lives") -> torch.Tensor:
+def take_workspace(workspace: Optional[torch.Tensor], ws_bytes: int, device,
+                   owner: Optional[str] = "the mesh lives") -> torch.Tensor:
     """The caller's workspace, checked - a contiguous, 16-byte aligned uint8 tensor of at least ws_bytes on `device` - or
-    a new one."""
+    a new one.  owner None: the device is not compared (the view passes and the focal estimate never did)."""
     if workspace is None:
         workspace = torch.empty((ws_bytes,), dtype=torch.uint8, device=device)
     _check_workspace(workspace, ws_bytes)
-    if workspace.device != device:
+    if owner is not None and workspace.device != device:
         raise ValueError(f"{owner} on {device}, the workspace on {workspace.device}")
     return workspace
 

@@ -31,8 +31,9 @@ from typing import Optional
 import torch
 
 from . import _ffi
-from .export import _MapTables, _check_workspace, _conf_gate, _grid_size, _map_tables, _with_pointmap
-from .render import _pinhole
+from ._mesh_args import take_workspace
+from ._view_args import _map_frames, map_camera, planes_workspace_bytes
+from .export import _conf_gate
 
 __all__ = ["multiview_support", "consistent_keyframes", "nearest_neighbours", "ConsistentFrame"]
 
@@ -91,10 +92,7 @@ def _all_others(k: int, dev) -> torch.Tensor:
 
 def workspace_bytes(k: int, n: int) -> int:
     """Bytes of the inverse-pose table and the observation planes multiview_support needs for k keyframes of n pixels."""
-    b = int(_ffi.lib().m3_consistency_ws_bytes(int(k), int(n)))
-    if b <= 0 and k:
-        raise ValueError(f"unsupported map of {k} x {n} points (limit 2^31 - 1 points)")
-    return b
+    return planes_workspace_bytes("m3_consistency_ws_bytes", k, n)
 
 
 def multiview_support(keyframes, K, neighbours=8, c_conf_threshold: Optional[float] = 1.5, depth_rtol: float = 0.03,
@@ -119,24 +117,13 @@ def multiview_support(keyframes, K, neighbours=8, c_conf_threshold: Optional[flo
     RuntimeError for CPU tensors.  No keyframes: three empty [0,0] tensors."""
     rtol, mv, mc, z_min = _scalars(depth_rtol, min_views, max_conflicts, z_min)
     _check_neighbours(neighbours)
-    frames = keyframes.frames if isinstance(keyframes, _MapTables) else _with_pointmap(keyframes)
+    frames = _map_frames(keyframes)
     if not frames:
         dev = "cuda" if torch.cuda.is_available() else "cpu"
         return (torch.empty((0, 0), dtype=torch.uint8, device=dev), torch.empty((0, 0), dtype=torch.uint8, device=dev),
                 torch.empty((0, 0), dtype=torch.float32, device=dev))
-    h, w = _grid_size(frames)                                            # ValueError: sizes differ, or N != H * W
-    if isinstance(K, str):
-        if K != "estimate":
-            raise ValueError(f"K must be a 3 x 3 matrix, (fx, fy, cx, cy) or 'estimate', got {K!r}")
-    else:
-        K = _pinhole(K, (h, w))
-    m = keyframes if isinstance(keyframes, _MapTables) else _map_tables(frames)   # RuntimeError: CPU tensors
-    if isinstance(K, str):
-        from .intrinsics import estimate_intrinsics
-        K = _pinhole(estimate_intrinsics(m, c_conf_threshold=c_conf_threshold).K, (h, w))
-    fx, fy, cx, cy = K
+    m, (h, w), (fx, fy, cx, cy), poses = map_camera(keyframes, frames, K, c_conf_threshold)
     k, n, dev = m.k, m.n, m.device
-    poses = torch.cat([_ffi.check(f.T_WC.reshape(1, 8), torch.float32, "T_WC") for f in m.frames])
     if neighbours is None:
         if k - 1 > MAX_NEIGHBOURS:
             raise ValueError(f"neighbours=None needs V = {k - 1} > {MAX_NEIGHBOURS}: pass a number of nearest neighbours")
@@ -155,9 +142,7 @@ def multiview_support(keyframes, K, neighbours=8, c_conf_threshold: Optional[flo
     for t, dt, name in zip(out, (torch.uint8, torch.uint8, torch.float32), ("support", "conflict", "conf")):
         if _ffi.check(t, dt, f"out {name}", (k, n)).data_ptr() != t.data_ptr() or t.data_ptr() % 16:
             raise ValueError(f"out {name} must be contiguous and 16-byte aligned")
-    if workspace is None:
-        workspace = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
-    _check_workspace(workspace, ws_bytes)
+    workspace = take_workspace(workspace, ws_bytes, dev, owner=None)
     use, thr = _conf_gate(c_conf_threshold)
     _ffi.call("m3_consistency", _ffi.ptr(m.table[0]), _ffi.ptr(m.table[1]), _ffi.ptr(poses), _ffi.ptr(m.nk), k, h, w, use, thr,
               fx, fy, cx, cy, _ffi.ptr(nbr) if v else None, v, z_min, rtol, mv, mc, _ffi.ptr(workspace), ws_bytes,
@@ -184,6 +169,6 @@ def consistent_keyframes(keyframes, K, **kw) -> list:
     multiview_support(keyframes, K, **kw).  Anything that takes keyframes takes them: collect_map, collect_mesh,
     render_map, estimate_focal; a rejected point has confidence -inf and fails every finite threshold (pass -inf, not
     None, to mean "every kept point")."""
-    frames = keyframes.frames if isinstance(keyframes, _MapTables) else _with_pointmap(keyframes)
+    frames = _map_frames(keyframes)
     conf = multiview_support(keyframes, K, **kw)[2]
     return [ConsistentFrame(f, conf[i].reshape(-1, 1)) for i, f in enumerate(frames)]

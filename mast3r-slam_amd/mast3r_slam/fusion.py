@@ -39,8 +39,9 @@ import numpy as np
 import torch
 
 from . import _ffi
-from .export import _MapTables, _check_workspace, _conf_gate, _empty_mesh, _grid_size, _map_tables, _with_pointmap, collect_map
-from .render import _pinhole
+from ._mesh_args import take_workspace
+from ._view_args import _check_K_word, _map_frames, map_camera, planes_workspace_bytes
+from .export import _MapTables, _conf_gate, _empty_mesh, collect_map
 
 __all__ = ["fuse_tsdf", "extract_surface", "TSDFVolume", "volume_grid", "empty_volume", "map_bounds"]
 
@@ -144,10 +145,7 @@ def map_bounds(keyframes, c_conf_threshold: Optional[float] = 1.5):
 
 def workspace_bytes(k: int, n: int) -> int:
     """Bytes of the inverse-pose table and the observation planes fuse_tsdf needs for k keyframes of n pixels."""
-    b = int(_ffi.lib().m3_tsdf_integrate_ws_bytes(int(k), int(n)))
-    if b <= 0 and k:
-        raise ValueError(f"unsupported map of {k} x {n} points (limit 2^31 - 1 points)")
-    return b
+    return planes_workspace_bytes("m3_tsdf_integrate_ws_bytes", k, n)
 
 
 def _check_volume(v: TSDFVolume, shape, need_colored: bool) -> None:
@@ -185,9 +183,8 @@ def fuse_tsdf(keyframes, K, voxel_size: float, bounds=None, trunc: Optional[floa
     z_min = float(z_min)
     if not 0.0 <= z_min < math.inf:
         raise ValueError(f"z_min must be >= 0 and finite, got {z_min}")
-    frames = keyframes.frames if isinstance(keyframes, _MapTables) else _with_pointmap(keyframes)
-    if isinstance(K, str) and K != "estimate":
-        raise ValueError(f"K must be a 3 x 3 matrix, (fx, fy, cx, cy) or 'estimate', got {K!r}")
+    frames = _map_frames(keyframes)
+    _check_K_word(K)                                                   # before the grid: the order this call has always had
     if bounds is not None:
         origin, shape = volume_grid(bounds, vs, tr)
         origin = tuple(float(v) for v in origin)
@@ -201,19 +198,7 @@ def fuse_tsdf(keyframes, K, voxel_size: float, bounds=None, trunc: Optional[floa
                             out.dims != tuple(shape) or _f32(out.voxel_size) != vs or _f32(out.trunc) != tr):
         raise ValueError(f"out must be a TSDFVolume of this call's grid: origin {origin}, dims {tuple(shape)}, voxel_size {vs}, "
                          f"trunc {tr}; the call asks for another one than out has")
-    h, w, m = 1, 1, None
-    if frames:
-        h, w = _grid_size(frames)                                      # ValueError: sizes differ, or N != H * W
-        if not isinstance(K, str):
-            K = _pinhole(K, (h, w))
-        m = keyframes if isinstance(keyframes, _MapTables) else _map_tables(frames)   # RuntimeError: CPU tensors
-        if isinstance(K, str):
-            from .intrinsics import estimate_intrinsics
-            K = _pinhole(estimate_intrinsics(m, c_conf_threshold=c_conf_threshold).K, (h, w))
-    elif isinstance(K, str):
-        K = (1.0, 1.0, 0.0, 0.0)                                       # no keyframe projects anything
-    else:
-        K = _pinhole(K, (h, w))
+    m, (h, w), (fx, fy, cx, cy), poses = map_camera(keyframes, frames, K, c_conf_threshold)
     if origin is None:
         if m is None:
             raise ValueError("no keyframes: the volume needs bounds or out")
@@ -225,15 +210,11 @@ def fuse_tsdf(keyframes, K, voxel_size: float, bounds=None, trunc: Optional[floa
     else:
         _check_volume(out, tuple(shape), need_colored=False)
     k = m.k if m is not None else 0
-    fx, fy, cx, cy = K
     use, thr = _conf_gate(c_conf_threshold)
     dz, dy, dx = shape
     if k:
         ws_bytes = workspace_bytes(k, m.n)
-        if workspace is None:
-            workspace = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
-        _check_workspace(workspace, ws_bytes)
-        poses = torch.cat([_ffi.check(f.T_WC.reshape(1, 8), torch.float32, "T_WC") for f in m.frames])
+        workspace = take_workspace(workspace, ws_bytes, dev, owner=None)
         tables = (_ffi.ptr(m.table[0]), _ffi.ptr(m.table[1]), _ffi.ptr(m.table[2]), _ffi.ptr(poses), _ffi.ptr(m.nk))
         layout = m.layout
     else:

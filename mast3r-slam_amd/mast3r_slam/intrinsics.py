@@ -26,7 +26,8 @@ import numpy as np
 import torch
 
 from . import _ffi
-from .export import _MapTables, _check_workspace, _conf_gate, _map_tables, _with_pointmap
+from ._mesh_args import take_workspace
+from .export import _MapTables, _conf_gate, _map_tables, _with_pointmap
 from .render import _frame_size
 
 __all__ = ["estimate_focal", "estimate_intrinsics", "intrinsics_from_rows", "IntrinsicsEstimate"]
@@ -116,9 +117,7 @@ def estimate_focal(keyframes, size: Optional[Sequence[int]] = None, principal_po
         out = torch.empty((m.k, 4), dtype=torch.float64, device=dev)
     if _ffi.check(out, torch.float64, "out", (m.k, 4)).data_ptr() != out.data_ptr():
         raise ValueError("out must be contiguous")
-    if workspace is None:
-        workspace = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
-    _check_workspace(workspace, ws_bytes)
+    workspace = take_workspace(workspace, ws_bytes, dev, owner=None)
     use, thr = _conf_gate(c_conf_threshold)
     _ffi.call("m3_focal_estimate", _ffi.ptr(m.table[0]), _ffi.ptr(m.table[1]), _ffi.ptr(m.nk), m.k, m.n, size[0], size[1],
               use, thr, pp[0], pp[1], z_min, iters, _ffi.ptr(workspace), ws_bytes, _ffi.ptr(out), _ffi.stream_ptr())

@@ -27,7 +27,9 @@ import numpy as np
 import torch
 
 from . import _ffi
-from .export import _MapTables, _check_workspace, _conf_gate, _map_tables, collect_mesh
+from ._mesh_args import check_shape3, take_workspace
+from ._view_args import _outputs, _pinhole, _view_args, _view_pose
+from .export import _MapTables, _conf_gate, _map_tables, collect_mesh
 
 __all__ = ["render_map", "render_mesh", "mesh_workspace_bytes", "default_intrinsics", "look_at", "behind", "depth_to_rgb",
            "save_image", "ViewRecorder"]
@@ -92,22 +94,6 @@ def behind(T_WC: torch.Tensor, distance: float = 1.0, height: float = 0.25) -> t
     return torch.cat([t + v + w * u + torch.linalg.cross(qv, u), T[:, 3:7], torch.ones_like(w)], dim=1)
 
 
-def _pinhole(K, size):
-    if K is None:
-        return default_intrinsics(size)
-    if isinstance(K, torch.Tensor):
-        K = K.detach().cpu().tolist()
-    K = np.asarray(K, dtype=np.float64)
-    if K.shape == (3, 3):
-        K = np.array([K[0, 0], K[1, 1], K[0, 2], K[1, 2]])
-    if K.shape != (4,):
-        raise ValueError(f"K must be (fx, fy, cx, cy) or a 3 x 3 matrix, got shape {K.shape}")
-    fx, fy, cx, cy = (float(v) for v in K)
-    if not (0.0 < fx < math.inf and 0.0 < fy < math.inf and math.isfinite(cx) and math.isfinite(cy)):
-        raise ValueError(f"focal lengths must be positive and the principal point finite, got {(fx, fy, cx, cy)}")
-    return fx, fy, cx, cy
-
-
 def map_tables(keyframes):
     """The device tables render_map builds from `keyframes` on every call (three small host-to-device copies), built once:
     pass the result as `keyframes` to draw the same map again without them, e.g. inside a graph capture, where a copy
@@ -122,43 +108,6 @@ def workspace_bytes(size: Sequence[int]) -> int:
     if n <= 0:
         raise ValueError(f"unsupported view size {tuple(size)} (each side 1 ... 16384)")
     return n
-
-
-def _view_args(size, K, near, far, background):
-    """(H, W, (fx, fy, cx, cy), near, far, background) of a view, checked: ValueError for anything a renderer rejects."""
-    if len(size) != 2 or int(size[0]) <= 0 or int(size[1]) <= 0:
-        raise ValueError(f"size must be (H, W) with positive entries, got {size}")
-    hv, wv = int(size[0]), int(size[1])
-    pinhole = _pinhole(K, (hv, wv))
-    near, far = float(near), float(far)
-    if not (0.0 <= near < far):
-        raise ValueError(f"need 0 <= near < far, got near={near}, far={far}")
-    bg = tuple(int(v) for v in background)
-    if len(bg) != 3 or any(v < 0 or v > 255 for v in bg):
-        raise ValueError(f"background must be three values in 0 ... 255, got {background}")
-    return hv, wv, pinhole, near, far, bg
-
-
-def _outputs(out, return_index: bool, hv: int, wv: int, dev):
-    """`out` checked, or freshly allocated: (rgb, depth[, index])."""
-    if out is None:
-        out = (torch.empty((hv, wv, 3), dtype=torch.uint8, device=dev), torch.empty((hv, wv), dtype=torch.float32, device=dev))
-        if return_index:
-            out += (torch.empty((hv, wv), dtype=torch.int64, device=dev),)
-    if len(out) != (3 if return_index else 2):
-        raise ValueError(f"out must hold {'rgb, depth and index' if return_index else 'rgb and depth'}")
-    shapes = ((hv, wv, 3), (hv, wv), (hv, wv))
-    for t, dt, name, shape in zip(out, (torch.uint8, torch.float32, torch.int64), ("rgb", "depth", "index"), shapes):
-        if _ffi.check(t, dt, f"out {name}", shape).data_ptr() != t.data_ptr():
-            raise ValueError(f"out {name} must be contiguous")
-    return tuple(out)
-
-
-def _view_pose(T_WC) -> torch.Tensor:
-    view = _ffi.check(T_WC, torch.float32, "T_WC").reshape(-1)
-    if view.numel() != 8:
-        raise ValueError(f"T_WC must have 8 elements (t, q xyzw, s), got {tuple(T_WC.shape)}")
-    return view
 
 
 def render_map(keyframes, T_WC, K, size, c_conf_threshold: Optional[float] = 1.5, point_size: int = 1,
@@ -181,9 +130,7 @@ def render_map(keyframes, T_WC, K, size, c_conf_threshold: Optional[float] = 1.5
     if m is not None and m.device != dev:
         raise ValueError(f"T_WC lives on {dev}, the map on {m.device}")
     out = _outputs(out, return_index, hv, wv, dev)
-    if workspace is None:
-        workspace = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
-    _check_workspace(workspace, ws_bytes)
+    workspace = take_workspace(workspace, ws_bytes, dev, owner=None)
     use, thr = _conf_gate(c_conf_threshold)
     if m is None:
         tabs, poses, nk, k, n, layout = (None, None, None), None, None, 0, 1, 0
@@ -250,9 +197,7 @@ def render_mesh(vertices, colors=None, faces=None, T_WC=None, K=None, size=None,
     if not set(shade_kw or {}) <= {"light", "ambient", "two_sided", "albedo", "colors"}:
         raise ValueError(f"shade_kw holds shade_vertices' light, ambient, two_sided, albedo and colors, got {sorted(shade_kw)}")
     for t, dt, name in ((vertices, torch.float32, "vertices"), (colors, torch.uint8, "colors"), (faces, torch.int32, "faces")):
-        if not isinstance(t, torch.Tensor) or t.dtype != dt or t.dim() != 2 or t.shape[1] != 3:
-            got = f"{t.dtype} {tuple(t.shape)}" if isinstance(t, torch.Tensor) else type(t).__name__
-            raise ValueError(f"{name} must be a {dt} [n,3] tensor, got {got}")
+        check_shape3(t, dt, name)
     if colors.shape[0] != vertices.shape[0]:
         raise ValueError(f"vertices has {vertices.shape[0]} rows, colors {colors.shape[0]}")
     v, f = int(vertices.shape[0]), int(faces.shape[0])
@@ -270,9 +215,7 @@ def render_mesh(vertices, colors=None, faces=None, T_WC=None, K=None, size=None,
         kw = dict(colors=colors, T_WC=view, mode="normals" if shading == "normals" else "lambert")
         kw.update(shade_kw or {})
         colors = _normals.shade_vertices(vertices, normals, **kw)
-    if workspace is None:
-        workspace = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
-    _check_workspace(workspace, ws_bytes)
+    workspace = take_workspace(workspace, ws_bytes, dev, owner=None)
     _ffi.call("m3_raster_mesh", _ffi.ptr(vertices) if v else None, _ffi.ptr(colors) if v else None, _ffi.ptr(faces) if f else None,
               v, f, _ffi.ptr(view), fx, fy, cx, cy, hv, wv, near, far, CULL[cull], bg[0], bg[1], bg[2], _ffi.ptr(workspace),
               ws_bytes, _ffi.ptr(out[0]), _ffi.ptr(out[1]), _ffi.ptr(out[2]) if return_index else None, _ffi.stream_ptr())
